@@ -16,10 +16,17 @@ payload + reference-exact Example decode + columnar gather of every value), inpu
 torch.distributed.run; under torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE. RCCL carries only the
 barrier and the max-over-ranks time and byte sums.
 
-At N = 1 the same run also measures the other configs under ``configs`` (rank 0's share of the
-directory at N = 8 decoded alone, one resident 65,536-record C1 file, C2 flowers-shaped records, C3
-wide-schema records, the C2-shaped 256-file directory), each with its own roofline and CPU baseline.
-Prints ONE JSON line (rank 0).
+A plain run does what the headline figure needs and no more: it sets up the resident shard, warms up,
+times ``--steps`` steps and prints ONE JSON line (rank 0) with ``metric``, ``value``, ``unit``,
+``higher_is_better``, ``dtype`` and ``ms_per_step`` (the milliseconds of one timed step).
+``--dump-outputs DIR`` then writes what the last timed step computed as ``DIR/<name>.npy``
+(``dump_outputs``). The inputs are the same from run to run, so two builds compare output for output.
+
+``--full`` adds every other measurement to the line: the consumer's confirmation and device-view
+costs, per-kernel times with the dominant kernel's roofline, the achievable streaming read, the CPU
+baseline, and at N = 1 the other configs under ``configs`` (rank 0's share of the directory at N = 8
+decoded alone, one resident 65,536-record C1 file, C2 flowers-shaped records, C3 wide-schema records,
+the C2-shaped 256-file directory), each with its own roofline and CPU baseline.
 """
 
 from __future__ import annotations
@@ -59,14 +66,19 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=2, help="HIP streams the shard's batches are spread over")
     ap.add_argument("--only", default=None, choices=["c4", "c1file", "c2", "c3", "c4c2", "c4of8", "c4of8v"],
                     help="measure one config only and report it as the headline (profiling runs)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the per-config measurements at N = 1")
-    ap.add_argument("--profile-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: consumer costs, per-kernel times and "
+                         "roofline, the streaming read, CPU baselines and (N = 1) the other configs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the per-config measurements at N = 1")
+    ap.add_argument("--profile-steps", type=int, default=5, help="--full: steps of the per-kernel times")
     # record offsets handed to the decode: "auto" = u32 ends of back-to-back records (the framing
     # index of whole files; 4 B per record), else u32 (start, end) pairs; "u64" = the u64 pairs of
     # tfrg_decode_device (16 B per record)
     ap.add_argument("--offsets", default="auto", choices=["auto", "u32", "u64"])
-    ap.add_argument("--cpu-seconds", type=float, default=1.5, help="wall budget of each CPU baseline")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=1.5, help="--full: wall budget of each CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
     return ap.parse_args(argv)
 
 
@@ -81,6 +93,7 @@ class Workload:
         self.name, self.desc = name, desc
         self.buf, self.starts, self.ends = buf, starts, ends
         self.units = units  # [(first record, end record)]
+        self._sz = None
 
     @property
     def n(self) -> int:
@@ -88,7 +101,18 @@ class Workload:
 
     @property
     def framed_bytes(self) -> int:
-        return int((self.ends - self.starts).sum())
+        return self._sizes()[0]
+
+    @property
+    def max_record(self) -> int:
+        return self._sizes()[1]
+
+    def _sizes(self) -> tuple[int, int]:
+        """(sum, max) of end - start, computed once (a pass over every record of the shard)."""
+        if self._sz is None:
+            sz = self.ends - self.starts
+            self._sz = (int(sz.sum()), int(sz.max()))
+        return self._sz
 
 
 def _gen(fn, items, threads=16):
@@ -218,11 +242,14 @@ def _check(infos) -> None:
         assert info.n_errors == 0 and info.n_miss_records == 0 and info.scan_timeout == 0, "decode check failed"
 
 
-def measure(ctx: Ctx, w: Workload, steps: int, warmup: int, prof_steps: int, templates: bool = True) -> dict:
+def measure(ctx: Ctx, w: Workload, steps: int, warmup: int, prof_steps: int, templates: bool = True,
+            full: bool = True, dump: str | None = None) -> dict:
     """Decode the rank's resident shard `steps` times. The shard is cut into record-range batches
     of <= --batch-bytes (tfr_reader.shard.plan_batches), batch k decoded by its own context on
     stream k % --streams; a step is the decode of every batch. templates=False: no record-shape
-    templates (every lane record takes the canonical walk; results identical)."""
+    templates (every lane record takes the canonical walk; results identical). dump: write the last
+    timed step's results there (dump_outputs). full=False: return after the timed steps, without
+    the consumer, per-kernel and roofline figures (each takes steps of its own)."""
     from tfr_reader import hip, shard
 
     dev, main = ctx.dev, ctx.stream
@@ -250,10 +277,12 @@ def measure(ctx: Ctx, w: Workload, steps: int, warmup: int, prof_steps: int, tem
         for d in sd._decoders(len(plan)):
             d.set_templates(False)
     sd.learn(plan, w.buf, w.starts, w.ends)
+    # (for the roofline's bytes; a 4,096-record decode, kept in a plain run too so that the first
+    # context enters the warm-up in the same state either way)
     present = _present_lists(sd.decs[0], w)
     side = [torch.cuda.Stream(dev) for _ in range(max(1, ctx.args.streams))]
     handles = [s.cuda_stream for s in side]
-    max_record = int((w.ends - w.starts).max())  # (the host knows its ranges: no large-record launch for C1)
+    max_record = w.max_record  # (the host knows its ranges: no large-record launch for C1)
     for d in sd._decoders(len(plan)):
         d.set_record_bound(max_record)
 
@@ -316,6 +345,38 @@ def measure(ctx: Ctx, w: Workload, steps: int, warmup: int, prof_steps: int, tem
     # optimistic decode that left records; the steps decode the same input, so the confirmation of
     # the last one stands for all of them)
     assert reruns == 0, f"{reruns} decodes re-run after the timed region"
+    if dump:
+        dump_outputs(dump, sd, plan, w, ctx)
+
+    framed = w.framed_bytes
+    ms_step = elapsed / steps * 1e3
+    out = {
+        "workload": w.desc,
+        "records": w.n,
+        "tpl_groups_missed": sum(int(i.tpl_groups_missed) for i in infos),
+        "framed_bytes": framed,
+        "batches": len(plan),
+        "batch_bytes_max": int((plan[:, 3] - plan[:, 2]).max()),
+        "offsets": {"mode": omode, "bytes_per_record": off_bytes},
+        # device memory of the decode contexts (value columns sized from the learning sample), and
+        # of the resident input, in multiples of the input
+        "device_memory": {"contexts_bytes": dev_bytes, "x_input": round(dev_bytes / max(nbytes, 1), 3),
+                          "reruns": reruns},
+        # optimistic decodes (k_tpl_lane alone, confirmed by tfrg_result_info)
+        "optimistic": os.environ.get("TFRG_OPTIMISTIC", "1") != "0",
+        "streams": len(handles),
+        "ms_per_step": round(ms_step, 4),
+        # (the step is the larger of the host's wall clock and the GPU events: a small batch's step
+        # can be the host's enqueue rate)
+        "step_parts_ms": {"host_wall": round(wall / steps * 1e3, 4), "gpu_events": round(ev_s / steps * 1e3, 4)},
+        "GiB_s": round(framed / (ms_step / 1e3) / 2**30, 3),
+        "examples_per_s": round(w.n / (ms_step / 1e3), 1),
+        "_elapsed": elapsed,
+        "_d_bytes": d_bytes,
+    }
+    if not full:
+        sd.close()
+        return out
 
     # ---- what a device-resident consumer pays on top of the step (not part of `value`): an
     # optimistic decode is complete once confirmed (tfrg_result_info: one host-synchronizing read of
@@ -371,7 +432,6 @@ def measure(ctx: Ctx, w: Workload, steps: int, warmup: int, prof_steps: int, tem
     kt = [sum(int(i.kind_totals[k]) for i in infos) for k in range(4)]
     sz = w.ends - w.starts
     big_bytes = int(sz[sz > hip.DEFAULT_LANE_MAX].sum())
-    framed = w.framed_bytes
     small_bytes = framed - big_bytes
     n_small = n - n_big
     n_vals = kt[3] + kt[2] + kt[1]
@@ -417,36 +477,15 @@ def measure(ctx: Ctx, w: Workload, steps: int, warmup: int, prof_steps: int, tem
     # (SURVEY D2's W, less the row splits of placed slots and the implicit status, never stored)
     W = (0 if implicit & 1 else 4 * n) + 4 * n * (n_keys - n_placed) + 8 * kt[3] + 4 * kt[2] + \
         (8 if implicit & 4 else 12) * kt[1]
-    ms_step = elapsed / steps * 1e3
-    out = {
-        "workload": w.desc,
-        "records": n,
-        "tpl_groups_missed": sum(int(i.tpl_groups_missed) for i in infos),
-        "framed_bytes": framed,
-        "batches": launches,
-        "batch_bytes_max": int((plan[:, 3] - plan[:, 2]).max()),
-        "offsets": {"mode": omode, "bytes_per_record": off_bytes},
-        # device memory of the decode contexts (value columns sized from the learning sample), and
-        # of the resident input, in multiples of the input
-        "device_memory": {"contexts_bytes": dev_bytes, "x_input": round(dev_bytes / max(nbytes, 1), 3),
-                          "reruns": reruns},
-        # optimistic decodes (k_tpl_lane alone, confirmed by tfrg_result_info)
-        "optimistic": os.environ.get("TFRG_OPTIMISTIC", "1") != "0",
+    out.update({
         # TFRG_IMPLICIT_* bits common to every batch: 1 status / verdict, 2 order words
         "implicit_cols": implicit,
-        "streams": len(handles),
-        "ms_per_step": round(ms_step, 4),
-        # (the step is the larger of the host's wall clock and the GPU events: a small batch's step
-        # can be the host's enqueue rate)
-        "step_parts_ms": {"host_wall": round(wall / steps * 1e3, 4), "gpu_events": round(ev_s / steps * 1e3, 4)},
         # a consumer's cost per step beyond the timed step (wall clock, k_cons steps each): the
         # confirmation of every batch (host sync included), then the device view on top of it
         "consumer": {"step_plus_confirm_ms": round(conf_ms, 4), "confirm_ms": round(conf_ms - ms_step, 4),
                      "step_plus_confirm_view_ms": round(view_ms, 4), "device_view_ms": round(view_ms - conf_ms, 4),
                      "GiB_s_confirmed": round(framed / (conf_ms / 1e3) / 2**30, 3),
                      "GiB_s_confirmed_view": round(framed / (view_ms / 1e3) / 2**30, 3), "steps": k_cons},
-        "GiB_s": round(framed / (ms_step / 1e3) / 2**30, 3),
-        "examples_per_s": round(n / (ms_step / 1e3), 1),
         "kernels_ms": {k: round(v, 4) for k, v in kern_ms.items()},
         "roofline": {
             "kernel": dominant,
@@ -467,9 +506,7 @@ def measure(ctx: Ctx, w: Workload, steps: int, warmup: int, prof_steps: int, tem
             "achieved_GBps": round((R + W) / (ms_step / 1e3) / 1e9, 1),
             "frac": round((R + W) / (ms_step / 1e3) / 1e9 / PEAK_HBM_GBS, 4),
         },
-        "_elapsed": elapsed,
-        "_d_bytes": d_bytes,
-    }
+    })
     # small workloads: the per-stage HIP events inflate microsecond kernels, so a committed rocprofv3
     # kernel trace of the same workload (tools/kernel_trace.py) gives their durations instead
     kt = REPO / "profiles" / f"kernels_{w.name}.json"
@@ -507,6 +544,85 @@ def _present_lists(dec, w: Workload) -> float:
     lo, hi = int(w.starts[0]) & ~15, int(w.ends[k - 1])
     r = dec.decode(w.buf[lo:hi], w.starts[:k] - lo, w.ends[:k] - lo)
     return float((r.order != 0).sum()) * w.n / k
+
+
+DUMP_RECORDS = 1 << 18  # records sampled by --dump-outputs, at most
+DUMP_BYTES = 48 << 20  # bytes the sample is sized for (64 MB is the limit of a dump)
+
+
+def dump_outputs(out_dir: str, sd, plan: np.ndarray, w: Workload, ctx: Ctx) -> None:
+    """What the last decode of every batch left, as a caller fetches it (tfrg_result_fetch, the
+    columns of hip.BatchResult), for a fixed sample of the shard's records: default_rng(0) draws the
+    record numbers, as many as DUMP_BYTES allow at the shard's mean values per record. float64
+    unless noted, so every integer is exact; m records sampled, S key slots:
+
+    records[m]          the sampled records' numbers in the shard, ascending
+    status[m]           decode status (0 = OK)
+    verdict[m]          float32: framing verdict bits (7 = length, length CRC and payload CRC match)
+    order[m, S]         float32: 1-based position of slot s in the record's dict order, 0 = absent
+    counts[m, S]        values of slot s in the record (from the slot's row splits)
+    int64_values[k, 2]  the int64_list values, as (v >> 32, v & 0xffffffff)
+    float_values[k]     float32: the float_list values
+    bytes_views[k, 2]   the bytes_list elements, as (offset in the shard image, length)
+
+    The value arrays hold the sampled records' values batch by batch, inside a batch slot by slot,
+    inside a slot in record order. An array without elements (a value kind the schema lacks) is not
+    written. With several ranks each writes its own <name>.rank<r>.npy."""
+    infos = sd.infos(plan)
+    n = w.n
+    ns = int(infos[0].n_slots)
+    kt = [sum(int(i.kind_totals[k]) for i in infos) for k in range(4)]
+    per_record = 28 + 12 * ns + (16 * kt[3] + 4 * kt[2] + 16 * kt[1]) / max(n, 1)
+    m = max(1, min(n, DUMP_RECORDS, int(DUMP_BYTES / per_record)))
+    sel = np.arange(n) if m >= n else np.unique(np.random.default_rng(0).integers(0, n, size=m))
+    m = int(sel.size)
+    status = np.empty(m, np.float64)
+    verdict = np.empty(m, np.float32)
+    order = np.empty((m, ns), np.float32)
+    counts = np.empty((m, ns), np.float64)
+    vals: dict[int, list] = {1: [], 2: [], 3: []}
+    for k, (r0, r1, lo, _) in enumerate(plan.tolist()):
+        d = sd.decs[k]
+        r = d._fetch(w.buf[lo:], w.starts[r0:r1] - np.uint64(lo), w.ends[r0:r1] - np.uint64(lo), d.info(), False)
+        assert r.order.shape[0] == ns
+        a, b = np.searchsorted(sel, [r0, r1])
+        sub = sel[a:b] - r0
+        status[a:b] = r.status[sub]
+        verdict[a:b] = r.verdict[sub]
+        order[a:b] = r.order[:, sub].T
+        for s in range(ns):
+            v0 = r.row_splits[s, sub].astype(np.int64)
+            cnt = r.row_splits[s, sub + 1].astype(np.int64) - v0
+            counts[a:b, s] = cnt
+            # positions in the value column of the slot's kind: each sampled record's run of values
+            first = np.cumsum(cnt) - cnt
+            idx = np.repeat(int(r.slot_base[s]) + v0 - first, cnt) + np.arange(int(cnt.sum()))
+            kind = int(r.slot_kind[s])
+            if kind == 3:
+                v = r.i64[idx]
+                vals[3].append(np.stack([v >> 32, v & 0xFFFFFFFF], axis=1).astype(np.float64))
+            elif kind == 2:
+                vals[2].append(r.f32[idx].view(np.float32))
+            else:
+                vals[1].append(np.stack([r.bytes_off[idx].astype(np.float64) + lo,
+                                         r.bytes_len[idx].astype(np.float64)], axis=1))
+        del r
+    arrays = {
+        "records": sel.astype(np.float64), "status": status, "verdict": verdict, "order": order, "counts": counts,
+        "int64_values": np.concatenate(vals[3] + [np.zeros((0, 2), np.float64)]),
+        "float_values": np.concatenate(vals[2] + [np.zeros(0, np.float32)]),
+        "bytes_views": np.concatenate(vals[1] + [np.zeros((0, 2), np.float64)]),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 60 << 20, "the dump's sample outgrew its limit"
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    rank = int(os.environ.get("RANK", "0"))
+    for name, arr in arrays.items():
+        path = d / (f"{name}.rank{rank}.npy" if ctx.dist else f"{name}.npy")
+        if arr.size:
+            np.save(path, arr)
+        else:  # (a kind the schema has no values of: no file, and none left from an earlier run)
+            path.unlink(missing_ok=True)
 
 
 def _traffic(w: Workload, kernel: str, launches: int, omode: str = "u64"):
@@ -592,12 +708,14 @@ def run(args) -> None:
         w = c4_workload("c1v", 0, 8, args.files, "c4_c1v_rank0of8")
     else:
         w = single_workload(only)
-    head = measure(ctx, w, args.steps, args.warmup, args.profile_steps)
+    full = args.full
+    head = measure(ctx, w, args.steps, args.warmup, args.profile_steps, full=full, dump=args.dump_outputs)
     meta = {k: getattr(w, k) for k in ("files_total", "files_mine", "lpt_max_over_mean") if hasattr(w, k)}
-    rd = stream_read_gbs(ctx, head["_d_bytes"])
-    head["roofline"]["achievable_read_GBps"] = rd["GBps"]
-    head["roofline"]["achievable_read"] = rd
-    head["roofline"]["guide_copy_GBps"] = GUIDE_COPY_GBS
+    if full:
+        rd = stream_read_gbs(ctx, head["_d_bytes"])
+        head["roofline"]["achievable_read_GBps"] = rd["GBps"]
+        head["roofline"]["achievable_read"] = rd
+        head["roofline"]["guide_copy_GBps"] = GUIDE_COPY_GBS
     elapsed = head["_elapsed"]
     tot_bytes, tot_n = w.framed_bytes, w.n
     if dist:
@@ -610,12 +728,12 @@ def run(args) -> None:
     del head["_d_bytes"]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(w, args.cpu_seconds)
 
     configs = {}
     templates_off = None
-    if world == 1 and only is None and not args.no_extra:
+    if full and world == 1 and only is None and not args.no_extra:
         del w
         # c4of8: one rank's share of the same directory at N = 8 (32 of 256 files) decoded alone, the
         # per-GPU work of the 8-GPU strong-scaling point (a weak-scaling reference figure)
@@ -684,15 +802,18 @@ def run(args) -> None:
             "dtype": "u8",
             "data": "synthetic",
             "config": cfg,
-            "kernels_ms": head["kernels_ms"],
-            "roofline": head["roofline"],
-            "pipeline": head["pipeline"],
-            "cpu_baseline": cpu,
-            # a device-resident consumer's extra cost per step (measure(): consumer), not in `value`
-            "confirm_ms": head["consumer"]["confirm_ms"],
-            "device_view_ms": head["consumer"]["device_view_ms"],
-            "consumer": head["consumer"],
         }
+        if full:
+            line.update({
+                "kernels_ms": head["kernels_ms"],
+                "roofline": head["roofline"],
+                "pipeline": head["pipeline"],
+                "cpu_baseline": cpu,
+                # a device-resident consumer's extra cost per step (measure(): consumer), not in `value`
+                "confirm_ms": head["consumer"]["confirm_ms"],
+                "device_view_ms": head["consumer"]["device_view_ms"],
+                "consumer": head["consumer"],
+            })
         if configs:
             line["configs"] = configs
             if "c4of8" in configs:

@@ -4,7 +4,7 @@
 set -u
 O=gpurun_out/crclo; mkdir -p $O
 for c in c2 c4c2; do for L in libtfrg.so libtfrg_crc_loadonly.so libtfrg.so libtfrg_crc_loadonly.so; do
-TFRG_LIB=$PWD/tfrecords-reader_amd/tfr_reader/$L timeout -k 10 200 python bench.py --only $c --no-cpu --steps 100 > $O/$c.$L.json 2> $O/$c.$L.err || { tail $O/$c.$L.err; exit 1; }
+TFRG_LIB=$PWD/tfrecords-reader_amd/tfr_reader/$L timeout -k 10 200 python bench.py --full --only $c --no-cpu --steps 100 > $O/$c.$L.json 2> $O/$c.$L.err || { tail $O/$c.$L.err; exit 1; }
 python3 - $O/$c.$L.json $c $L <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

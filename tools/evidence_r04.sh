@@ -17,9 +17,9 @@ if [ "$1" = 1 ]; then
   done
   timeout -k 10 300 python tools/pmc_kernel.py $O/pk c4of8 k_tpl_lane > $O/pk.log 2>&1 || { tail $O/pk.log; exit 1; }
 elif [ "$1" = 2 ]; then
-  timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+  timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
   tail -c 400 $O/bench.json
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp -o run -- python bench.py --only c4 --no-cpu --steps 5 > $O/rp.log 2>&1 || { tail $O/rp.log; exit 1; }
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp -o run -- python bench.py --full --only c4 --no-cpu --steps 5 > $O/rp.log 2>&1 || { tail $O/rp.log; exit 1; }
   find $O/rp -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/rocprof_kernel_stats_r04.csv
 else
   for c in c1 c2 c3; do

@@ -1,5 +1,5 @@
 #!/usr/bin/env bash
-# GPU-box iteration: optional GPU tests, then bench.py --only <cfg> per named config (no CPU
+# One iteration on the GPU: optional GPU tests, then bench.py --full --only <cfg> per named config (no CPU
 # baseline), printing the step time, per-kernel times and the roofline fraction; PMC=1 adds the SQ
 # counters of k_tpl_lane on c4of8.
 #   bash tools/gpu_iter.sh OUTDIR [--tests "tests/a.py tests/b.py" | --all-tests] c4of8 c3 ...
@@ -14,7 +14,7 @@ if [ -n "$T" ]; then
   tail -2 $O/tests.log
 fi
 for c in "$@"; do
-  timeout -k 10 300 python bench.py --only "$c" --no-cpu --steps ${STEPS:-20} > $O/b_$c.json 2> $O/b_$c.err || { tail -30 $O/b_$c.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --only "$c" --no-cpu --steps ${STEPS:-20} > $O/b_$c.json 2> $O/b_$c.err || { tail -30 $O/b_$c.err; exit 1; }
   python3 - "$O/b_$c.json" "$c" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 between the launches: the per-stage events bench.py records inflate sub-10-us kernels ~2x).
 
 usage: kernel_trace.py <outdir> <only> [steps]
-Runs ``rocprofv3 --kernel-trace`` over ``bench.py --only <only> --no-cpu --steps S --profile-steps 1``
+Runs ``rocprofv3 --kernel-trace`` over ``bench.py --full --only <only> --no-cpu --steps S --profile-steps 1``
 and writes profiles-style JSON: the mean duration of each decode kernel over its last S x batches
 launches (the timed steps; earlier ones are the learning sample and the warmup), and their sum per
 step. bench.py reads ``profiles/kernels_<workload>.json`` for a workload of the same record count
@@ -26,7 +26,7 @@ def main() -> None:
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 50
     out.mkdir(parents=True, exist_ok=True)
     cmd = ["timeout", "-s", "KILL", "300", "rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", str(out),
-           "-o", "run", "--", sys.executable, str(REPO / "bench.py"), "--only", only, "--no-cpu", "--steps",
+           "-o", "run", "--", sys.executable, str(REPO / "bench.py"), "--full", "--only", only, "--no-cpu", "--steps",
            str(steps), "--profile-steps", "1", "--warmup", "3"]
     with open(out / "run.log", "w") as log, open(out / "run.err", "w") as err:
         subprocess.run(cmd, check=True, stdout=log, stderr=err, env=dict(os.environ, TMPDIR="/tmp"))

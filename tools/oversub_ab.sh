@@ -6,7 +6,7 @@
 set -u
 O=gpurun_out/${1:-ovs}; mkdir -p $O; export TMPDIR=/tmp
 for c in c2 c4c2 c3; do for rep in 1 2; do for m in 1 2 3; do
-TFRG_TAIL_OVERSUB=$m timeout -k 10 200 python bench.py --only $c --no-cpu --steps 100 > $O/$c.$m.json 2> $O/$c.$m.err || { tail $O/$c.$m.err; exit 1; }
+TFRG_TAIL_OVERSUB=$m timeout -k 10 200 python bench.py --full --only $c --no-cpu --steps 100 > $O/$c.$m.json 2> $O/$c.$m.err || { tail $O/$c.$m.err; exit 1; }
 python3 - $O/$c.$m.json $c $m <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

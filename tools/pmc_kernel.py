@@ -3,7 +3,7 @@
 
 usage: pmc_kernel.py <outdir> <only> <kernel-substring>
 Runs two rocprofv3 --pmc passes (each within the SQ block's 8 slots, MI355X_MICROARCH.md §counters)
-over `bench.py --only <only> --no-cpu --steps 3 --warmup 1 --profile-steps 1` and prints the mean
+over `bench.py --full --only <only> --no-cpu --steps 3 --warmup 1 --profile-steps 1` and prints the mean
 per full-batch launch of the kernel (tools/_dispatch.py), plus derived per-wave figures.
 """
 import json
@@ -30,7 +30,7 @@ def main() -> None:
     for i, cs in enumerate(SETS):
         d = out / f"p{i}"
         cmd = ["timeout", "-s", "KILL", "240", "rocprofv3", "--pmc", *cs.split(), "--kernel-trace", "--output-format",
-               "csv", "-d", str(d), "-o", "run", "--", sys.executable, str(REPO / "bench.py"), "--only", only,
+               "csv", "-d", str(d), "-o", "run", "--", sys.executable, str(REPO / "bench.py"), "--full", "--only", only,
                "--no-cpu", "--steps", "3", "--warmup", "1", "--profile-steps", "1"]
         with open(out / f"p{i}.log", "w") as log:
             subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, env=dict(os.environ, TMPDIR="/tmp"))

@@ -3,7 +3,7 @@
 
 usage (GPU box): pmc_traffic.py <outdir> <only> [kernel-substring]
 Runs `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (separate passes, MI355X_MICROARCH.md
-§HBM) over `bench.py --only <only> --no-cpu --steps 3 --warmup 1` (<only>: c4, c1file, c2, c3,
+§HBM) over `bench.py --full --only <only> --no-cpu --steps 3 --warmup 1` (<only>: c4, c1file, c2, c3,
 c4c2), keeps the dispatches of the kernel over the full batch (tools/_dispatch.py), and writes
 <outdir>/traffic_<workload>.json (bench.py's workload names: c4_c1, c1file, c2, c3, c4_c2) with the
 per-launch bytes: FETCH_SIZE x 1024 x 2 (gfx950 tallies 128-B fills at 64 B: the guide's correction
@@ -23,7 +23,7 @@ from _dispatch import full_batch_rows  # noqa: E402
 def run_pass(out: Path, counter: str, config: str) -> Path:
     d = out / counter
     cmd = ["timeout", "-s", "KILL", "240", "rocprofv3", "--pmc", counter, "--kernel-trace", "--output-format", "csv",
-           "-d", str(d), "-o", "run", "--", sys.executable, str(REPO / "bench.py"), "--only", config, "--no-cpu",
+           "-d", str(d), "-o", "run", "--", sys.executable, str(REPO / "bench.py"), "--full", "--only", config, "--no-cpu",
            "--steps", "3", "--warmup", "1", "--profile-steps", "1"]
     env = dict(os.environ, TMPDIR="/tmp")
     with open(out / f"{counter}.log", "w") as log, open(out / f"{counter}.err", "w") as err:

@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 150 --timeout
   || { grep -E "^(FAILED|ERROR)|Error" $O/tests.log | head -20; tail -3 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
 [ "${2:-}" = "--no-bench" ] && exit 0
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 - $O/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@
 set -u
 O=gpurun_out/${1:-wbb}; mkdir -p $O; export TMPDIR=/tmp
 for c in c2 c4c2; do for rep in 1 2; do for b in 16 8 4; do
-TFRG_WALK_BLOCKS=$b timeout -k 10 200 python bench.py --only $c --no-cpu --steps 100 > $O/$c.$b.json 2> $O/$c.$b.err || { tail $O/$c.$b.err; exit 1; }
+TFRG_WALK_BLOCKS=$b timeout -k 10 200 python bench.py --full --only $c --no-cpu --steps 100 > $O/$c.$b.json 2> $O/$c.$b.err || { tail $O/$c.$b.err; exit 1; }
 python3 - $O/$c.$b.json $c $b <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
