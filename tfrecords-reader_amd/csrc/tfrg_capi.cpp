@@ -91,6 +91,9 @@ struct tfrg_ctx {
   uint64_t record_bound = 0;  // tfrg_ctx_set_record_bound: no record above this (0 = unknown)
   uint64_t call_bound = 0;    // tfrg_decode_host: the bound of its own ranges (one call)
   int num_cus = 256;
+  uint32_t cu_lds = 65536;     // LDS bytes of a CU
+  int tpl_stage = 1;           // k_tpl_lane's staged windows: TFRG_TPL_STAGE=0 off (A/B measurements), 1 on
+                               // large batches, 2 on batches of any size (tests)
   // constants
   DBuf crc_tab, consts;
   // schema
@@ -128,6 +131,7 @@ struct tfrg_ctx {
   uint32_t tpl_w = 0;  // window words of the templates (16 / 32 / 64)
   size_t tpl_img_off = 0;  // the lane image follows the window-form templates in tpl
   uint32_t tpl_img_words = 0;
+  uint32_t tpl_tab_words = 0;  // the packed CRC position tables follow the image
   std::vector<uint32_t> tpl_h;  // host copy of the template words
   bool tpl_learned = false;
   bool tpl_full = false;  // the templates took every record of their learning sample
@@ -191,6 +195,7 @@ int tfrg_ctx_create(int device, tfrg_ctx** out) {
   c->device = device;
   if (const char* e = getenv("TFRG_TEMPLATES")) c->tpl_on = atoi(e) != 0;  // (A/B measurements)
   if (const char* e = getenv("TFRG_SPEC")) c->spec_on = atoi(e) != 0;
+  if (const char* e = getenv("TFRG_TPL_STAGE")) c->tpl_stage = atoi(e);
   if (const char* e = getenv("TFRG_OPTIMISTIC")) c->optimistic_on = atoi(e) != 0;
   if (const char* e = getenv("TFRG_WALK_BESIDE")) c->walk_beside = atoi(e) != 0;
   if (const char* e = getenv("TFRG_WALK_BLOCKS")) c->walk_blocks = (uint32_t)atoi(e);
@@ -202,7 +207,10 @@ int tfrg_ctx_create(int device, tfrg_ctx** out) {
     }
   }
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->num_cus = prop.multiProcessorCount;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
+    c->num_cus = prop.multiProcessorCount;
+    if (prop.maxSharedMemoryPerMultiProcessor) c->cu_lds = (uint32_t)prop.maxSharedMemoryPerMultiProcessor;
+  }
   if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
     delete c;
     set_error("hipStreamCreate failed");
@@ -215,10 +223,10 @@ int tfrg_ctx_create(int device, tfrg_ctx** out) {
     return TFRG_E_NOMEM;
   }
   // CRC tables: [4][256] slice-by-4 + [4][256] multiply-by-x^8192 (streaming CRC), then
-  // [8][256] slice-by-8 (lane kernel), then [16][256] slice-by-16 (streaming CRC), ..., then at
-  // kLeanTabOff [32][256] slice-by-32 (k_tpl_lane's position tables); consts: 64 lane shifts
+  // [8][256] slice-by-8 (lane kernel), then [16][256] slice-by-16 (streaming CRC), ...
+  // (k_tpl_lane's position tables are packed per learned shape: learn_shapes); consts: 64 lane shifts
   // x^(128 l), 16 un-shifts x^(-8z) and 32 round shifts x^(8192 * 2^k)
-  std::vector<uint32_t> tab(kLeanTabOff + 32 * 256), cst(128);
+  std::vector<uint32_t> tab(kCrcTabWords), cst(128);
   CrcTables T;
   crc_make_tables(&T);
   memcpy(tab.data(), T.t, 4096);
@@ -244,14 +252,6 @@ int tfrg_ctx_create(int device, tfrg_ctx** out) {
   for (int l = 0; l < 64; ++l) cst[l] = gf_xpow8(16ull * l);
   for (int z = 0; z < 16; ++z) cst[64 + z] = gf_xpow8_inv((uint64_t)z);
   for (int k = 0; k < 32; ++k) cst[96 + k] = gf_xpow8(1024ull << k);  // x^(8192 * 2^k): round shifts
-  // T_d[v] = U(0, v followed by d zero bytes), d < 32
-  for (int v = 0; v < 256; ++v) {
-    uint32_t x = T.t[0][v];
-    for (int d = 0; d < 32; ++d) {
-      tab[kLeanTabOff + d * 256 + v] = x;
-      x = (x >> 8) ^ T.t[0][x & 0xff];
-    }
-  }
   if (c->crc_tab.ensure(tab.size() * 4) != hipSuccess || c->consts.ensure(cst.size() * 4) != hipSuccess ||
       hipMemcpy(c->crc_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(c->consts.p, cst.data(), cst.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
@@ -447,6 +447,7 @@ static DevSchema schema_view(const tfrg_ctx* c) {
   s.tpl = c->tpl.as<uint32_t>();
   s.tpl_img = s.tpl + c->tpl_img_off;
   s.tpl_img_words = c->tpl_img_words;
+  s.tpl_tab_words = c->tpl_tab_words;
   s.n_tpl = c->tpl_on ? c->n_tpl : 0u;
   s.tpl_w = c->tpl_w;
   // speculative placement is a property of the learned shapes' schema (a slot that is one inline
@@ -581,6 +582,7 @@ bool tpl_derive(const TplSchema* c, const uint8_t* p, uint32_t L, Tpl& t) {
 // placement words. Returns the template count (0: none).
 struct Learned {
   std::vector<uint32_t> w, spec, img;  // window-form templates, spec words, lane image
+  std::vector<uint32_t> ptab;          // the packed CRC position tables the image's header names
   uint32_t W = 0;
   bool have_spec = false;
   bool full = false;  // every sampled record took a kept template
@@ -772,6 +774,27 @@ uint32_t learn_shapes(const TplSchema* c, uint32_t S, const uint8_t* h_bytes, ui
     }
   }
   memcpy(&img[kLiLut], lut.data(), lut.size());
+  // the packed position tables (tfrg_internal.h, image words 5 .. 7): of the 8 table words only
+  // those some kept template looks up, in word order; the chain runs on word 7's tables T_0 .. T_3
+  {
+    const uint32_t used = (img[3] & 0xffu) | (img[4] < W ? 0x80u : 0u);
+    uint32_t np = 0;
+    for (uint32_t j = 0; j < 8; ++j) {
+      if (!(used & (1u << j))) continue;
+      img[6 + j / 4] |= np << (8 * (j % 4));
+      out.ptab.resize((size_t)(np + 1) * kLiPtabWords);
+      uint32_t* t = &out.ptab[(size_t)np * kLiPtabWords];
+      for (uint32_t v = 0; v < 256; ++v) {  // T_d[v] = U(0, v followed by d zero bytes)
+        uint32_t x = CT.t[0][v];
+        for (uint32_t d = 0; d < 32; ++d) {
+          if (d >= 28 - 4 * j && d < 32 - 4 * j) t[(d - (28 - 4 * j)) * 256 + v] = x;
+          x = (x >> 8) ^ CT.t[0][x & 0xff];
+        }
+      }
+      ++np;
+    }
+    img[5] = np;
+  }
   // every slot present at the same key position (order word) in every kept shape: an optimistic
   // decode leaves the order column implicit (TFRG_IMPLICIT_ORDER)
   out.ord_const = S > 0 && S <= kLeanMaxSlots;
@@ -795,6 +818,7 @@ uint32_t learn_shapes(const TplSchema* c, uint32_t S, const uint8_t* h_bytes, ui
   out.w = std::move(w);
   out.spec = std::move(spec);
   out.img = std::move(img);
+  out.img.resize((out.img.size() + 3) & ~(size_t)3, 0u);  // (the tables after it: 16-byte aligned)
   out.W = W;
   out.have_spec = have_spec;
   return nt;
@@ -892,14 +916,18 @@ extern "C" int tfrg_learn_templates(tfrg_ctx* c, const uint8_t* h_bytes, uint64_
   const uint32_t W = L.W;
   HIP_TRY(hipSetDevice(c->device));
   if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
-  if (c->tpl.ensure((w.size() + L.img.size()) * 4) || (have_spec && c->spec.ensure((size_t)S * 4))) {
+  if (c->tpl.ensure((w.size() + L.img.size() + L.ptab.size()) * 4) || (have_spec && c->spec.ensure((size_t)S * 4))) {
     set_error("template allocation failed");
     return TFRG_E_NOMEM;
   }
   HIP_TRY(hipMemcpy(c->tpl.p, w.data(), w.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->tpl.as<uint32_t>() + w.size(), L.img.data(), L.img.size() * 4, hipMemcpyHostToDevice));
+  if (!L.ptab.empty())
+    HIP_TRY(hipMemcpy(c->tpl.as<uint32_t>() + w.size() + L.img.size(), L.ptab.data(), L.ptab.size() * 4,
+                      hipMemcpyHostToDevice));
   c->tpl_img_off = w.size();
   c->tpl_img_words = (uint32_t)L.img.size();
+  c->tpl_tab_words = (uint32_t)L.ptab.size();
   if (have_spec) HIP_TRY(hipMemcpy(c->spec.p, spec.data(), (size_t)S * 4, hipMemcpyHostToDevice));
   c->n_tpl = nt;
   c->tpl_w = W;
@@ -1151,6 +1179,8 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   o.rlist = c->rlist.as<uint32_t>();
   LaunchCfg cfg;
   cfg.num_cus = c->num_cus;
+  cfg.tpl_cu_lds = c->tpl_stage ? c->cu_lds : 0u;
+  cfg.tpl_stage_any = c->tpl_stage == 2;
   cfg.lean = c->tpl_on && c->n_tpl;
   cfg.tpl_full = cfg.lean && c->tpl_full;
   cfg.spec_h = c->spec_h.empty() ? nullptr : c->spec_h.data();

@@ -23,6 +23,7 @@ struct DevSchema {
   const uint32_t* tpl;         // [n_tpl][kLtWords] record-shape templates in window form (below)
   const uint32_t* tpl_img;     // their lane image (kLiHdr ...), tpl_img_words words
   uint32_t tpl_img_words;
+  uint32_t tpl_tab_words;      // the packed CRC position tables behind the image (kLiPtabWords each table word)
   uint32_t n_tpl;
   uint32_t tpl_w;              // their window words W (16, 32 or 64)
   // [n_slots] speculative placement of single values (null = off): 0, or (rank + 1) << 2 | kind for
@@ -61,14 +62,15 @@ constexpr uint32_t kLeanMaxSlots = 16;  // k_tpl_lane runs for schemas of at mos
 constexpr uint32_t kLtL = 0, kLtNe = 1, kLtCrcw = 2, kLtChain = 3, kLtK = 4, kLtAbsent = 5, kLtEnt = 8,
                    kLtWin = kLtEnt + 4 * kTplMaxEntries, kLtSlot = kLtWin + 3 * kLtMaxW,
                    kLtWords = kLtSlot + 3 * kLeanMaxSlots;
-constexpr uint32_t kLeanTabOff = 51200;  // crc_tab words: T_d, d < 32, 256 entries each (slice-by-32)
+constexpr uint32_t kCrcTabWords = 51200;  // crc_tab words (tfrg_ctx_create)
 
 // Lane image of the templates (k_tpl_lane): each lane matches the template its record's payload
 // length selects, so the template words are read per lane from LDS, where the workgroup copies this
 // image. Built on the host from the window-form templates (tfrg_learn_templates) and stored after
 // them in the template buffer (DevSchema::tpl_img). u32 words:
 //   header [0, kLiHdr): [0] templates, [1] W, [2] words per template (kLiTw), [3] union over the
-//     templates of kLtCrcw, [4] the smallest kLtChain;
+//     templates of kLtCrcw, [4] the smallest kLtChain, [5] the table words packed behind the image
+//     (below), [6] / [7] a byte per table word j = 0 .. 3 / 4 .. 7: its place in the packed block;
 //   [kLiSlotQ + k] slot k (< kLeanMaxSlots): qlo | qhi << 8 | kLiQValue (some template holds an
 //     inline int64 / float there, in window words qlo .. qhi + 1) | kLiQSingle (no template has more
 //     than one value there);
@@ -78,13 +80,19 @@ constexpr uint32_t kLeanTabOff = 51200;  // crc_tab words: T_d, d < 32, 256 entr
 //     (0xff: none), [4, 4 + W) Bm, [4 + W, 4 + 2 W) Mm, [4 + 2 W, 4 + 3 W) Cm, then per slot k 4 words
 //     {mode | len << 8 | rank << 16 (0: absent), pos, count word (0: absent), 0}
 //     (tfrg_internal.h "Record-shape template" for the fields).
+// Packed position tables: the image (padded to whole 16 bytes) is followed by the CRC tables the
+// templates look up and no others. Table word j < 8 is the four tables T_{28 - 4 j} .. T_{31 - 4 j}
+// of window word W - 9 + j (256 entries each: kLiPtabWords u32); a word is packed when its
+// bit of header word [3] is set, and word 7 (T_0 .. T_3) also when any template runs the chain.
+// Every workgroup of k_tpl_lane copies the block into LDS: C1 packs 3 of the 8 words.
+constexpr uint32_t kLiPtabWords = 4 * 256;
 constexpr uint32_t kTplMaxLane = 32;  // templates kept for the lane kernel (the most frequent shapes; TFRG_TPL_MAX)
 constexpr uint32_t kLiHdr = 8, kLiSlotQ = kLiHdr, kLiLut = kLiSlotQ + kLeanMaxSlots,
                    kLiLutWords = (kTplMaxL + 1 + 3) / 4, kLiTpl = (kLiLut + kLiLutWords + 3) & ~3u;
 constexpr uint32_t kLiQValue = 1u << 16, kLiQSingle = 1u << 17;
 __host__ __device__ constexpr uint32_t kLiTw(uint32_t W) { return 4 + 3 * W + 4 * kLeanMaxSlots; }
-// LDS words the lane image may take: a workgroup's 64 KiB less k_tpl_lane's static 32 KiB of CRC
-// tables and 512 B for its other static words (tfrg_tpl.hip asserts it). With W = 64 this keeps 30
+// LDS words the lane image may take: a workgroup's 64 KiB less k_tpl_lane's CRC tables when every
+// table word is packed (32 KiB) and 512 B for its static words (tfrg_tpl.hip asserts it). With W = 64 this keeps 30
 // templates, not kTplMaxLane (learn_shapes drops the least frequent ones).
 constexpr uint32_t kLiMaxWords = (65536u - 32768u - 512u) / 4u;
 
@@ -115,6 +123,11 @@ struct LeanArgs {
                           // the decode (tpl_quiet_finish); nullptr: the passes after this kernel do
   uint32_t implicit;      // optimistic decode, TFRG_IMPLICIT_* columns not stored for template hits
                           // (constant: every record of a confirmed decode is one)
+  uint32_t tab_words;     // the packed CRC tables behind the image (DevSchema::tpl_tab_words), copied into LDS
+  uint32_t cu_lds;        // (host) LDS bytes of a CU: launch_tpl_lane takes the staged-window kernel on
+                          // large batches when three workgroups with their stages fit; 0: never
+                          // (TFRG_TPL_STAGE=0)
+  uint32_t stage_any;     // (host) staged windows on batches of any size (TFRG_TPL_STAGE=2: tests)
   LeanTgt tg[kLeanMaxSlots];
 };
 
@@ -321,6 +334,8 @@ struct LaunchCfg {
   bool ord_const;          // every learned shape has every slot at the same key position
   bool len_const;          // every bytes slot one element of one length in every learned shape
   bool ran_quiet_big;      // (out) optimistic without shapes: k_tail_count's last workgroup ends it
+  uint32_t tpl_cu_lds;     // LeanArgs::cu_lds
+  bool tpl_stage_any;      // LeanArgs::stage_any
   bool walk_beside;        // optimistic without shapes: records above lane_max walked beside the CRC
                            // (k_tail_count's first workgroups) instead of before it (k_lane_count)
   uint32_t walk_blocks;    // cap on those workgroups (0: automatic)
@@ -334,7 +349,7 @@ extern const char* const kStageNames[kNumStages];
 
 // ev: optional kNumStages + 1 events recorded on `stream` before each stage and after the last.
 hipError_t launch_tpl_lane(const DevBatch& b, const DevOut& o, const LeanArgs& a, const uint32_t* img, uint32_t w,
-                           const uint32_t* d_tab, int num_cus, hipStream_t st);
+                           int num_cus, hipStream_t st);
 hipError_t launch_fill_placed_rows(uint32_t* rs, const uint32_t* info, uint32_t n_slots, uint32_t n, hipStream_t st);
 hipError_t launch_stream_read(const void* d, uint64_t nbytes, uint32_t* sink, hipStream_t st, int variant);
 hipError_t launch_decode(const DevBatch& b, const DevSchema& sc, const DevOut& o, LaunchCfg& cfg,

@@ -3682,6 +3682,9 @@ static hipError_t launch_all(const DevBatch& b, const DevSchema& sc, const DevOu
     LeanArgs a{};
     a.n_tpl = sc.n_tpl;
     a.img_words = sc.tpl_img_words;
+    a.tab_words = sc.tpl_tab_words;
+    a.cu_lds = cfg.tpl_cu_lds;
+    a.stage_any = cfg.tpl_stage_any ? 1u : 0u;
     a.lane_max = cfg.lane_max;
     a.tsum = cfg.ran_optimistic ? nullptr : o.tsum;  // (placed slots: no scan; a re-run clears tsum)
     a.finish = cfg.ran_optimistic ? sc.slot_kind : nullptr;
@@ -3712,7 +3715,7 @@ static hipError_t launch_all(const DevBatch& b, const DevSchema& sc, const DevOu
         t.v2 = o.b_len + base;
       }
     }
-    const hipError_t e = launch_tpl_lane(b, ox, a, sc.tpl_img, sc.tpl_w, d_tab, cfg.num_cus, st);
+    const hipError_t e = launch_tpl_lane(b, ox, a, sc.tpl_img, sc.tpl_w, cfg.num_cus, st);
     if (e != hipSuccess) return e;
   }
   if (cfg.ran_optimistic && !quiet_big) {  // (k_tpl_lane's last workgroup finished the decode)

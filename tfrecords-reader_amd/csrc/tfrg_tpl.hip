@@ -8,11 +8,15 @@
 // K ^ lin(variable bits) with lin linear (crc32c.h). So a lane takes its record as a fixed set of
 // words and does constant work, no walk:
 //   * the last 4 W bytes of the record [end - 4 W, end) -> W VGPRs, W / 4 unaligned 16-byte buffer
-//     loads straight from HBM (no LDS stage; out-of-range offsets read zeros);
+//     loads straight from HBM (out-of-range offsets read zeros); or, W = 16 with LDS to spare (ST):
+//     the 64 records of a group are usually one span of a few KiB, read as wave-contiguous 16-byte
+//     loads (8 cache lines per instruction, not ~30) into the wave's LDS stage, from where every
+//     lane takes its window;
 //   * match: (word ^ Bm) & Mm == 0 over the window (two VALU per word, template words in SGPRs);
 //   * CRC: one LDS lookup per variable payload byte in the position tables T_d (d = the byte's
 //     distance from the payload end, slice-by-32 tables), XOR-combined; variable bits further than
-//     32 bytes from the end first run a slice-by-4 chain whose state joins at distance 28..31;
+//     32 bytes from the end first run a slice-by-4 chain whose state joins at distance 28..31. LDS
+//     holds only the tables the templates look up, packed at learn time (kLiPtabWords);
 //   * the dict into the columns, ONE store per column and 64-record group whatever template each
 //     lane took: per slot, every template with hits in the group contributes its lanes' order,
 //     count / loc or speculatively placed value (DevSchema::spec; the row split r implicit), taken
@@ -31,9 +35,12 @@ namespace tfrg {
 
 namespace {
 
-constexpr int kTplBlock = 512;        // 8 waves: the 32 KiB of tables are shared by 8 waves
-constexpr uint32_t kTplTabs = 32;     // T_0 .. T_31
-static_assert(4u * kTplTabs * 256u + 4u * kLiMaxWords + 512u <= 65536u, "lane image + CRC tables exceed LDS");
+constexpr int kTplBlock = 512;        // 8 waves: the tables (up to 32 KiB) are shared by 8 waves
+constexpr uint32_t kTplTabWords = 8;  // table words: T_0 .. T_31, four tables each
+static_assert(4u * kTplTabWords * kLiPtabWords + 4u * kLiMaxWords + 512u <= 65536u, "lane image + CRC tables exceed LDS");
+// staged windows (W = 16): a wave's stage holds the span [first end - 64 rounded down to 16, last end)
+// of a group, 4 KiB and slack (64 records of 59 bytes: 3,855 bytes at most)
+constexpr uint32_t kStageWords = 1024 + 32, kStageRounds = (kStageWords * 4u + 1023u) / 1024u;
 constexpr uint32_t kHitVerdict = TFRG_V_LEN_MATCH | TFRG_V_LEN_CRC | TFRG_V_DATA_CRC;
 
 typedef __attribute__((address_space(4))) const uint32_t cu32;  // wave-uniform reads -> s_load
@@ -64,17 +71,17 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
   return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
 
-// table T_d at byte address bx of the static table array (d a compile-time constant: the table base
-// folds into the ds_read offset)
-template <int D>
-__device__ __forceinline__ uint32_t tl(const uint32_t* tab, uint32_t bx) {
-  return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(tab) + D * 1024 + bx);
+// table Q of a packed table word at byte address bx (tw: the word's four tables in LDS, wave-uniform;
+// one add per lookup, the table's place in the word folds into the ds_read offset)
+template <int Q>
+__device__ __forceinline__ uint32_t tl(const uint8_t* tw, uint32_t bx) {
+  return *reinterpret_cast<const uint32_t*>(tw + Q * 1024 + bx);
 }
 
-// linear CRC contribution of a word whose 4 bytes sit at distances D+3, D+2, D+1, D from the payload end
-template <int D>
-__device__ __forceinline__ uint32_t lin_word(const uint32_t* tab, uint32_t x) {
-  return xor3(tl<D + 3>(tab, bx4<0>(x)), tl<D + 2>(tab, bx4<1>(x)), tl<D + 1>(tab, bx4<2>(x))) ^ tl<D>(tab, bx4<3>(x));
+// linear CRC contribution of a word whose 4 bytes sit at distances D+3, D+2, D+1, D from the payload
+// end; tw: the tables T_D .. T_{D+3}
+__device__ __forceinline__ uint32_t lin_word(const uint8_t* tw, uint32_t x) {
+  return xor3(tl<3>(tw, bx4<0>(x)), tl<2>(tw, bx4<1>(x)), tl<1>(tw, bx4<2>(x))) ^ tl<0>(tw, bx4<3>(x));
 }
 
 // 7-bit groups of the bytes of w selected by byte mask m, compacted (a varint of <= 4 bytes)
@@ -131,18 +138,25 @@ __device__ void tpl_quiet_finish(const DevOut& o, const uint8_t* slot_kind, uint
   }
 }
 
-template <int W, int OM>
+template <int W, int OM, bool ST>
 __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_tpl_lane(
     DevBatch B, DevOut o, LeanArgs A, const uint32_t* __restrict__ img, const uint32_t* __restrict__ tabs) {
   static_assert(W == 16 || W == 32 || W == 64, "window words");
+  static_assert(!ST || W == 16, "staged windows: W = 16");
   typedef uint32_t wvec __attribute__((ext_vector_type(W)));
-  __shared__ __attribute__((aligned(16))) uint32_t tab[kTplTabs * 256];
-  extern __shared__ __attribute__((aligned(16))) uint32_t limg[];  // the templates' lane image
+  // the packed CRC tables (A.tab_words), then the templates' lane image (whole 16 bytes both), then
+  // (ST) a stage of kStageWords per wave
+  extern __shared__ __attribute__((aligned(16))) uint32_t tab[];
+  uint32_t* const limg = tab + A.tab_words;
   constexpr uint32_t kWaves = kTplBlock / 64;
   constexpr uint32_t kTw = kLiTw(W);
   const uint32_t lane = threadIdx.x & 63u, wib = rfl(threadIdx.x >> 6);
   cu32* gimg = (cu32*)img;  // (the image's wave-uniform words: scalar loads)
   const uint32_t crcw_u = gimg[3], chain_u = gimg[4];
+  // table word j's four tables in LDS (header words 6, 7: its place in the packed block)
+  auto tabw = [&](uint32_t j) -> const uint8_t* {
+    return reinterpret_cast<const uint8_t*>(tab) + 4u * kLiPtabWords * ((gimg[6u + (j >> 2)] >> (8u * (j & 3u))) & 0xffu);
+  };
   const uint8_t* lut = reinterpret_cast<const uint8_t*>(limg + kLiLut);
   // batches are < 0xffffff00 bytes (launch_tpl_lane): an offset of 0xffffff00 reads zeros
   const __amdgpu_buffer_rsrc_t rsrc =
@@ -197,6 +211,59 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
       wn[4 * q + 2] = v.z;
       wn[4 * q + 3] = v.w;
     }
+  };
+  // ST: the group's windows through the wave's stage when (wave-uniform) its valid lanes' ends do
+  // not decrease and lie in the batch, and the span from the first window (16-byte aligned) to the
+  // last end fits the stage in whole 16-byte pieces inside the batch (so not a batch's last group,
+  // unless it ends on a piece); any order and gaps the caller's offsets have pass this one test.
+  // Lane l takes pieces l, l + 64, ...; then every lane builds its window from aligned stage dwords.
+  // A lane whose window is not whole in the batch gets zeros, as from window(). Any other group:
+  // window(). The stage is the wave's own and LDS runs a wave's accesses in order: no wait between
+  // the writes, the reads and the next group's writes.
+  auto window_st = [&](wvec& wn, const LaneOff& f, uint32_t g) {
+    if constexpr (ST) {
+      uint32_t* const stg = limg + A.img_words + wib * kStageWords;
+      const uint32_t e = f.e;
+      const uint32_t g0 = g << 6;
+      const uint32_t nv = g < gend ? (B.n - g0 < 64u ? B.n - g0 : 64u) : 0u;  // valid lanes: [0, nv)
+      const uint32_t pe = (uint32_t)__builtin_amdgcn_update_dpp((int)e, (int)e, 0x138, 0xf, 0xf, false);  // lane - 1's
+      const bool bad = lane < nv && (e < pe || e > nb);
+      if (nv && !__ballot(bad)) {
+        const uint32_t e0 = rfl(e), hi = (uint32_t)__builtin_amdgcn_readlane((int)e, (int)(nv - 1u));
+        const uint32_t lo = (e0 >= 4u * W ? e0 - 4u * W : 0u) & ~15u;
+        const uint32_t nch = (hi - lo + 15u) >> 4;  // 16-byte pieces
+        // (the window reads run one dword past the lane's end)
+        if (hi > lo && nch * 16u + 4u <= kStageWords * 4u && lo + nch * 16u <= nb) {
+          u32x4 t[kStageRounds];
+#pragma unroll
+          for (uint32_t k = 0; k < kStageRounds; ++k)
+            if (lane + 64u * k < nch)
+              t[k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lo + 16u * (lane + 64u * k), 0, 0));
+#pragma unroll
+          for (uint32_t k = 0; k < kStageRounds; ++k)
+            if (lane + 64u * k < nch) reinterpret_cast<u32x4*>(stg)[lane + 64u * k] = t[k];
+          __builtin_amdgcn_wave_barrier();
+          const bool full = e >= 4u * W && lane < nv;
+          const uint32_t b0 = full ? e - 4u * W - lo : 0u;
+          const uint32_t* const sp = stg + (b0 >> 2);
+          const uint32_t sh = b0 & 3u;
+          uint32_t prev = sp[0];
+#pragma unroll
+          for (int i = 0; i < W; ++i) {
+            const uint32_t nx = sp[i + 1];
+            wn[i] = __builtin_amdgcn_alignbyte(nx, prev, sh);
+            prev = nx;
+          }
+          __builtin_amdgcn_wave_barrier();
+          if (__ballot(!full)) {  // (a batch's first records, the lanes past its last one)
+#pragma unroll
+            for (int i = 0; i < W; ++i) wn[i] = full ? wn[i] : 0u;
+          }
+          return;
+        }
+      }
+    }
+    window(wn, f);
   };
   // a record ending in the batch's first 4 W bytes (group 0 only): its window begins before the
   // batch; those bytes are outside the record (template mask 0), the rest is read byte by byte. (Its
@@ -269,11 +336,11 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
       if (chain_u < (uint32_t)(W - 9)) {
 #pragma unroll
         for (int i = 0; i < W - 9; ++i)
-          if ((uint32_t)i >= chain_u) c = lin_word<0>(tab, c ^ (w[i] & cm[i]));
+          if ((uint32_t)i >= chain_u) c = lin_word(tabw(7), c ^ (w[i] & cm[i]));
       }
       uint32_t lin = 0;
 #define TFRG_LIN(j)                                                                                       \
-  if (crcw_u & (1u << (j))) lin ^= lin_word<28 - 4 * (j)>(tab, (w[W - 9 + (j)] & cm[W - 9 + (j)]) ^ ((j) == 0 ? c : 0u));
+  if (crcw_u & (1u << (j))) lin ^= lin_word(tabw(j), (w[W - 9 + (j)] & cm[W - 9 + (j)]) ^ ((j) == 0 ? c : 0u));
       TFRG_LIN(0) TFRG_LIN(1) TFRG_LIN(2) TFRG_LIN(3) TFRG_LIN(4) TFRG_LIN(5) TFRG_LIN(6) TFRG_LIN(7)
 #undef TFRG_LIN
       const bool ok = act && diff == 0u && crc_mask(lin ^ meta.y) == w[W - 1];
@@ -354,21 +421,24 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
   };
   // one group per step (one window live: the per-lane template words need the registers); the next
   // group's offsets are requested before this group's stores. The wave's first offsets and window
-  // are requested before the workgroup copies its CRC tables and lane image into LDS, so its first
+  // (ST: into its stage, which no other wave touches) are requested before the workgroup copies its CRC tables and lane image into LDS, so its first
   // HBM round trips overlap that copy (~3 % of a launch of 2,000 workgroups).
   // (the first round of the table and image copies, the first two groups' offsets: all in flight
   // together; then the first window, which needs the offsets)
   LaneOff fa = offsets(gbeg), f0 = offsets(gbeg + 1u);
-  static_assert(kTplTabs * 256u % (4u * kTplBlock) == 0u, "table copy in whole 16-byte rounds");
-  constexpr uint32_t kTabRounds = kTplTabs * 256u / (4u * kTplBlock);
+  static_assert(kTplTabWords * kLiPtabWords % (4u * kTplBlock) == 0u, "table copy in whole 16-byte rounds");
+  constexpr uint32_t kTabRounds = kTplTabWords * kLiPtabWords / (4u * kTplBlock);
+  const uint32_t tab16 = A.tab_words >> 2;  // (the packed block alone: a table word is half a round)
   u32x4 tv[kTabRounds];
 #pragma unroll
-  for (uint32_t j = 0; j < kTabRounds; ++j) tv[j] = reinterpret_cast<const u32x4*>(tabs)[threadIdx.x + j * kTplBlock];
+  for (uint32_t j = 0; j < kTabRounds; ++j)
+    if (threadIdx.x + j * kTplBlock < tab16) tv[j] = reinterpret_cast<const u32x4*>(tabs)[threadIdx.x + j * kTplBlock];
   const uint32_t iw0 = threadIdx.x < A.img_words ? img[threadIdx.x] : 0u;
   wvec wa;
-  window(wa, fa);
+  window_st(wa, fa, gbeg);
 #pragma unroll
-  for (uint32_t j = 0; j < kTabRounds; ++j) reinterpret_cast<u32x4*>(tab)[threadIdx.x + j * kTplBlock] = tv[j];
+  for (uint32_t j = 0; j < kTabRounds; ++j)
+    if (threadIdx.x + j * kTplBlock < tab16) reinterpret_cast<u32x4*>(tab)[threadIdx.x + j * kTplBlock] = tv[j];
   if (threadIdx.x < A.img_words) limg[threadIdx.x] = iw0;
   for (uint32_t i = threadIdx.x + kTplBlock; i < A.img_words; i += kTplBlock) limg[i] = img[i];
   __syncthreads();
@@ -377,7 +447,7 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
     proc(wa, g, fa);
     if (((g + 1u) & 3u) == 0u || g + 1u >= gend) flush(g);
     if (g + 1u < gend) {
-      window(wa, f0);
+      window_st(wa, f0, g + 1u);
       fa = f0;
       f0 = offsets(g + 2u);
     }
@@ -403,7 +473,7 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
 }  // namespace
 
 hipError_t launch_tpl_lane(const DevBatch& b, const DevOut& o, const LeanArgs& a, const uint32_t* img, uint32_t w,
-                           const uint32_t* d_tab, int num_cus, hipStream_t st) {
+                           int num_cus, hipStream_t st) {
   const uint32_t groups = (b.n + 63u) / 64u;
   const uint32_t tiles = (groups + 3u) / 4u;  // (one wave per 256-record tile)
   const uint32_t need = (tiles + kTplBlock / 64 - 1) / (kTplBlock / 64);
@@ -411,7 +481,7 @@ hipError_t launch_tpl_lane(const DevBatch& b, const DevOut& o, const LeanArgs& a
   // fewer workgroups than CUs, a quarter -- one group -- below half as many: a latency-bound launch
   // of a few MiB, c1file 15.5 -> 12.2 us), no resident-grid stride: workgroups retire all through the launch,
   // so the end of the batch does not wait on the waves that drew an extra round of tiles (c4of8:
-  // 0.414 ms against 0.430 ms for one round of resident workgroups; the 32 KiB table copy per
+  // 0.414 ms against 0.430 ms for one round of resident workgroups; the table copy per
   // workgroup is L2 traffic)
   LeanArgs a2 = a;
   a2.gpw = need < (uint32_t)num_cus / 2u ? 1u : need < (uint32_t)num_cus ? 2u : need >= 8u * (uint32_t)num_cus ? 8u : 4u;
@@ -439,19 +509,36 @@ hipError_t launch_tpl_lane(const DevBatch& b, const DevOut& o, const LeanArgs& a
                               ? bsplit + (groups - gsplit + kW * 2u - 1u) / (kW * 2u)
                               : ((groups + a2.gpw - 1u) / a2.gpw + kW - 1u) / kW;
   const dim3 grid(blocks ? blocks : 1u);
-  const uint32_t* tabs = d_tab + kLeanTabOff;
-  const size_t lds = (size_t)a.img_words * 4;  // (the lane image; the CRC tables are static)
-#define TFRG_TPL_LAUNCH(WW, OO) hipLaunchKernelGGL((k_tpl_lane<WW, OO>), grid, dim3(kTplBlock), lds, st, b, o, a2, img, tabs)
-#define TFRG_TPL_OM(WW)                                                        \
+  const uint32_t* tabs = img + a.img_words;  // (the packed CRC tables follow the image)
+  size_t lds = ((size_t)a.tab_words + a.img_words) * 4;
+  // staged windows (W = 16) where three workgroups with a stage each still fit a CU's LDS, the
+  // residency the kernel's registers allow (6 waves per SIMD); with fewer the stage loses more than
+  // its loads gain. And on large batches only (8 groups per wave, several rounds of workgroups per
+  // CU), which the memory system bounds: a small batch is one round trip after another, and the
+  // stage adds its LDS round trip to each (c1file, 65,536 records: 9.2 us staged, 8.9 us not).
+  // a.cu_lds 0: TFRG_TPL_STAGE=0; a.stage_any: TFRG_TPL_STAGE=2, batches of any size (tests).
+  const size_t lds_st = lds + (size_t)kW * kStageWords * 4;
+  const bool staged = w == 16 && (a2.gpw >= 8u || a.stage_any) && lds_st + 64u <= 65536u &&
+                      3u * ((lds_st + 64u + 2047u) & ~(size_t)2047u) <= a.cu_lds;
+  if (staged) lds = lds_st;
+#define TFRG_TPL_LAUNCH(WW, OO, SS) \
+  hipLaunchKernelGGL((k_tpl_lane<WW, OO, SS>), grid, dim3(kTplBlock), lds, st, b, o, a2, img, tabs)
+#define TFRG_TPL_OM(WW, SS)                                                    \
   switch (b.omode) {                                                           \
-    case kOffU64: TFRG_TPL_LAUNCH(WW, kOffU64); break;                         \
-    case kOffU32: TFRG_TPL_LAUNCH(WW, kOffU32); break;                         \
-    default: TFRG_TPL_LAUNCH(WW, kOffEnds); break;                             \
+    case kOffU64: TFRG_TPL_LAUNCH(WW, kOffU64, SS); break;                     \
+    case kOffU32: TFRG_TPL_LAUNCH(WW, kOffU32, SS); break;                     \
+    default: TFRG_TPL_LAUNCH(WW, kOffEnds, SS); break;                         \
   }
   switch (w) {
-    case 16: TFRG_TPL_OM(16) break;
-    case 32: TFRG_TPL_OM(32) break;
-    case 64: TFRG_TPL_OM(64) break;
+    case 16:
+      if (staged) {
+        TFRG_TPL_OM(16, true)
+      } else {
+        TFRG_TPL_OM(16, false)
+      }
+      break;
+    case 32: TFRG_TPL_OM(32, false) break;
+    case 64: TFRG_TPL_OM(64, false) break;
     default: return hipErrorInvalidValue;
   }
 #undef TFRG_TPL_OM

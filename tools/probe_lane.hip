@@ -38,7 +38,7 @@ struct Cols {
 };
 
 enum : int { kU64 = 1, kStore = 2, kPipe = 4, kCheck = 8, kNoSV = 16, kNoOrd = 32, kStaged = 64, kTabLds = 128,
-             kTab8 = 256, kGlds = 512, kTab16 = 1024, kNoLen = 2048 };
+             kTab8 = 256, kGlds = 512, kTab16 = 1024, kNoLen = 2048, kTab12 = 4096 };
 typedef __attribute__((address_space(1))) void gvoid;
 typedef __attribute__((address_space(3))) void lvoid;
 
@@ -75,7 +75,9 @@ __global__ __launch_bounds__(512, 6) void k_probe(const uint8_t* bytes, uint32_t
   };
   __shared__ __attribute__((aligned(16))) uint32_t stage[8][1024 + 32];  // 4 KiB + slack per wave
   // kTabLds: 32 KiB more LDS per workgroup (k_tpl_lane's CRC position tables): 2 workgroups per CU
-  constexpr uint32_t kPad = (MODE & kTabLds) ? ((MODE & kTab8) ? 2048u : (MODE & kTab16) ? 4096u : 8192u) : 1u;
+  // (kTab16 / kTab12: the packed tables of a shape that touches 4 / 3 of the 8 table words)
+  constexpr uint32_t kPad =
+      (MODE & kTabLds) ? ((MODE & kTab8) ? 2048u : (MODE & kTab12) ? 3072u : (MODE & kTab16) ? 4096u : 8192u) : 1u;
   __shared__ uint32_t tabpad[kPad];
   if (MODE & kTabLds) {
     for (uint32_t i = threadIdx.x; i < kPad; i += 512u) tabpad[i] = i;
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(512, 6) void k_probe(const uint8_t* bytes, uint32_t
     uint32_t x = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) x ^= w[i] * (uint32_t)(2 * i + 1);
-    if (MODE & kTabLds) x ^= tabpad[x & (kPad - 1u)];
+    if (MODE & kTabLds) x ^= tabpad[(MODE & kTab12) ? ((x & 4095u) * 3u) >> 2 : x & (kPad - 1u)];
     acc += x;
     if (MODE & kStore) {
       if (r < n) {
@@ -288,7 +290,24 @@ int main(int argc, char** argv) {
            name, tpw, ms, (rd + wr) / ms / 1e9, (rd + wr) / ms / 1e9 / 8.0, nb / (ms / 1e3) / 1073741824.0);
     fflush(stdout);
   };
-  for (int rep = 0; rep < 2; ++rep)
+  // argv[2]: 6 = the round-6 rows (LDS-DMA), default = staged windows beside packed tables of
+  // 12 / 16 KiB against the per-lane windows, today's store set (value columns only)
+  const int set = argc > 2 ? atoi(argv[2]) : 7;
+#define ROW(name, mode) rep_(name, mode, tpw, run<mode>(d_b, nb, d_s64, d_e64, d_e32, n, c, tpw, reps))
+  for (int rep = 0; rep < (set == 7 ? 3 : 0); ++rep)
+    for (uint32_t tpw : {2u}) {
+      constexpr int V = kStore | kNoSV | kNoOrd | kNoLen;
+      ROW("v12_lane_tab32", V | kTabLds);
+      ROW("v12_lane_tab16", V | kTabLds | kTab16);
+      ROW("v12_staged_tab16", V | kStaged | kTabLds | kTab16);
+      ROW("v12_lane_tab12", V | kTabLds | kTab12);
+      ROW("v12_staged_tab12", V | kStaged | kTabLds | kTab12);
+      ROW("v12_staged_tab32", V | kStaged | kTabLds);
+      ROW("v12_lane", V);
+      ROW("v12_staged", V | kStaged);
+    }
+#undef ROW
+  for (int rep = 0; rep < (set == 6 ? 2 : 0); ++rep)
     for (uint32_t tpw : {1u, 2u}) {
       constexpr int V = kStore | kNoSV | kNoOrd | kNoLen;
       rep_("v12_lane", V, tpw, run<V>(d_b, nb, d_s64, d_e64, d_e32, n, c, tpw, reps));
