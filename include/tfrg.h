@@ -31,7 +31,9 @@ extern "C" {
 #define TFRG_FLAG_PAYLOAD_ONLY 1u /* ranges are bare Example payloads (decode(raw) semantics)   */
 #define TFRG_FLAG_SPEC_VARINT 2u  /* protobuf-spec int64 varints instead of the reference's
                                      int-width shift (decoder.pyx:44)               */
-#define TFRG_FLAG_NO_CRC 4u       /* skip the CRC-32C verdicts                                   */
+#define TFRG_FLAG_NO_CRC 4u       /* skip the CRC-32C verdicts. Record-shape templates still apply:
+                                     a record matching one under its mask takes it whatever its
+                                     CRCs (verdict TFRG_V_LEN_MATCH)                              */
 #define TFRG_FLAG_STRICT_CRC 8u   /* a record whose length field or either masked CRC-32C does not
                                      match fails with TFRG_ERR_CRC (no values) instead of only
                                      clearing its verdict bits; overrides TFRG_FLAG_NO_CRC      */
@@ -134,7 +136,9 @@ int tfrg_ctx_set_wave_stage(tfrg_ctx* ctx, uint32_t nbytes);
  * not kept; with payloads over 112 bytes the lane image holds at most 30, the LDS beside the CRC
  * tables). A framed record equal to a template under its mask, with matching length field and CRCs,
  * gets the template's dict without a walk (its values are still read from the record; k_tpl_lane,
- * schemas of <= TFRG_TPL_MAX_SLOTS slots, CRC verdicts on); any other record takes the canonical walk.
+ * schemas of <= TFRG_TPL_MAX_SLOTS slots); any other record takes the canonical walk. A shape is kept
+ * per frame class (tfrg_template_frames): records whose two CRC fields are 0 match a template of
+ * their own, and with TFRG_FLAG_NO_CRC the CRCs play no part in the match.
  * Learned automatically from the first tfrg_decode_host batch after each tfrg_set_schema; device-only
  * callers pass a host sample here. Returns the number of templates (0..TFRG_TPL_MAX). With no shape
  * kept, the slots that are one inline value in every sampled record (host decode) are still learned
@@ -149,6 +153,11 @@ int tfrg_ctx_set_wave_stage(tfrg_ctx* ctx, uint32_t nbytes);
 int tfrg_learn_templates(tfrg_ctx* ctx, const uint8_t* h_bytes, uint64_t nbytes, const uint64_t* h_start,
                          const uint64_t* h_end, uint32_t n, uint32_t flags);
 int tfrg_template_count(tfrg_ctx* ctx);
+/* The frame classes of the kept templates, a bit mask: bit 0 -- spec-framed (length and data CRC
+ * fields hold the spec masked CRC-32C), bit 1 -- unchecked-framed (both CRC fields 0, as the
+ * reference's test writers leave them: such a record takes its template with verdict
+ * TFRG_V_LEN_MATCH). A sample with both kinds keeps a shape once per class. 0: no templates. */
+int tfrg_template_frames(tfrg_ctx* ctx);
 /* The learned templates in their window form (u32 words, layout in csrc/tfrg_internal.h): up to cap
  * words into out, the window size W (words) into *window_words; returns the template count. For
  * checking a template against records on the host. */

@@ -135,6 +135,7 @@ struct tfrg_ctx {
   std::vector<uint32_t> tpl_h;  // host copy of the template words
   bool tpl_learned = false;
   bool tpl_full = false;  // the templates took every record of their learning sample
+  uint32_t tpl_frames = 0;  // frame classes of the kept templates: bit 0 spec, bit 1 unchecked
   bool tpl_on = true;
   // speculative single-value placement (DevSchema::spec), derived from the templates
   std::vector<uint8_t> slot_kind_h;
@@ -164,6 +165,7 @@ struct tfrg_ctx {
   bool len_const = false;     // (Learned::len_const)
   std::vector<uint32_t> const_len;  // per slot: the bytes element length of every learned shape
   uint32_t last_implicit = 0; // TFRG_IMPLICIT_* columns the last decode did not store
+  bool last_aux_zero = false; // the last decode ran optimistically with stored statuses: aux is all 0
   uint32_t* info_pin = nullptr;  // pinned host copy of the info words + kind totals (confirmation)
   bool cols_complete = false; // tfrg_result_device filled them into the device columns
   bool mat_pending = false;   // an optimistic decode's byte materialization waits for its confirmation
@@ -481,10 +483,12 @@ struct Tpl {
   uint32_t L = 0;
   std::vector<uint8_t> bytes, mask;
   std::vector<uint32_t> ent;  // 4 words per entry
-  std::string key() const {  // identity: length, masked bytes, mask
+  uint32_t frame = 0;         // frame class (kLtFrame): 0 spec CRCs, 1 unchecked (both CRC fields 0)
+  std::string key() const {  // identity: length, masked bytes, mask, frame class
     std::string k((const char*)&L, 4);
     for (uint32_t i = 0; i < L; ++i) k.push_back((char)(bytes[i] & mask[i]));
     k.append((const char*)mask.data(), mask.size());
+    k.push_back((char)frame);
     return k;
   }
 };
@@ -504,6 +508,7 @@ bool tpl_derive(const TplSchema* c, const uint8_t* p, uint32_t L, Tpl& t) {
   t.bytes.assign(p, p + L);
   t.mask.assign(L, 0xffu);
   t.ent.clear();
+  t.frame = 0;
   uint32_t fn, fo, fl;
   if (!tpl_hdr2(p, L, 0, L, fn, fo, fl) || fn != 1u || fo + fl != L) return false;
   std::vector<uint32_t> seen;
@@ -586,6 +591,7 @@ struct Learned {
   uint32_t W = 0;
   bool have_spec = false;
   bool full = false;  // every sampled record took a kept template
+  uint32_t frames = 0;  // frame classes of the kept templates: bit 0 spec, bit 1 unchecked
   bool ord_const = false;  // every slot (< kLeanMaxSlots) at one key position in every kept template
   // every bytes slot one element (mode 3) of one length in every kept template: an optimistic decode
   // leaves the bytes_len column implicit (TFRG_IMPLICIT_BYTES_LEN); const_len[k] that length
@@ -594,7 +600,7 @@ struct Learned {
 };
 uint32_t learn_shapes(const TplSchema* c, uint32_t S, const uint8_t* h_bytes, uint64_t nbytes, const uint64_t* h_start,
                       const uint64_t* h_end, uint32_t n, uint32_t flags, Learned& out) {
-  std::map<std::string, std::pair<uint32_t, Tpl>> seen;  // shape -> (records, template)
+  std::map<std::string, std::pair<uint32_t, Tpl>> seen;  // (shape, frame class) -> (records, template)
   Tpl t;
   // up to 4,096 records spread over the whole batch (not its first ones: ids that grow with the
   // record index give the first records shapes the rest of a file does not have)
@@ -603,15 +609,22 @@ uint32_t learn_shapes(const TplSchema* c, uint32_t S, const uint8_t* h_bytes, ui
     const uint32_t i = (uint32_t)((uint64_t)j * n / lim);
     uint64_t a = h_start[i], e = h_end[i];
     if (e > nbytes || e < a) continue;
+    bool unchecked = false;
     if (!(flags & TFRG_FLAG_PAYLOAD_ONLY)) {  // framed: a length field matching the range
       if (e - a < 16) continue;
       uint64_t len = 0;
       memcpy(&len, h_bytes + a, 8);
       if (len != e - a - 16) continue;
+      // unchecked frame (the reference's writers): both CRC fields 0 where the spec length CRC is not
+      uint32_t lc = 0, dc = 0;
+      memcpy(&lc, h_bytes + a + 8, 4);
+      memcpy(&dc, h_bytes + e - 4, 4);
+      unchecked = lc == 0 && dc == 0 && tfrg_masked_crc32c(h_bytes + a, 8) != 0;
       a += 12;
       e -= 4;
     }
     if (!tpl_derive(c, h_bytes + a, (uint32_t)(e - a > 0xffffffffull ? 0 : e - a), t)) continue;
+    t.frame = unchecked ? 1u : 0u;
     auto& slot = seen[t.key()];
     if (!slot.first) slot.second = t;
     ++slot.first;
@@ -676,9 +689,10 @@ uint32_t learn_shapes(const TplSchema* c, uint32_t S, const uint8_t* h_bytes, ui
       Bm[off + i] = (uint8_t)(L64 >> (8 * i));
       Mm[off + i] = 0xffu;
     }
-    for (int i = 0; i < 4; ++i) {
-      Bm[off + 8 + i] = (uint8_t)(lcrc >> (8 * i));
+    for (int i = 0; i < 4; ++i) {  // (unchecked frame: both CRC fields are 0, the data CRC's word W - 1)
+      Bm[off + 8 + i] = x.frame ? 0u : (uint8_t)(lcrc >> (8 * i));
       Mm[off + 8 + i] = 0xffu;
+      if (x.frame) Mm[4 * W - 4 + i] = 0xffu;
     }
     std::vector<uint8_t> fixed(L);
     for (uint32_t p = 0; p < L; ++p) {
@@ -706,6 +720,8 @@ uint32_t learn_shapes(const TplSchema* c, uint32_t S, const uint8_t* h_bytes, ui
     d[kLtCrcw] = crcw;
     d[kLtChain] = chain;
     d[kLtK] = ~crc_update_bytes(CT, 0xffffffffu, fixed.data(), L);  // CRC-32C with every variable bit 0
+    d[kLtFrame] = x.frame;
+    out.frames |= 1u << x.frame;
     uint32_t present = 0;
     for (size_t e = 0; e < x.ent.size(); e += 4) {
       const uint32_t slot = x.ent[e] & 0xffffffu, mode = x.ent[e] >> 24;
@@ -744,6 +760,7 @@ uint32_t learn_shapes(const TplSchema* c, uint32_t S, const uint8_t* h_bytes, ui
     q[0] = L;
     q[1] = d[kLtK];
     q[2] = 0xffu;
+    q[3] = d[kLtFrame];
     for (uint32_t i = 0; i < 3 * W; ++i) q[4 + i] = d[kLtWin + (i / W) * W + i % W];
     for (uint32_t s2 = 0; s2 < kLeanMaxSlots; ++s2) {
       const uint32_t* z = d + kLtSlot + 3 * s2;
@@ -890,6 +907,7 @@ extern "C" int tfrg_learn_templates(tfrg_ctx* c, const uint8_t* h_bytes, uint64_
   if (!c || (n && (!h_bytes || !h_start || !h_end))) return TFRG_E_ARG;
   c->tpl_learned = true;
   c->n_tpl = 0;
+  c->tpl_frames = 0;
   c->have_spec = false;
   if (!c->n_keys) return 0;
   const TplSchema sch{c->key_id, c->key_slot_h, c->slot_kind_h};
@@ -935,6 +953,7 @@ extern "C" int tfrg_learn_templates(tfrg_ctx* c, const uint8_t* h_bytes, uint64_
   c->spec_h = spec;
   c->have_spec = have_spec;
   c->tpl_full = L.full;
+  c->tpl_frames = L.frames;
   c->ord_const = L.ord_const;
   c->len_const = L.len_const;
   c->const_len = L.const_len;
@@ -967,6 +986,8 @@ extern "C" int tfrg_learn_templates_host(uint32_t n_keys, const uint8_t* key_blo
 }
 
 extern "C" int tfrg_template_count(tfrg_ctx* c) { return c ? (int)c->n_tpl : TFRG_E_ARG; }
+
+extern "C" int tfrg_template_frames(tfrg_ctx* c) { return c ? (int)(c->n_tpl ? c->tpl_frames : 0u) : TFRG_E_ARG; }
 
 extern "C" int tfrg_template_words(tfrg_ctx* c, uint32_t* out, uint64_t cap, uint32_t* window_words) {
   if (!c) return TFRG_E_ARG;
@@ -1183,6 +1204,7 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   cfg.tpl_stage_any = c->tpl_stage == 2;
   cfg.lean = c->tpl_on && c->n_tpl;
   cfg.tpl_full = cfg.lean && c->tpl_full;
+  cfg.tpl_unchecked = cfg.lean && (c->tpl_frames & 2u) != 0;
   cfg.spec_h = c->spec_h.empty() ? nullptr : c->spec_h.data();
   const uint64_t lane_blocks = (n + 255) / 256;
   const uint64_t lane_cap = (uint64_t)c->num_cus * 8;
@@ -1266,6 +1288,8 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   if (n != 0 && cfg.ran_quiet_big) c->tsum_dirty = true;
   c->mat_pending = c->opt_pending && mat && S;
   c->last_implicit = n != 0 ? cfg.implicit : 0u;
+  // (k_tpl_lane stored status and verdict per record and no aux: every record of a confirmed decode is OK)
+  c->last_aux_zero = n != 0 && cfg.ran_optimistic && !cfg.ran_quiet_big && !(cfg.implicit & TFRG_IMPLICIT_STATUS);
   c->cols_complete = false;
   return 0;
 }
@@ -1421,9 +1445,10 @@ int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
                                     c->n_slots, c->n, c->last_stream));
   }
   c->rs_complete = true;
-  if (c->last_implicit && !c->cols_complete) {  // the constant columns of an optimistic decode
+  if ((c->last_implicit || c->last_aux_zero) && !c->cols_complete) {  // the constant columns of an optimistic decode
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = c->n;
+    if (c->last_aux_zero) HIP_TRY(hipMemsetAsync(c->aux.p, 0, n * 8, c->last_stream));
     if (c->last_implicit & TFRG_IMPLICIT_STATUS) {
       HIP_TRY(hipMemsetAsync(c->status.p, 0, n * 4, c->last_stream));
       HIP_TRY(hipMemsetAsync(c->aux.p, 0, n * 8, c->last_stream));
@@ -1472,7 +1497,11 @@ int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {
     if (h->verdict) memset(h->verdict, TFRG_V_LEN_MATCH | TFRG_V_LEN_CRC | TFRG_V_DATA_CRC, n);
   } else {
     HIP_TRY(cp(h->status, c->status.p, n * 4));
-    HIP_TRY(cp(h->aux, c->aux.p, n * 8));
+    if (c->last_aux_zero) {
+      if (h->aux) memset(h->aux, 0, n * 8);
+    } else {
+      HIP_TRY(cp(h->aux, c->aux.p, n * 8));
+    }
     HIP_TRY(cp(h->verdict, c->verdict.p, n));
   }
   if ((info.implicit_cols & TFRG_IMPLICIT_ORDER) && h->order) {

@@ -49,6 +49,7 @@ struct DevSchema {
 // Layout (u32): [kLtL] L, [kLtNe] entries, [kLtCrcw] bit j: word W - 9 + j has variable payload
 // bits, [kLtChain] first word < W - 9 with variable payload bits (W: none), [kLtK] CRC-32C of the
 // payload with every variable bit 0, [kLtAbsent] slots (< kLeanMaxSlots) absent from the shape,
+// [kLtFrame] the frame class (below),
 // [kLtEnt + 4 e] entries {slot | mode << 8 | spec << 12 | len << 16, rank, count word, pos}; mode 0:
 // list location (pos = payload offset, len), 1: inline int64 varint of len bytes at window byte pos,
 // 2: inline float at window byte pos, 3: inline bytes element of len bytes, pos = payload offset -
@@ -56,10 +57,17 @@ struct DevSchema {
 // [kLtSlot + 3 k] the same entries by SLOT k (< kLeanMaxSlots), so that k_tpl_lane stores slot k's
 // columns once for the lanes of every template: {mode | len << 8 | rank << 16 (0: absent), pos,
 // count word (0: absent)}.
+// Frame class (kLtFrame; a shape is kept once per class its sample shows, tfrg_template_frames):
+// 0 = spec, the length CRC a fixed template field and the data CRC computed, as above; 1 = unchecked,
+// the frames of writers that leave both CRC fields 0 (the reference's test writers, crc=False):
+// Bm 0 / Mm 0xff on the four length-CRC bytes and Bm 0 / Mm 0xffffffff on word W - 1, every other
+// word as the spec template of the shape. A hit of an unchecked template proves both stored fields
+// 0; its verdict is TFRG_V_LEN_MATCH, and k_tpl_lane takes the record only if its true masked
+// payload CRC is not 0 as well (else the canonical walk's TFRG_V_DATA_CRC would be lost).
 constexpr uint32_t kTplMaxL = 240, kTplMaxEntries = 16;  // (tfrg.h TFRG_TPL_MAX_PAYLOAD / _ENTRIES)
 constexpr uint32_t kLtMaxW = 64;
 constexpr uint32_t kLeanMaxSlots = 16;  // k_tpl_lane runs for schemas of at most this many slots
-constexpr uint32_t kLtL = 0, kLtNe = 1, kLtCrcw = 2, kLtChain = 3, kLtK = 4, kLtAbsent = 5, kLtEnt = 8,
+constexpr uint32_t kLtL = 0, kLtNe = 1, kLtCrcw = 2, kLtChain = 3, kLtK = 4, kLtAbsent = 5, kLtFrame = 6, kLtEnt = 8,
                    kLtWin = kLtEnt + 4 * kTplMaxEntries, kLtSlot = kLtWin + 3 * kLtMaxW,
                    kLtWords = kLtSlot + 3 * kLeanMaxSlots;
 constexpr uint32_t kCrcTabWords = 51200;  // crc_tab words (tfrg_ctx_create)
@@ -77,7 +85,7 @@ constexpr uint32_t kCrcTabWords = 51200;  // crc_tab words (tfrg_ctx_create)
 //   [kLiLut, + kLiLutWords) bytes: for payload length L <= kTplMaxL the first template of that
 //     length (0xff: none);
 //   [kLiTpl + t kLiTw(W)] template t: [0] L, [1] K, [2] the next template of the same length
-//     (0xff: none), [4, 4 + W) Bm, [4 + W, 4 + 2 W) Mm, [4 + 2 W, 4 + 3 W) Cm, then per slot k 4 words
+//     (0xff: none; either frame class), [3] the frame class (kLtFrame), [4, 4 + W) Bm, [4 + W, 4 + 2 W) Mm, [4 + 2 W, 4 + 3 W) Cm, then per slot k 4 words
 //     {mode | len << 8 | rank << 16 (0: absent), pos, count word (0: absent), 0}
 //     (tfrg_internal.h "Record-shape template" for the fields).
 // Packed position tables: the image (padded to whole 16 bytes) is followed by the CRC tables the
@@ -128,6 +136,11 @@ struct LeanArgs {
                           // large batches when three workgroups with their stages fit; 0: never
                           // (TFRG_TPL_STAGE=0)
   uint32_t stage_any;     // (host) staged windows on batches of any size (TFRG_TPL_STAGE=2: tests)
+  uint32_t nocrc;         // TFRG_FLAG_NO_CRC decode: no CRC arithmetic, no tables in LDS (tab_words 0); a hit
+                          // is the mask match of a template of either frame class, verdict TFRG_V_LEN_MATCH
+  uint32_t strict;        // TFRG_FLAG_STRICT_CRC decode: unchecked-frame templates take nothing
+  uint32_t uframes;       // (host) some template has an unchecked frame: with nocrc, selects the kernel
+                          // that knows frame classes
   LeanTgt tg[kLeanMaxSlots];
 };
 
@@ -317,9 +330,10 @@ uint64_t materialize_lb_words(uint64_t cap_b);
 // launchers (tfrg_kernels.hip)
 struct LaunchCfg {
   int num_cus;
-  bool lean;               // k_tpl_lane first (window-form templates, framed records with CRCs)
+  bool lean;               // k_tpl_lane first (window-form templates, framed records)
   bool tpl_full;           // the templates took their whole learning sample (the later passes are
                            // then usually empty: launched with small grids)
+  bool tpl_unchecked;      // some kept template has an unchecked frame (kLtFrame 1): hit verdicts vary
   const uint32_t* spec_h;  // host copy of DevSchema::spec (k_tpl_lane's placement targets)
   int lane_grid;           // cap: workgroups for one record per lane
   int wave_grid;

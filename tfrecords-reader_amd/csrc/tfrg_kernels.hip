@@ -3635,11 +3635,13 @@ static hipError_t launch_all(const DevBatch& b, const DevSchema& sc, const DevOu
   DevSchema scx = sc;
   if (lane_lds > kLaneLdsBudget || !fast_ok) scx.spec = nullptr;
   const uint32_t wave_stage = cfg.wave_stage < kWStage ? cfg.wave_stage : kWStage;
-  // record-shape templates first (k_tpl_lane, tfrg_tpl.hip): framed records with CRC verdicts, a
-  // schema of <= kLeanMaxSlots slots; k_lane_count then takes only the records it left
+  // record-shape templates first (k_tpl_lane, tfrg_tpl.hip): framed records (with CRC verdicts or,
+  // kFlagNoCrc, the mask match alone), a schema of <= kLeanMaxSlots slots; k_lane_count then takes
+  // only the records it left
   const bool lean = cfg.lean && sc.n_tpl && fast_ok && S <= kLeanMaxSlots && o.lmask && o.rlist &&
                     (sc.tpl_w == 16 || sc.tpl_w == 32 || sc.tpl_w == 64) &&
-                    !(b.flags & (kFlagPayloadOnly | kFlagNoCrc)) && b.nbytes < 0xffffff00ull;
+                    !(b.flags & kFlagPayloadOnly) && b.nbytes < 0xffffff00ull;
+  const bool tpl_nocrc = (b.flags & kFlagNoCrc) != 0, tpl_strict = (b.flags & kFlagStrictCrc) != 0;
   // every record of the learning sample took a template and none is above lane_max: the passes after
   // k_tpl_lane (residual lane records, slow walks, large-record CRCs, gathers of placed slots) are
   // usually empty, and a full grid of workgroups that exit at once costs ~4 us per launch; they
@@ -3653,7 +3655,8 @@ static hipError_t launch_all(const DevBatch& b, const DevSchema& sc, const DevOu
   // workgroup of k_tpl_lane does their bookkeeping (tpl_quiet_finish), or flags the batch for a full
   // re-run by the host (tfrg_result_info) if a record took no template. Saves five dependent
   // launches (~4 us each) per batch.
-  cfg.ran_optimistic = cfg.optimistic && quiet && all_spec && S > 0;
+  // (not in strict mode with unchecked-frame templates: their records are errors there, for the full passes)
+  cfg.ran_optimistic = cfg.optimistic && quiet && all_spec && S > 0 && !(tpl_strict && cfg.tpl_unchecked);
   // Optimistic without record shapes (C2: records above lane_max, every slot one inline value in the
   // learning sample, placed speculatively by k_lane_count MODE 0): k_lane_count, k_tail_count, and
   // the last workgroup of k_tail_count ends the decode (tail_quiet_finish) or flags it for a full
@@ -3682,14 +3685,20 @@ static hipError_t launch_all(const DevBatch& b, const DevSchema& sc, const DevOu
     LeanArgs a{};
     a.n_tpl = sc.n_tpl;
     a.img_words = sc.tpl_img_words;
-    a.tab_words = sc.tpl_tab_words;
+    a.tab_words = tpl_nocrc ? 0u : sc.tpl_tab_words;
+    a.nocrc = tpl_nocrc ? 1u : 0u;
+    a.strict = tpl_strict ? 1u : 0u;
+    a.uframes = cfg.tpl_unchecked ? 1u : 0u;
     a.cu_lds = cfg.tpl_cu_lds;
     a.stage_any = cfg.tpl_stage_any ? 1u : 0u;
     a.lane_max = cfg.lane_max;
     a.tsum = cfg.ran_optimistic ? nullptr : o.tsum;  // (placed slots: no scan; a re-run clears tsum)
     a.finish = cfg.ran_optimistic ? sc.slot_kind : nullptr;
-    // (optimistic: status / verdict and constant order words are implicit, tfrg_info.implicit_cols)
-    cfg.implicit = cfg.ran_optimistic ? TFRG_IMPLICIT_STATUS | (cfg.ord_const ? TFRG_IMPLICIT_ORDER : 0u) |
+    // (optimistic: status / verdict and constant order words are implicit, tfrg_info.implicit_cols;
+    // TFRG_IMPLICIT_STATUS says every verdict is 7: CRCs on and every template spec-framed, else
+    // k_tpl_lane stores status and verdict per record)
+    cfg.implicit = cfg.ran_optimistic ? (!tpl_nocrc && !cfg.tpl_unchecked ? TFRG_IMPLICIT_STATUS : 0u) |
+                                            (cfg.ord_const ? TFRG_IMPLICIT_ORDER : 0u) |
                                             (cfg.len_const ? TFRG_IMPLICIT_BYTES_LEN : 0u)
                                       : 0u;
     a.implicit = cfg.implicit;

@@ -22,6 +22,9 @@
 //     count / loc or speculatively placed value (DevSchema::spec; the row split r implicit), taken
 //     from the window registers at the template's (wave-uniform) position, and a select keeps each
 //     lane's own; then the per-tile value counts.
+// Frame classes (tfrg_internal.h kLtFrame): a record whose two CRC fields are 0 (the reference's own
+// writers) matches an unchecked-frame template of its shape, verdict TFRG_V_LEN_MATCH; a decode
+// without CRC verdicts (LeanArgs::nocrc) matches on the mask alone, with no tables in LDS.
 // A wave owns a contiguous range of groups (whole tiles, or half a tile on small batches).
 // A record no template takes (another shape, a framing or CRC mismatch) is left to k_lane_count:
 // per 64-record group a miss mask (DevOut::lmask) and a list of the groups with misses
@@ -138,7 +141,10 @@ __device__ void tpl_quiet_finish(const DevOut& o, const uint8_t* slot_kind, uint
   }
 }
 
-template <int W, int OM, bool ST>
+// UF: the launch knows frame classes (tfrg_internal.h kLtFrame) -- some template has an unchecked
+// frame, or the decode computes no CRCs (A.nocrc); a hit's verdict is then the lane's own. !UF: every
+// template is spec-framed and CRCs are on, the code of a spec-only context as it always was.
+template <int W, int OM, bool ST, bool UF>
 __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_tpl_lane(
     DevBatch B, DevOut o, LeanArgs A, const uint32_t* __restrict__ img, const uint32_t* __restrict__ tabs) {
   static_assert(W == 16 || W == 32 || W == 64, "window words");
@@ -152,7 +158,9 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
   constexpr uint32_t kTw = kLiTw(W);
   const uint32_t lane = threadIdx.x & 63u, wib = rfl(threadIdx.x >> 6);
   cu32* gimg = (cu32*)img;  // (the image's wave-uniform words: scalar loads)
-  const uint32_t crcw_u = gimg[3], chain_u = gimg[4];
+  // (A.nocrc: no variable word enters a CRC, no table is read -- none is in LDS, tab_words 0)
+  const bool nocrc = UF && A.nocrc;
+  const uint32_t crcw_u = nocrc ? 0u : gimg[3], chain_u = nocrc ? (uint32_t)W : gimg[4];
   // table word j's four tables in LDS (header words 6, 7: its place in the packed block)
   auto tabw = [&](uint32_t j) -> const uint8_t* {
     return reinterpret_cast<const uint8_t*>(tab) + 4u * kLiPtabWords * ((gimg[6u + (j >> 2)] >> (8u * (j & 3u))) & 0xffu);
@@ -316,7 +324,7 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
     while (__ballot(cand != 0xffu)) {  // (usually one pass: lengths rarely share templates)
       const bool act = cand != 0xffu;
       const uint32_t* tp = limg + kLiTpl + (act ? cand : 0u) * kTw;
-      const u32x4 meta = *reinterpret_cast<const u32x4*>(tp);  // L, K, next
+      const u32x4 meta = *reinterpret_cast<const u32x4*>(tp);  // L, K, next, frame class
       uint32_t diff = 0;
 #pragma unroll
       for (int q = 0; q < W / 4; ++q) {
@@ -343,14 +351,27 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
   if (crcw_u & (1u << (j))) lin ^= lin_word(tabw(j), (w[W - 9 + (j)] & cm[W - 9 + (j)]) ^ ((j) == 0 ? c : 0u));
       TFRG_LIN(0) TFRG_LIN(1) TFRG_LIN(2) TFRG_LIN(3) TFRG_LIN(4) TFRG_LIN(5) TFRG_LIN(6) TFRG_LIN(7)
 #undef TFRG_LIN
-      const bool ok = act && diff == 0u && crc_mask(lin ^ meta.y) == w[W - 1];
+      // spec frame: the stored data CRC is the payload's. Unchecked frame: the mask proved both
+      // stored fields 0, so the payload's must not be 0 too (that record's verdict has the DATA_CRC
+      // bit: k_lane_count's); never in strict mode, where such a record is an error. No CRCs: the
+      // mask match alone, either class.
+      bool ok = act && diff == 0u;
+      if constexpr (UF) {
+        const uint32_t mc = crc_mask(lin ^ meta.y);
+        ok = ok && (nocrc || (meta.w ? mc != 0u && !A.strict : mc == w[W - 1]));
+      } else {
+        ok = ok && crc_mask(lin ^ meta.y) == w[W - 1];
+      }
       tsel = ok ? cand : tsel;
       cand = act && !ok ? meta.z : 0xffu;
     }
     const bool hit = tsel != 0xffu;
     if (hit && !(A.implicit & TFRG_IMPLICIT_STATUS)) {  // (uniform test)
       o.status[r] = TFRG_OK;
-      o.verdict[r] = (uint8_t)kHitVerdict;
+      if constexpr (UF)  // (the lane's own: its template's frame class)
+        o.verdict[r] = (uint8_t)(nocrc || limg[kLiTpl + tsel * kTw + 3] ? (uint32_t)TFRG_V_LEN_MATCH : kHitVerdict);
+      else
+        o.verdict[r] = (uint8_t)kHitVerdict;
     }
     if (__ballot(hit)) {
       const uint32_t* ts = limg + kLiTpl + (hit ? tsel : 0u) * kTw + 4 + 3 * W;  // the lane's slot table
@@ -521,8 +542,10 @@ hipError_t launch_tpl_lane(const DevBatch& b, const DevOut& o, const LeanArgs& a
   const bool staged = w == 16 && (a2.gpw >= 8u || a.stage_any) && lds_st + 64u <= 65536u &&
                       3u * ((lds_st + 64u + 2047u) & ~(size_t)2047u) <= a.cu_lds;
   if (staged) lds = lds_st;
-#define TFRG_TPL_LAUNCH(WW, OO, SS) \
-  hipLaunchKernelGGL((k_tpl_lane<WW, OO, SS>), grid, dim3(kTplBlock), lds, st, b, o, a2, img, tabs)
+  const bool uf = a.nocrc || a.uframes;
+#define TFRG_TPL_LAUNCH(WW, OO, SS)                                                                            \
+  if (uf) hipLaunchKernelGGL((k_tpl_lane<WW, OO, SS, true>), grid, dim3(kTplBlock), lds, st, b, o, a2, img, tabs); \
+  else hipLaunchKernelGGL((k_tpl_lane<WW, OO, SS, false>), grid, dim3(kTplBlock), lds, st, b, o, a2, img, tabs)
 #define TFRG_TPL_OM(WW, SS)                                                    \
   switch (b.omode) {                                                           \
     case kOffU64: TFRG_TPL_LAUNCH(WW, kOffU64, SS); break;                     \

@@ -109,6 +109,7 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_host_ctx_destroy": (C.c_int, [C.c_void_p]),
     "tfrg_host_decode": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(TfrgHostRecord)]),
     "tfrg_template_count": (C.c_int, [C.c_void_p]),
+    "tfrg_template_frames": (C.c_int, [C.c_void_p]),
     "tfrg_template_words": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "tfrg_learn_templates_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,

@@ -156,6 +156,11 @@ class HipDecoder:
     def template_count(self) -> int:
         return int(self._lib.tfrg_template_count(self._ctx))
 
+    def template_frames(self) -> int:
+        """Frame classes of the kept templates: bit 0 spec-framed, bit 1 unchecked-framed (both CRC
+        fields 0); 0 without templates."""
+        return int(self._lib.tfrg_template_frames(self._ctx))
+
     def learn_templates(self, buf: np.ndarray, starts: np.ndarray, ends: np.ndarray, payload_only: bool = False) -> int:
         """Learn record shapes from a host sample (device-only callers; tfrg_decode_host does it itself)."""
         b = np.ascontiguousarray(buf, np.uint8)
