@@ -94,6 +94,8 @@ struct tfrg_ctx {
   uint32_t cu_lds = 65536;     // LDS bytes of a CU
   int tpl_stage = 1;           // k_tpl_lane's staged windows: TFRG_TPL_STAGE=0 off (A/B measurements), 1 on
                                // large batches, 2 on batches of any size (tests)
+  uint32_t tpl_gpw = 0;        // TFRG_TPL_GPW=2, 4 or 8: k_tpl_lane's groups per wave whatever the batch size
+                               // (tests, measurements); 0: launch_tpl_lane's choice
   // constants
   DBuf crc_tab, consts;
   // schema
@@ -198,6 +200,10 @@ int tfrg_ctx_create(int device, tfrg_ctx** out) {
   if (const char* e = getenv("TFRG_TEMPLATES")) c->tpl_on = atoi(e) != 0;  // (A/B measurements)
   if (const char* e = getenv("TFRG_SPEC")) c->spec_on = atoi(e) != 0;
   if (const char* e = getenv("TFRG_TPL_STAGE")) c->tpl_stage = atoi(e);
+  if (const char* e = getenv("TFRG_TPL_GPW")) {
+    const int v = atoi(e);
+    if (v == 2 || v == 4 || v == 8) c->tpl_gpw = (uint32_t)v;
+  }
   if (const char* e = getenv("TFRG_OPTIMISTIC")) c->optimistic_on = atoi(e) != 0;
   if (const char* e = getenv("TFRG_WALK_BESIDE")) c->walk_beside = atoi(e) != 0;
   if (const char* e = getenv("TFRG_WALK_BLOCKS")) c->walk_blocks = (uint32_t)atoi(e);
@@ -1202,6 +1208,7 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   cfg.num_cus = c->num_cus;
   cfg.tpl_cu_lds = c->tpl_stage ? c->cu_lds : 0u;
   cfg.tpl_stage_any = c->tpl_stage == 2;
+  cfg.tpl_gpw = c->tpl_gpw;
   cfg.lean = c->tpl_on && c->n_tpl;
   cfg.tpl_full = cfg.lean && c->tpl_full;
   cfg.tpl_unchecked = cfg.lean && (c->tpl_frames & 2u) != 0;

@@ -136,6 +136,8 @@ struct LeanArgs {
                           // large batches when three workgroups with their stages fit; 0: never
                           // (TFRG_TPL_STAGE=0)
   uint32_t stage_any;     // (host) staged windows on batches of any size (TFRG_TPL_STAGE=2: tests)
+  uint32_t gpw_force;     // (host) TFRG_TPL_GPW = 2, 4 or 8: launch_tpl_lane's groups per wave on batches of
+                          // any size, without the tail split (tests, measurements); 0: by batch size
   uint32_t nocrc;         // TFRG_FLAG_NO_CRC decode: no CRC arithmetic, no tables in LDS (tab_words 0); a hit
                           // is the mask match of a template of either frame class, verdict TFRG_V_LEN_MATCH
   uint32_t strict;        // TFRG_FLAG_STRICT_CRC decode: unchecked-frame templates take nothing
@@ -350,6 +352,7 @@ struct LaunchCfg {
   bool ran_quiet_big;      // (out) optimistic without shapes: k_tail_count's last workgroup ends it
   uint32_t tpl_cu_lds;     // LeanArgs::cu_lds
   bool tpl_stage_any;      // LeanArgs::stage_any
+  uint32_t tpl_gpw;        // LeanArgs::gpw_force
   bool walk_beside;        // optimistic without shapes: records above lane_max walked beside the CRC
                            // (k_tail_count's first workgroups) instead of before it (k_lane_count)
   uint32_t walk_blocks;    // cap on those workgroups (0: automatic)

@@ -3691,6 +3691,7 @@ static hipError_t launch_all(const DevBatch& b, const DevSchema& sc, const DevOu
     a.uframes = cfg.tpl_unchecked ? 1u : 0u;
     a.cu_lds = cfg.tpl_cu_lds;
     a.stage_any = cfg.tpl_stage_any ? 1u : 0u;
+    a.gpw_force = cfg.tpl_gpw;
     a.lane_max = cfg.lane_max;
     a.tsum = cfg.ran_optimistic ? nullptr : o.tsum;  // (placed slots: no scan; a re-run clears tsum)
     a.finish = cfg.ran_optimistic ? sc.slot_kind : nullptr;

@@ -44,9 +44,51 @@ static_assert(4u * kTplTabWords * kLiPtabWords + 4u * kLiMaxWords + 512u <= 6553
 // staged windows (W = 16): a wave's stage holds the span [first end - 64 rounded down to 16, last end)
 // of a group, 4 KiB and slack (64 records of 59 bytes: 3,855 bytes at most)
 constexpr uint32_t kStageWords = 1024 + 32, kStageRounds = (kStageWords * 4u + 1023u) / 1024u;
+// The staged kernel's LDS is static, two arrays: the wave stages, filled by LDS-DMA, and the tables
+// and lane image. The compiler makes every LDS read that may alias a pending LDS-DMA wait for it
+// (vmcnt(0)); reads of another array carry the alias scopes that rule it out, reads of one dynamic
+// block do not -- there the table lookups of a group would wait for the next group's span. Sized so
+// that three workgroups fit a CU's 160 KiB (2 KiB granules, 64 bytes of other static words).
+constexpr uint32_t kStTimgWords = (53248u - 64u - (kTplBlock / 64u) * kStageWords * 4u) / 16u * 4u;
+template <bool ST>
+__device__ __forceinline__ uint32_t* st_timg() {
+  if constexpr (ST) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_timg[kStTimgWords];
+    return s_timg;
+  } else {
+    return nullptr;
+  }
+}
+template <bool ST>
+__device__ __forceinline__ uint32_t* st_stage() {
+  if constexpr (ST) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[(kTplBlock / 64u) * kStageWords];
+    return s_stage;
+  } else {
+    return nullptr;
+  }
+}
 constexpr uint32_t kHitVerdict = TFRG_V_LEN_MATCH | TFRG_V_LEN_CRC | TFRG_V_DATA_CRC;
 
 typedef __attribute__((address_space(4))) const uint32_t cu32;  // wave-uniform reads -> s_load
+typedef __attribute__((address_space(3))) void lds_void;
+// Cache policy of the staged kernel's streams, both read or written once per launch: the span DMA
+// loads (aux 2 = nt, 0 = default) and the placed-value stores (1 = nt). Compile-time only, for
+// measurement builds (-DTFRG_TPL_SPAN_AUX=0 -DTFRG_TPL_STORE_NT=0: the default policy); the offsets,
+// the table and image copies and the per-lane window loads keep the default policy.
+#ifndef TFRG_TPL_SPAN_AUX
+#define TFRG_TPL_SPAN_AUX 2
+#endif
+#ifndef TFRG_TPL_STORE_NT
+#define TFRG_TPL_STORE_NT 1
+#endif
+template <bool NT, typename T>
+__device__ __forceinline__ void put(T* p, T v) {
+  if constexpr (NT)
+    __builtin_nontemporal_store(v, p);
+  else
+    *p = v;
+}
 
 __device__ __forceinline__ uint32_t rfl(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
 
@@ -150,9 +192,11 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
   static_assert(W == 16 || W == 32 || W == 64, "window words");
   static_assert(!ST || W == 16, "staged windows: W = 16");
   typedef uint32_t wvec __attribute__((ext_vector_type(W)));
-  // the packed CRC tables (A.tab_words), then the templates' lane image (whole 16 bytes both), then
-  // (ST) a stage of kStageWords per wave
-  extern __shared__ __attribute__((aligned(16))) uint32_t tab[];
+  // the packed CRC tables (A.tab_words), then the templates' lane image (whole 16 bytes both):
+  // dynamic LDS, or (ST) static, beside a stage of kStageWords per wave
+  extern __shared__ __attribute__((aligned(16))) uint32_t dyn_lds[];
+  uint32_t* tab = dyn_lds;
+  if constexpr (ST) tab = st_timg<ST>();
   uint32_t* const limg = tab + A.tab_words;
   constexpr uint32_t kWaves = kTplBlock / 64;
   constexpr uint32_t kTw = kLiTw(W);
@@ -224,13 +268,20 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
   // not decrease and lie in the batch, and the span from the first window (16-byte aligned) to the
   // last end fits the stage in whole 16-byte pieces inside the batch (so not a batch's last group,
   // unless it ends on a piece); any order and gaps the caller's offsets have pass this one test.
-  // Lane l takes pieces l, l + 64, ...; then every lane builds its window from aligned stage dwords.
-  // A lane whose window is not whole in the batch gets zeros, as from window(). Any other group:
-  // window(). The stage is the wave's own and LDS runs a wave's accesses in order: no wait between
-  // the writes, the reads and the next group's writes.
-  auto window_st = [&](wvec& wn, const LaneOff& f, uint32_t g) {
+  // fill: the span requested by LDS-DMA (buffer_load ... lds, no registers), lane l's pieces l,
+  // l + 64, ... lane-linear in the stage; issued one group ahead, so it is in flight while the
+  // group before is matched and stored. take: every lane builds its window from aligned stage
+  // dwords; a lane whose window is not whole in the batch gets zeros, as from window(). Any other
+  // group: no DMA, and take is window(). The stage is the wave's own, so the wave's own counters
+  // order it: vmcnt(0) (the DMA has landed) before take's reads, lgkmcnt(0) (the reads have
+  // returned) before the next fill -- both written out in the group loop, the compiler adds neither.
+  struct Span {  // (wave-uniform)
+    uint32_t lo;  // the stage's first byte in the batch
+    bool on;      // the group is staged
+  };
+  auto fill = [&](const LaneOff& f, uint32_t g) -> Span {
     if constexpr (ST) {
-      uint32_t* const stg = limg + A.img_words + wib * kStageWords;
+      uint32_t* const stg = st_stage<ST>() + wib * kStageWords;
       const uint32_t e = f.e;
       const uint32_t g0 = g << 6;
       const uint32_t nv = g < gend ? (B.n - g0 < 64u ? B.n - g0 : 64u) : 0u;  // valid lanes: [0, nv)
@@ -242,36 +293,44 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
         const uint32_t nch = (hi - lo + 15u) >> 4;  // 16-byte pieces
         // (the window reads run one dword past the lane's end)
         if (hi > lo && nch * 16u + 4u <= kStageWords * 4u && lo + nch * 16u <= nb) {
-          u32x4 t[kStageRounds];
 #pragma unroll
           for (uint32_t k = 0; k < kStageRounds; ++k)
             if (lane + 64u * k < nch)
-              t[k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lo + 16u * (lane + 64u * k), 0, 0));
-#pragma unroll
-          for (uint32_t k = 0; k < kStageRounds; ++k)
-            if (lane + 64u * k < nch) reinterpret_cast<u32x4*>(stg)[lane + 64u * k] = t[k];
-          __builtin_amdgcn_wave_barrier();
-          const bool full = e >= 4u * W && lane < nv;
-          const uint32_t b0 = full ? e - 4u * W - lo : 0u;
-          const uint32_t* const sp = stg + (b0 >> 2);
-          const uint32_t sh = b0 & 3u;
-          uint32_t prev = sp[0];
-#pragma unroll
-          for (int i = 0; i < W; ++i) {
-            const uint32_t nx = sp[i + 1];
-            wn[i] = __builtin_amdgcn_alignbyte(nx, prev, sh);
-            prev = nx;
-          }
-          __builtin_amdgcn_wave_barrier();
-          if (__ballot(!full)) {  // (a batch's first records, the lanes past its last one)
-#pragma unroll
-            for (int i = 0; i < W; ++i) wn[i] = full ? wn[i] : 0u;
-          }
-          return;
+              __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(stg + 256u * k), 16, lo + 16u * (lane + 64u * k), 0,
+                                                       0, TFRG_TPL_SPAN_AUX);
+          return Span{lo, true};
         }
       }
     }
+    return Span{0u, false};
+  };
+  auto take = [&](wvec& wn, const LaneOff& f, uint32_t g, const Span& sp_) {
+    if constexpr (ST) {
+      if (sp_.on) {  // (uniform)
+        const uint32_t* const stg = st_stage<ST>() + wib * kStageWords;
+        const uint32_t e = f.e;
+        const bool full = e >= 4u * W && (g << 6) + lane < B.n;  // (g < gend: the group was filled)
+        const uint32_t b0 = full ? e - 4u * W - sp_.lo : 0u;
+        const uint32_t* const sp = stg + (b0 >> 2);
+        const uint32_t sh = b0 & 3u;
+        uint32_t prev = sp[0];
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+          const uint32_t nx = sp[i + 1];
+          wn[i] = __builtin_amdgcn_alignbyte(nx, prev, sh);
+          prev = nx;
+        }
+        if (__ballot(!full)) {  // (a batch's first records, the lanes past its last one)
+#pragma unroll
+          for (int i = 0; i < W; ++i) wn[i] = full ? wn[i] : 0u;
+        }
+        return;
+      }
+    }
     window(wn, f);
+    // (ST: the per-lane window is waited for here, not at its first use: loads pending into the window
+    // registers on this path would make every group's match wait, by count, for the span behind them)
+    if constexpr (ST) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   };
   // a record ending in the batch's first 4 W bytes (group 0 only): its window begins before the
   // batch; those bytes are outside the record (template mask 0), the rest is read byte by byte. (Its
@@ -293,6 +352,9 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
         }
         if (head) wn[i] = x;
       }
+      // (ST: no byte load pending where this path joins the common one -- there the compiler would
+      // wait for everything in flight, the next group's span included, in every group)
+      if constexpr (ST) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     }
   };
   // window word q (wave-uniform): one indexed move (s_set_gpr_idx) for W <= 32; a compare chain for
@@ -407,11 +469,12 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
           if (T.kind) {  // speculative placement: value at column row r; the row split r is implicit
                          // (tfrg_info.placed_slots: a final placement's row splits are never stored)
             if (r < T.lim) {
+              constexpr bool kNt = ST && TFRG_TPL_STORE_NT;
               if (T.kind == TFRG_KIND_INT64) {
-                reinterpret_cast<uint64_t*>(T.v1)[r] = lx;
+                put<kNt>(reinterpret_cast<uint64_t*>(T.v1) + r, (uint64_t)lx);
               } else {
-                reinterpret_cast<uint32_t*>(T.v1)[r] = lx;
-                if (T.kind == TFRG_KIND_BYTES && !(A.implicit & TFRG_IMPLICIT_BYTES_LEN)) T.v2[r] = ly;
+                put<kNt>(reinterpret_cast<uint32_t*>(T.v1) + r, lx);
+                if (T.kind == TFRG_KIND_BYTES && !(A.implicit & TFRG_IMPLICIT_BYTES_LEN)) put<kNt>(T.v2 + r, ly);
               }
             }
           } else {
@@ -440,10 +503,15 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
     }
     acc = 0;
   };
-  // one group per step (one window live: the per-lane template words need the registers); the next
-  // group's offsets are requested before this group's stores. The wave's first offsets and window
-  // (ST: into its stage, which no other wave touches) are requested before the workgroup copies its CRC tables and lane image into LDS, so its first
-  // HBM round trips overlap that copy (~3 % of a launch of 2,000 workgroups).
+  // one group per step (one window live: the per-lane template words need the registers). ST: the
+  // next group's span is requested (fill) as soon as this group's windows are out of the stage, and
+  // the offsets two groups ahead after it, all before this group's match and stores; neither is
+  // touched again before the next step's wait -- a use in between would make the compiler wait for
+  // everything in flight, the DMA included, ahead of proc. !ST: the next group's window is loaded
+  // where it is consumed, its offsets requested before this group's stores. The wave's first offsets
+  // and window (ST: the fill of its stage, which no other wave touches) are requested before the
+  // workgroup copies its CRC tables and lane image into LDS, so its first HBM round trips overlap
+  // that copy (~3 % of a launch of 2,000 workgroups).
   // (the first round of the table and image copies, the first two groups' offsets: all in flight
   // together; then the first window, which needs the offsets)
   LaneOff fa = offsets(gbeg), f0 = offsets(gbeg + 1u);
@@ -456,21 +524,48 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
     if (threadIdx.x + j * kTplBlock < tab16) tv[j] = reinterpret_cast<const u32x4*>(tabs)[threadIdx.x + j * kTplBlock];
   const uint32_t iw0 = threadIdx.x < A.img_words ? img[threadIdx.x] : 0u;
   wvec wa;
-  window_st(wa, fa, gbeg);
+  Span sa{0u, false};
+  if constexpr (ST)
+    sa = fill(fa, gbeg);
+  else
+    window(wa, fa);
 #pragma unroll
   for (uint32_t j = 0; j < kTabRounds; ++j)
     if (threadIdx.x + j * kTplBlock < tab16) reinterpret_cast<u32x4*>(tab)[threadIdx.x + j * kTplBlock] = tv[j];
   if (threadIdx.x < A.img_words) limg[threadIdx.x] = iw0;
   for (uint32_t i = threadIdx.x + kTplBlock; i < A.img_words; i += kTplBlock) limg[i] = img[i];
   __syncthreads();
-  for (uint32_t g = gbeg; g < gend; ++g) {
-    head_fix(wa, fa, g);
-    proc(wa, g, fa);
-    if (((g + 1u) & 3u) == 0u || g + 1u >= gend) flush(g);
-    if (g + 1u < gend) {
-      window_st(wa, f0, g + 1u);
+  if constexpr (ST) {
+    for (uint32_t g = gbeg; g < gend; ++g) {
+      // the wave's own DMA (and every earlier load and store) has landed: the stage may be read
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+      asm volatile("" ::: "memory");
+      take(wa, fa, g, sa);
+      // the stage's dwords are in registers: it may be refilled
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+      asm volatile("" ::: "memory");
+      Span sn{0u, false};
+      if (g + 1u < gend) sn = fill(f0, g + 1u);
+      const LaneOff f2 = offsets(g + 2u);
+      head_fix(wa, fa, g);
+      proc(wa, g, fa);
+      if (((g + 1u) & 3u) == 0u || g + 1u >= gend) flush(g);
       fa = f0;
-      f0 = offsets(g + 2u);
+      f0 = f2;
+      sa = sn;
+    }
+  } else {
+    for (uint32_t g = gbeg; g < gend; ++g) {
+      head_fix(wa, fa, g);
+      proc(wa, g, fa);
+      if (((g + 1u) & 3u) == 0u || g + 1u >= gend) flush(g);
+      if (g + 1u < gend) {
+        window(wa, f0);
+        fa = f0;
+        f0 = offsets(g + 2u);
+      }
     }
   }
   if (A.finish) {  // (uniform) optimistic decode: the last workgroup to finish ends it
@@ -506,6 +601,10 @@ hipError_t launch_tpl_lane(const DevBatch& b, const DevOut& o, const LeanArgs& a
   // workgroup is L2 traffic)
   LeanArgs a2 = a;
   a2.gpw = need < (uint32_t)num_cus / 2u ? 1u : need < (uint32_t)num_cus ? 2u : need >= 8u * (uint32_t)num_cus ? 8u : 4u;
+  // (TFRG_TPL_GPW: the groups per wave of a large batch on one of any size; no tail split below, so
+  // a test of a few thousand records runs the group loop of the headline launch)
+  const bool forced = a.gpw_force == 2u || a.gpw_force == 4u || a.gpw_force == 8u;
+  if (forced) a2.gpw = a.gpw_force;
   // The dispatcher hands out workgroups in index order as slots free up, so the last ones decide
   // when the batch ends: the groups of about one round of resident workgroups (3 per CU) at the end
   // of a large batch go to workgroups of 2 groups per wave instead of gpw, and the last round idles
@@ -516,7 +615,7 @@ hipError_t launch_tpl_lane(const DevBatch& b, const DevOut& o, const LeanArgs& a
   }();
   constexpr uint32_t kW = kTplBlock / 64;
   uint32_t gsplit = groups, bsplit = 0xffffffffu;
-  if (split_on && a2.gpw == 8u) {
+  if (split_on && !forced && a2.gpw == 8u) {
     const uint32_t small = 3u * (uint32_t)num_cus * kW * 2u;  // groups of one round of 2-group workgroups
     if (groups > 4u * small) {
       const uint32_t big_blocks = (groups - small) / (kW * a2.gpw);
@@ -538,10 +637,12 @@ hipError_t launch_tpl_lane(const DevBatch& b, const DevOut& o, const LeanArgs& a
   // CU), which the memory system bounds: a small batch is one round trip after another, and the
   // stage adds its LDS round trip to each (c1file, 65,536 records: 9.2 us staged, 8.9 us not).
   // a.cu_lds 0: TFRG_TPL_STAGE=0; a.stage_any: TFRG_TPL_STAGE=2, batches of any size (tests).
-  const size_t lds_st = lds + (size_t)kW * kStageWords * 4;
-  const bool staged = w == 16 && (a2.gpw >= 8u || a.stage_any) && lds_st + 64u <= 65536u &&
+  // (the staged kernel's LDS is static: room for tables and image of kStTimgWords, no dynamic LDS)
+  constexpr size_t lds_st = ((size_t)kStTimgWords + kW * kStageWords) * 4;
+  static_assert(lds_st + 64u <= 65536u, "staged kernel's LDS");
+  const bool staged = w == 16 && (a2.gpw >= 8u || a.stage_any) && (size_t)a.tab_words + a.img_words <= kStTimgWords &&
                       3u * ((lds_st + 64u + 2047u) & ~(size_t)2047u) <= a.cu_lds;
-  if (staged) lds = lds_st;
+  if (staged) lds = 0;
   const bool uf = a.nocrc || a.uframes;
 #define TFRG_TPL_LAUNCH(WW, OO, SS)                                                                            \
   if (uf) hipLaunchKernelGGL((k_tpl_lane<WW, OO, SS, true>), grid, dim3(kTplBlock), lds, st, b, o, a2, img, tabs); \

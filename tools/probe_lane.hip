@@ -38,7 +38,7 @@ struct Cols {
 };
 
 enum : int { kU64 = 1, kStore = 2, kPipe = 4, kCheck = 8, kNoSV = 16, kNoOrd = 32, kStaged = 64, kTabLds = 128,
-             kTab8 = 256, kGlds = 512, kTab16 = 1024, kNoLen = 2048, kTab12 = 4096 };
+             kTab8 = 256, kGlds = 512, kTab16 = 1024, kNoLen = 2048, kTab12 = 4096, kSpanDma = 8192, kNt = 16384 };
 typedef __attribute__((address_space(1))) void gvoid;
 typedef __attribute__((address_space(3))) void lvoid;
 
@@ -145,7 +145,52 @@ __global__ __launch_bounds__(512, 6) void k_probe(const uint8_t* bytes, uint32_t
       }
     }
   };
-  if (MODE & kGlds) {
+  if (MODE & kSpanDma) {
+    // the staged span of the NEXT group requested by LDS-DMA (buffer_load ... lds, wave-contiguous
+    // 16-byte pieces, lane-linear in the wave's one stage) right after this group's windows were
+    // read out of the stage, so the request is in flight during proc(g); kNt: nt on those loads
+    constexpr int kAux = (MODE & kNt) ? 2 : 0;
+    auto fill = [&](uint32_t e) -> uint32_t {
+      const uint32_t e_last = __builtin_amdgcn_readlane(e, 63), e_first = __builtin_amdgcn_readfirstlane(e);
+      const uint32_t lo = (e_first >= 64u ? e_first - 64u : 0u) & ~15u;
+#pragma unroll
+      for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t off = lo + 16u * (lane + 64u * k);
+        if (off < e_last) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lvoid*)(st_w + 256u * k), 16, off, 0, 0, kAux);
+      }
+      return lo;
+    };
+    uint32_t sa, ea, sb = 0, eb = 0;
+    ends(g0, sa, ea);
+    uint32_t lo = fill(ea);
+    if (g0 + 1u < g1) ends(g0 + 1u, sb, eb);
+    for (uint32_t g = g0; g < g1; ++g) {
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the wave's own DMA has landed
+      asm volatile("" ::: "memory");
+      uint32_t w[16];
+      const uint32_t b0 = ea >= 64u ? ea - 64u - lo : 0u;
+      const uint32_t q0 = b0 >> 2, sh = b0 & 3u;
+      uint32_t prev = st_w[q0];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const uint32_t nx = st_w[q0 + i + 1];
+        w[i] = __builtin_amdgcn_alignbyte(nx, prev, sh);
+        prev = nx;
+      }
+      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the stage is read before it is refilled
+      asm volatile("" ::: "memory");
+      // (the offsets two groups ahead are not touched before the loop's end: a use of them here
+      // would make the compiler wait vmcnt(0), i.e. for the DMA, ahead of proc)
+      uint32_t sc = 0, ec = 0;
+      if (g + 1u < g1) lo = fill(eb);
+      if (g + 2u < g1) ends(g + 2u, sc, ec);
+      proc(g, sa, ea, w);
+      sa = sb;
+      ea = eb;
+      sb = sc;
+      eb = ec;
+    }
+  } else if (MODE & kGlds) {
     // round 6: each wave's next window loaded straight into its LDS buffer (global_load_lds, lane-
     // linear: lane l's 16-byte piece q at q * 1 KiB + 16 l) while this group is processed from VGPRs
     auto issue = [&](uint32_t e) {
@@ -292,6 +337,7 @@ int main(int argc, char** argv) {
   };
   // argv[2]: 6 = the round-6 rows (LDS-DMA), default = staged windows beside packed tables of
   // 12 / 16 KiB against the per-lane windows, today's store set (value columns only)
+  // 8 = the span LDS-DMA rows beside the staged row they are judged against
   const int set = argc > 2 ? atoi(argv[2]) : 7;
 #define ROW(name, mode) rep_(name, mode, tpw, run<mode>(d_b, nb, d_s64, d_e64, d_e32, n, c, tpw, reps))
   for (int rep = 0; rep < (set == 7 ? 3 : 0); ++rep)
@@ -305,6 +351,13 @@ int main(int argc, char** argv) {
       ROW("v12_staged_tab32", V | kStaged | kTabLds);
       ROW("v12_lane", V);
       ROW("v12_staged", V | kStaged);
+    }
+  for (int rep = 0; rep < (set == 8 ? 3 : 0); ++rep)
+    for (uint32_t tpw : {2u}) {
+      constexpr int V = kStore | kNoSV | kNoOrd | kNoLen;
+      ROW("v12_staged_tab12", V | kStaged | kTabLds | kTab12);
+      ROW("v12_spandma_tab12", V | kSpanDma | kTabLds | kTab12);
+      ROW("v12_spandma_nt_tab12", V | kSpanDma | kNt | kTabLds | kTab12);
     }
 #undef ROW
   for (int rep = 0; rep < (set == 6 ? 2 : 0); ++rep)
