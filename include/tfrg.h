@@ -302,6 +302,47 @@ int tfrg_result_device(tfrg_ctx* ctx, tfrg_columns* cols);
 int tfrg_result_fetch(tfrg_ctx* ctx, const tfrg_columns* host);
 
 /* ---------------------------------------------------------------------------------------------
+ * Dense device tensors from the last result (the tf.io.parse_example FixedLenFeature / padded VarLen
+ * step the reference's users run after decoder.pyx:107; no reference counterpart). One kernel on the
+ * decode's stream writes, for every spec, out[r][j] for r < n, j < width:
+ *   int64_list / float_list slot: the record's value j if it has one, else fill (TFRG_DENSE_I64;
+ *     TFRG_DENSE_I32: the low 32 bits of the int64; TFRG_DENSE_F32: the float's raw bits);
+ *     lengths[r] = the record's value count;
+ *   bytes_list slot (TFRG_DENSE_U8): byte j of element 0 of the record's list if it has one, else
+ *     fill; lengths[r] = that element's byte length (0: the list is empty or absent).
+ * d_stats (device, [n_specs][4] u32, or NULL; zeroed by the call on the stream): records whose
+ * count (bytes: length) is > width (truncated), < width (padded), records without a value, and, for
+ * bytes slots, records with more than one element.
+ * The result is a function of the columns tfrg_result_fetch returns. An optimistic or hinted decode
+ * is confirmed first, as by tfrg_result_device (the only host synchronisation); the implicit columns
+ * and the identity row splits of placed slots are neither written nor read, and a later
+ * tfrg_result_device / tfrg_result_fetch still gives the full view. Any number of calls per decode.
+ * Stream order: the decode's stream waits for the work queued on consumer_stream so far (the
+ * caller's allocator may have work pending on the outputs), and consumer_stream then waits for the
+ * kernel; consumer_stream NULL is the decode's stream itself. n == 0 launches nothing.
+ * TFRG_E_ARG (text in tfrg_last_error): no result, n_specs 0 or > TFRG_DENSE_MAX_SPECS, a slot >=
+ * n_slots, a dtype that does not fit the slot's kind, a width outside 1..TFRG_DENSE_MAX_WIDTH, a NULL
+ * out, a nonzero reserved.
+ * ------------------------------------------------------------------------------------------- */
+#define TFRG_DENSE_I64 0
+#define TFRG_DENSE_I32 1
+#define TFRG_DENSE_F32 2
+#define TFRG_DENSE_U8 3
+#define TFRG_DENSE_MAX_SPECS 64
+#define TFRG_DENSE_MAX_WIDTH 4096
+typedef struct tfrg_dense_spec {
+  uint32_t slot;      /* column, as in tfrg_set_schema */
+  uint32_t dtype;     /* TFRG_DENSE_* ; must fit the slot's kind */
+  uint32_t width;     /* 1..TFRG_DENSE_MAX_WIDTH */
+  uint32_t reserved;  /* 0 */
+  uint64_t fill;      /* raw low bits of the pad value */
+  void* out;          /* device, [n][width] row-major, caller-owned */
+  int32_t* lengths;   /* device [n], or NULL */
+} tfrg_dense_spec;
+int tfrg_result_dense(tfrg_ctx* ctx, const tfrg_dense_spec* specs, uint32_t n_specs, uint32_t* d_stats,
+                      void* consumer_stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Double-buffered host -> HBM decode stream (replaces reader.py:212-247's per-record ThreadPool
  * read+decode for whole-dataset reads). Two slots, each with a pinned staging buffer of batch_bytes,
  * a device input buffer and its own decode context + stream. tfrg_stream_submit hands a batch (pieces:

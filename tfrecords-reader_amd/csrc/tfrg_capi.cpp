@@ -13,6 +13,7 @@
 
 #include "../../include/tfrg.h"
 #include "crc32c.h"
+#include "tfrg_dense.h"
 #include "tfrg_internal.h"
 
 namespace tfrg {
@@ -121,6 +122,8 @@ struct tfrg_ctx {
   uint32_t n = 0;
   uint64_t cap_hint = 0;  // tfrg_decode_host: total bytes of the given ranges (>= nbytes when they overlap)
   hipEvent_t order_ev = nullptr;  // orders a decode on a new stream after the previous one
+  hipEvent_t dense_ev[2] = {nullptr, nullptr};  // tfrg_result_dense: consumer stream -> decode stream -> consumer
+  int dense_nt = 0;  // k_dense's output stores nontemporal (env TFRG_DENSE_NT=1, for A/B measurements)
   uint64_t nbytes = 0;
   uint64_t cap_i64 = 0, cap_f32 = 0, cap_b = 0;
   bool have_result = false;
@@ -207,6 +210,7 @@ int tfrg_ctx_create(int device, tfrg_ctx** out) {
   if (const char* e = getenv("TFRG_OPTIMISTIC")) c->optimistic_on = atoi(e) != 0;
   if (const char* e = getenv("TFRG_WALK_BESIDE")) c->walk_beside = atoi(e) != 0;
   if (const char* e = getenv("TFRG_WALK_BLOCKS")) c->walk_blocks = (uint32_t)atoi(e);
+  if (const char* e = getenv("TFRG_DENSE_NT")) c->dense_nt = atoi(e) != 0;
   if (const char* e = getenv("TFRG_DEBUG_POISON_LOC")) {  // "r0,r1,..." (at most 4)
     char* q = const_cast<char*>(e);
     for (int i = 0; i < 4 && *q; ++i) {
@@ -283,6 +287,8 @@ int tfrg_ctx_destroy(tfrg_ctx* c) {
                  &c->dq, &c->dq_cnt, &c->lmask, &c->rlist};
   for (DBuf* b : all) b->release();
   if (c->order_ev) (void)hipEventDestroy(c->order_ev);
+  for (hipEvent_t e : c->dense_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->have_events)
     for (auto& e : c->ev) (void)hipEventDestroy(e);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1484,6 +1490,114 @@ int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
   d->miss = c->miss.as<uint32_t>();
   d->bytes_data = c->materialized ? c->bdata.as<uint8_t>() : nullptr;
   d->bytes_offsets = c->materialized ? c->boff64.as<uint64_t>() : nullptr;
+  return 0;
+}
+
+int tfrg_result_dense(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_specs, uint32_t* d_stats,
+                      void* consumer_stream) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_result_dense: " + why);
+    return TFRG_E_ARG;
+  };
+  if (!c) return bad("no context");
+  if (!c->have_result) return bad("no result (decode first)");
+  if (!specs || n_specs == 0 || n_specs > TFRG_DENSE_MAX_SPECS)
+    return bad("n_specs must be 1.." + std::to_string(TFRG_DENSE_MAX_SPECS));
+  static_assert(TFRG_DENSE_MAX_SPECS == kDenseMaxSpecs && TFRG_DENSE_MAX_WIDTH == kDenseMaxWidth &&
+                    TFRG_DENSE_I64 == kDenseI64 && TFRG_DENSE_I32 == kDenseI32 && TFRG_DENSE_F32 == kDenseF32 &&
+                    TFRG_DENSE_U8 == kDenseU8,
+                "tfrg.h mirrors tfrg_dense.h");
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_dense_spec& s = specs[i];
+    const std::string at = "spec " + std::to_string(i) + ": ";
+    if (s.slot >= c->n_slots) return bad(at + "slot " + std::to_string(s.slot) + " >= n_slots");
+    const uint32_t kind = c->slot_kind_h[s.slot] & 3u;
+    const bool fits = (kind == TFRG_KIND_INT64 && (s.dtype == TFRG_DENSE_I64 || s.dtype == TFRG_DENSE_I32)) ||
+                      (kind == TFRG_KIND_FLOAT && s.dtype == TFRG_DENSE_F32) ||
+                      (kind == TFRG_KIND_BYTES && s.dtype == TFRG_DENSE_U8);
+    if (!fits) return bad(at + "dtype " + std::to_string(s.dtype) + " does not fit the slot's kind " + std::to_string(kind));
+    if (s.width == 0 || s.width > TFRG_DENSE_MAX_WIDTH)
+      return bad(at + "width must be 1.." + std::to_string(TFRG_DENSE_MAX_WIDTH));
+    if (!s.out) return bad(at + "out is NULL");
+    if (s.reserved) return bad(at + "reserved must be 0");
+  }
+  if (c->n == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  // an optimistic or hinted decode is confirmed (or re-run) first, as tfrg_result_device does
+  if (c->opt_pending || c->hinted) {
+    uint32_t h[kInfoCount];
+    uint64_t kt[4];
+    const int rc = finish_decode(c, h, kt);
+    if (rc) return rc;
+    if (h[kInfoOverflow]) {
+      set_error("value columns overflowed their capacity (overlapping ranges in a device batch): decode "
+                "the ranges from host memory (tfrg_decode_host) or split the batch");
+      return TFRG_E_LIMIT;
+    }
+  }
+  DenseArgs a{};
+  a.rs = c->rs.as<uint32_t>();
+  a.slot_base = c->slot_base.as<uint64_t>();
+  // (k_dense reads element 0 of a value array for a record without a value, and drops it: an array
+  // that was never allocated is stood in for by the slot bases, which every result has)
+  auto col = [&](const DBuf& b) { return b.p ? b.p : c->slot_base.p; };
+  a.i64 = static_cast<const int64_t*>(col(c->i64));
+  a.f32 = static_cast<const uint32_t*>(col(c->f32));
+  a.b_off = static_cast<const uint32_t*>(col(c->b_off));
+  a.b_len = static_cast<const uint32_t*>(col(c->b_len));
+  // the bytes' source: the views' input buffer, readable to round_up(nbytes, 16), or the byte column
+  uint64_t bound;
+  if (c->materialized) {
+    a.b_off64 = static_cast<const uint64_t*>(col(c->boff64));
+    a.in = c->bdata.as<uint8_t>();
+    bound = c->bdata.p ? (uint64_t)c->bdata.cap & ~15ull : 0;
+  } else {
+    a.in = c->last.d_bytes;
+    bound = a.in ? (c->last.nbytes + 15ull) & ~15ull : 0;
+  }
+  a.in_bound = (uint32_t)std::min<uint64_t>(bound, 0xfffffff0ull);
+  a.info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
+  a.stats = d_stats;
+  a.n = c->n;
+  a.n_specs = n_specs;
+  a.nt = (uint32_t)c->dense_nt;
+  const bool const_len = (c->last_implicit & TFRG_IMPLICIT_BYTES_LEN) != 0;
+  // workgroups per spec: one per chunk of its output, within an even share of 16 per CU
+  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 16u / n_specs);
+  uint32_t blocks = 0;
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_dense_spec& s = specs[i];
+    DenseSpec& d = a.sp[i];
+    d.out = s.out;
+    d.lengths = s.lengths;
+    d.fill = s.fill;
+    d.slot = s.slot;
+    d.dtype = s.dtype;
+    d.width = s.width;
+    d.const_len = kDenseNoLen;  // (as implicit_len_runs: the column is not stored, the shapes' length holds)
+    if (const_len && s.dtype == TFRG_DENSE_U8) d.const_len = s.slot < c->const_len.size() ? c->const_len[s.slot] : 0u;
+    const uint64_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
+    const uint64_t total = (uint64_t)c->n * s.width * isz;
+    // 16-byte units, or single elements where the output's base is not 16-byte aligned
+    const uint64_t work = ((uintptr_t)s.out & 15u) ? total / isz : (total >> 4) + 16;
+    d.blk0 = blocks;
+    d.nblk = (uint32_t)std::min<uint64_t>(cap, (work + kDenseChunk - 1) / kDenseChunk);
+    blocks += d.nblk;
+  }
+  const hipStream_t st = c->last_stream;
+  const hipStream_t cs = consumer_stream ? static_cast<hipStream_t>(consumer_stream) : st;
+  if (cs != st) {
+    for (hipEvent_t& e : c->dense_ev)
+      if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->dense_ev[0], cs));
+    HIP_TRY(hipStreamWaitEvent(st, c->dense_ev[0], 0));
+  }
+  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
+  HIP_TRY(launch_dense(a, blocks, st));
+  if (cs != st) {
+    HIP_TRY(hipEventRecord(c->dense_ev[1], st));
+    HIP_TRY(hipStreamWaitEvent(cs, c->dense_ev[1], 0));
+  }
   return 0;
 }
 

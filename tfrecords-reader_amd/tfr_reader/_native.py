@@ -80,6 +80,25 @@ class TfrgColumns(C.Structure):
     ]
 
 
+class TfrgDenseSpec(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("dtype", C.c_uint32),
+        ("width", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("fill", C.c_uint64),
+        ("out", C.c_void_p),
+        ("lengths", C.c_void_p),
+    ]
+
+
+DENSE_I64 = 0
+DENSE_I32 = 1
+DENSE_F32 = 2
+DENSE_U8 = 3
+DENSE_MAX_SPECS = 64
+DENSE_MAX_WIDTH = 4096
+
 # name -> (restype, argtypes); the exact list of exported symbols declared in include/tfrg.h
 SIGNATURES: dict[str, tuple] = {
     "tfrg_abi_version": (C.c_int, []),
@@ -150,6 +169,7 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_result_info": (C.c_int, [C.c_void_p, C.POINTER(TfrgInfo)]),
     "tfrg_result_device": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),
     "tfrg_result_fetch": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),
+    "tfrg_result_dense": (C.c_int, [C.c_void_p, C.POINTER(TfrgDenseSpec), C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 FLAG_PAYLOAD_ONLY = 1

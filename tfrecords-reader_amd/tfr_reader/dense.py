@@ -1,0 +1,475 @@
+"""Dense tensors from decoded batches: the ``tf.io.parse_example`` step (FixedLenFeature / padded
+VarLenFeature) that the reference's users run after its decoder, here on the device.
+
+A decode ends as ragged columns (``BatchResult`` on the host, ``tfrg_result_device`` on the device).
+``Dense`` specs name the fixed-shape outputs a training loop takes -- ``[n, width]`` per key, padded
+with ``fill`` or truncated, in the dtype the model wants -- and
+
+* ``HipDecoder.dense`` / ``ShardDecoder.dense`` / ``TFRecordDatasetReader.load_tensors`` collate
+  them on the device with one kernel per decoded batch (``tfrg_result_dense``), into torch tensors
+  ordered with the caller's stream;
+* ``BatchResult.dense`` / ``densify`` compute the same function with numpy from fetched columns (the
+  host path, and the reference the device path is tested against).
+
+Per output: ``lengths[r]`` is the record's untruncated value count (bytes: the byte length of the
+list's first element, 0 if the list is empty or absent) and ``stats`` the four counters
+``(truncated, padded, empty, multi)``: records whose count (bytes: length) is above / below the
+width, records without a value, and (bytes) records with more than one element.
+"""
+
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+from collections.abc import Mapping, Sequence
+from dataclasses import dataclass
+
+import numpy as np
+
+from tfr_reader import _native as N
+from tfr_reader import _status as S
+
+#: dtype name -> (TFRG_DENSE_* id, slot kind, numpy dtype, unsigned dtype of the same size)
+DTYPES = {
+    "int64": (N.DENSE_I64, 3, np.int64, np.uint64),
+    "int32": (N.DENSE_I32, 3, np.int32, np.uint32),
+    "float32": (N.DENSE_F32, 2, np.float32, np.uint32),
+    "uint8": (N.DENSE_U8, 1, np.uint8, np.uint8),
+}
+STAT_NAMES = ("truncated", "padded", "empty", "multi")
+
+
+@dataclass(frozen=True)
+class Dense:
+    """One dense output: ``key``'s values as ``[n, width]`` of ``dtype`` ("int64", "int32",
+    "float32", "uint8"). The dtype selects the slot kind (int64_list, float_list, bytes_list), so a
+    key that occurs with several kinds is unambiguous. ``fill`` pads short records (a float for
+    float32). ``lengths``: also return the per-record lengths. ``name``: the output's name in the
+    result (default: the key; needed when one key is asked for twice)."""
+
+    key: str
+    dtype: str
+    width: int = 1
+    fill: float | int = 0
+    lengths: bool = False
+    name: str | None = None
+
+    def __post_init__(self) -> None:
+        if self.dtype not in DTYPES:
+            raise ValueError(f"Dense({self.key!r}): dtype must be one of {sorted(DTYPES)}, not {self.dtype!r}")
+        if not isinstance(self.width, (int, np.integer)) or not 1 <= int(self.width) <= N.DENSE_MAX_WIDTH:
+            raise ValueError(f"Dense({self.key!r}): width must be in 1..{N.DENSE_MAX_WIDTH}, not {self.width!r}")
+        if not isinstance(self.key, str):
+            raise TypeError(f"Dense key must be a str, not {type(self.key).__name__}")
+        self.fill_bits  # noqa: B018 (validates the fill)
+
+    @property
+    def out_name(self) -> str:
+        return self.name if self.name is not None else self.key
+
+    @property
+    def fill_bits(self) -> int:
+        """The pad value's raw bits, as ``tfrg_dense_spec.fill`` takes them."""
+        if self.dtype == "float32":
+            return int(np.array(self.fill, np.float32).view(np.uint32))
+        v = int(self.fill)
+        if self.dtype == "uint8":
+            if not 0 <= v <= 255:
+                raise ValueError(f"Dense({self.key!r}): a uint8 fill must be in 0..255, not {v}")
+            return v
+        bits = 64 if self.dtype == "int64" else 32
+        if not -(1 << (bits - 1)) <= v < (1 << bits):
+            raise ValueError(f"Dense({self.key!r}): fill {v} does not fit {self.dtype}")
+        return v & ((1 << bits) - 1)
+
+
+def check_specs(specs: Sequence[Dense]) -> list[Dense]:
+    specs = list(specs)
+    if not 1 <= len(specs) <= N.DENSE_MAX_SPECS:
+        raise ValueError(f"between 1 and {N.DENSE_MAX_SPECS} Dense specs per call, not {len(specs)}")
+    seen = set()
+    for s in specs:
+        if not isinstance(s, Dense):
+            raise TypeError(f"specs must be Dense objects, not {type(s).__name__}")
+        if s.out_name in seen:
+            raise ValueError(f"two Dense specs are named {s.out_name!r}: give one of them name=")
+        seen.add(s.out_name)
+    return specs
+
+
+class DenseBatch(dict):
+    """name -> ``[n, width]`` array (torch tensors on the decoder's device, numpy arrays on the host
+    path); ``lengths[name]`` for the specs that asked for them; ``stats[name]`` the four counters
+    ``STAT_NAMES`` as a uint32 array (read back from the device on first access)."""
+
+    def __init__(self, values: Mapping, lengths: Mapping, stats) -> None:
+        super().__init__(values)
+        self.lengths = dict(lengths)
+        self._stats = stats  # a dict, or a function returning it
+
+    @property
+    def stats(self) -> dict[str, np.ndarray]:
+        if callable(self._stats):
+            self._stats = self._stats()
+        return self._stats
+
+
+def check_strict(specs: Sequence[Dense], stats: Mapping[str, np.ndarray]) -> None:
+    """The FixedLenFeature contract: every record has exactly ``width`` values (bytes: one element of
+    ``width`` bytes)."""
+    for s in specs:
+        t, p, _, m = (int(x) for x in stats[s.out_name])
+        if t or p or m:
+            raise ValueError(f"Dense({s.key!r}, {s.dtype!r}, width={s.width}): {t} records truncated, {p} padded, "
+                             f"{m} with more than one element")
+
+
+# ---------------------------------------------------------------------- host path (numpy)
+def find_slot(slot_key: Sequence[str | None], slot_kind: Sequence[int], key: str, kind: int) -> int | None:
+    for s, (k, kd) in enumerate(zip(slot_key, slot_kind)):
+        if k == key and kd == kind:
+            return s
+    return None
+
+
+def densify(specs: Sequence[Dense], *, n: int, slot_key: Sequence[str | None], slot_kind: Sequence[int],
+            row_splits: np.ndarray, slot_base: np.ndarray, i64: np.ndarray, f32: np.ndarray,
+            bytes_off: np.ndarray | None = None, bytes_len: np.ndarray | None = None, buf: np.ndarray | None = None,
+            bytes_data: np.ndarray | None = None, bytes_offsets: np.ndarray | None = None,
+            strict: bool = False) -> DenseBatch:
+    """The dense outputs of ``specs`` from plain result columns (``BatchResult``'s: ``row_splits``
+    ``[n_slots][n + 1]``, ``slot_base``, the value arrays; bytes as ``(bytes_off, bytes_len)`` views
+    into ``buf``, or ``bytes_data`` / ``bytes_offsets``), record by record. A key without a slot
+    gives an all-``fill`` output (``strict``: KeyError)."""
+    specs = check_specs(specs)
+    values, lengths, stats = {}, {}, {}
+    for sp in specs:
+        _, kind, dt, udt = DTYPES[sp.dtype]
+        W = int(sp.width)
+        out = np.full((n, W), sp.fill_bits, udt)
+        lens = np.zeros(n, np.int32)
+        st = np.zeros(4, np.uint32)
+        s = find_slot(slot_key, slot_kind, sp.key, kind)
+        if s is None:
+            if strict:
+                raise KeyError(sp.key)
+            st[1] = st[2] = n
+        else:
+            base = int(slot_base[s])
+            rs = np.asarray(row_splits[s]).astype(np.int64)
+            for r in range(n):
+                lo, c = base + int(rs[r]), int(rs[r + 1] - rs[r])
+                if kind == 1:
+                    ln = 0
+                    if c:
+                        if bytes_data is not None:
+                            elem = bytes_data[int(bytes_offsets[lo]) : int(bytes_offsets[lo + 1])]
+                            ln = int(elem.size)
+                        else:
+                            o, ln = int(bytes_off[lo]), int(bytes_len[lo])
+                            elem = buf[o : o + ln]
+                        m = min(ln, W, int(elem.size))  # (a view past the input reads zeros)
+                        out[r, :m] = elem[:m]
+                        out[r, m : min(ln, W)] = 0
+                    st[3] += c > 1
+                else:
+                    ln = c
+                    m = min(c, W)
+                    src = f32 if kind == 2 else i64
+                    out[r, :m] = np.asarray(src[lo : lo + m]).view(np.uint32 if kind == 2 else np.uint64).astype(udt)
+                lens[r] = ln
+                st[0] += ln > W
+                st[1] += ln < W
+                st[2] += c == 0
+        values[sp.out_name] = out.view(dt)
+        if sp.lengths:
+            lengths[sp.out_name] = lens
+        stats[sp.out_name] = st
+    if strict:
+        check_strict(specs, stats)
+    return DenseBatch(values, lengths, stats)
+
+
+def batch_dense(res, specs: Sequence[Dense], strict: bool = False) -> DenseBatch:
+    """``BatchResult.dense``: ``densify`` over a fetched result's columns."""
+    if strict and res.status.any():
+        res.raise_for(int(np.flatnonzero(res.status)[0]))
+    return densify(specs, n=len(res), slot_key=res.slot_key, slot_kind=res.slot_kind, row_splits=res.row_splits,
+                   slot_base=res.slot_base, i64=res.i64, f32=res.f32, bytes_off=res.bytes_off,
+                   bytes_len=res.bytes_len, buf=res.buf, bytes_data=res.bytes_data, bytes_offsets=res.bytes_offsets,
+                   strict=strict)
+
+
+# ---------------------------------------------------------------------- device path
+def resolve_slot(dec, sp: Dense) -> int | None:
+    """The device column of a spec on ``dec`` (None: the key / kind is not in its key table)."""
+    kt = dec.keys
+    kid = kt.key_ids.get(sp.key.encode("utf-8"))
+    if kid is None:
+        return None
+    s = kt.slots.get((kid, DTYPES[sp.dtype][1]))
+    if s is None or s >= getattr(dec, "_pushed_slots", 0):
+        return None
+    return s
+
+
+def launch(dec, items: Sequence[tuple], stats_ptr: int | None, consumer: int | None) -> None:
+    """One ``tfrg_result_dense`` call: items are (slot, TFRG_DENSE_* id, width, fill bits, out
+    pointer, lengths pointer or None)."""
+    arr = (N.TfrgDenseSpec * len(items))()
+    for a, (slot, dt, width, fill, out, lens) in zip(arr, items):
+        a.slot, a.dtype, a.width, a.reserved, a.fill, a.out, a.lengths = slot, dt, width, 0, fill, out, lens
+    N.check(dec._lib.tfrg_result_dense(dec._ctx, arr, len(items), C.c_void_p(stats_ptr) if stats_ptr else None,
+                                       C.c_void_p(consumer) if consumer else None), "tfrg_result_dense")
+
+
+_SIDE_STREAMS: dict = {}
+
+
+class _Collator:
+    """Torch outputs of ``specs`` for ``n`` rows on ``device``, written batch by batch: batch k of
+    ``n_batches`` fills rows [r0, r1) from its decoder's last result. Tensors come from
+    ``torch.empty`` on the current torch stream, which is handed to the library as the consumer
+    stream: the collate kernels start after the work queued on it so far and the stream waits for
+    them, so the tensors are used like any other torch result."""
+
+    def __init__(self, specs: Sequence[Dense], n: int, device: int, n_batches: int, out: Mapping | None = None,
+                 stream: int | None = None) -> None:
+        import torch  # noqa: PLC0415
+
+        self.torch = torch
+        self.specs = check_specs(specs)
+        self.n = n
+        self.dev = torch.device("cuda", device)
+        tdt = {"int64": torch.int64, "int32": torch.int32, "float32": torch.float32, "uint8": torch.uint8}
+        self.values, self.lengths = {}, {}
+        with torch.cuda.device(self.dev):
+            self.cur = torch.cuda.current_stream(self.dev)
+            for sp in self.specs:
+                given = (out or {}).get(sp.out_name)
+                lens = None
+                if isinstance(given, tuple):
+                    given, lens = given
+                shape = (n, int(sp.width))
+                if given is None:
+                    given = torch.empty(shape, dtype=tdt[sp.dtype], device=self.dev)
+                self._check(given, shape, tdt[sp.dtype], sp.out_name)
+                if sp.lengths:
+                    if lens is None:
+                        lens = torch.empty((n,), dtype=torch.int32, device=self.dev)
+                    self._check(lens, (n,), torch.int32, sp.out_name + " lengths")
+                    self.lengths[sp.out_name] = lens
+                self.values[sp.out_name] = given
+            self.k = len(self.specs)
+            self.stats = torch.zeros((max(n_batches, 1), self.k, 4), dtype=torch.int32, device=self.dev)
+            self.absent = np.zeros((self.k, 4), np.int64)  # counters of the (batch, spec) pairs without a slot
+            self.calls: list = []  # (batch, spec indices of the call's counters)
+            # the consumer stream; the legacy default stream (handle 0, which NULL would not name) is
+            # stood in for by a side stream ordered after and before it
+            self.side = None
+            self.consumer = stream if stream is not None else int(self.cur.cuda_stream)
+            if not self.consumer:
+                self.side = _SIDE_STREAMS.get(device)
+                if self.side is None:
+                    self.side = _SIDE_STREAMS[device] = torch.cuda.Stream(self.dev)
+                self.side.wait_stream(self.cur)
+                self.consumer = int(self.side.cuda_stream)
+
+    def _check(self, t, shape, dtype, what: str) -> None:
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self.dev or not t.is_contiguous():
+            raise ValueError(f"out[{what!r}] must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.dev}")
+
+    def _fill(self, t, sp: Dense) -> None:
+        torch = self.torch
+        bits = sp.fill_bits
+        if sp.dtype == "uint8":
+            t.fill_(bits)
+        elif sp.dtype == "int64":
+            t.fill_(bits - (1 << 64) if bits >= 1 << 63 else bits)
+        else:
+            t.view(torch.int32).fill_(bits - (1 << 32) if bits >= 1 << 31 else bits)
+
+    def run(self, dec, r0: int, r1: int, k: int, strict: bool = False) -> None:
+        """Rows [r0, r1) from ``dec``'s last decode (r1 - r0 records), as batch k."""
+        if r1 <= r0:
+            return
+        items, rows = [], []
+        for i, sp in enumerate(self.specs):
+            t = self.values[sp.out_name]
+            lens = self.lengths.get(sp.out_name)
+            slot = resolve_slot(dec, sp)
+            if slot is None:
+                if strict:
+                    raise KeyError(sp.key)
+                with self.torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
+                    self._fill(t[r0:r1], sp)
+                    if lens is not None:
+                        lens[r0:r1].zero_()
+                self.absent[i, 1] += r1 - r0
+                self.absent[i, 2] += r1 - r0
+                continue
+            rows.append(i)
+            items.append((slot, DTYPES[sp.dtype][0], int(sp.width), sp.fill_bits,
+                          t.data_ptr() + r0 * t.stride(0) * t.element_size(),
+                          lens.data_ptr() + 4 * r0 if lens is not None else None))
+        if items:
+            # (the library's counters are per spec of the call: its rows map back on the host)
+            launch(dec, items, self.stats[k].data_ptr(), self.consumer)
+            self.calls.append((k, rows))
+
+    def finish(self, strict: bool = False) -> DenseBatch:
+        if self.side is not None:
+            self.cur.wait_stream(self.side)
+        specs, stats_t, absent, calls = self.specs, self.stats, self.absent, self.calls
+
+        def stats() -> dict:
+            got = stats_t.cpu().numpy().view(np.uint32)
+            tot = absent.copy()
+            for k, rows in calls:
+                tot[rows] += got[k, : len(rows)]
+            return {sp.out_name: tot[i].astype(np.uint32) for i, sp in enumerate(specs)}
+
+        b = DenseBatch(self.values, self.lengths, stats)
+        if strict:
+            check_strict(specs, b.stats)
+        return b
+
+
+def _raise_first_error(dec, info) -> None:
+    """Raises the exception of the last decode's first failing record (``strict``)."""
+    n = int(info.n_records)
+    status, aux = np.empty(n, np.int32), np.empty(n, np.int64)
+    cols = N.TfrgColumns()
+    cols.status, cols.aux = N.ptr(status, N.i32p), N.ptr(aux, N.i64p)
+    N.check(dec._lib.tfrg_result_fetch(dec._ctx, C.byref(cols)), "tfrg_result_fetch")
+    r = int(info.first_error)
+    st, ax = int(status[r]), int(aux[r])
+    key = None
+    host = getattr(dec, "_last_host", None)
+    if st == S.ERR_KEY_UTF8 and host is not None:
+        buf, starts, payload_only = host
+        a = ax & 0xFFFFFFFFFFFFFFFF
+        p = int(starts[r]) + (0 if payload_only else 12) + (a >> 32)
+        key = bytes(buf[p : p + (a & 0xFFFFFFFF)])
+    raise S.exception_for(st, ax, key)
+
+
+def decoder_dense(dec, specs: Sequence[Dense], *, strict: bool = False, out: Mapping | None = None,
+                  stream: int | None = None) -> DenseBatch:
+    """``HipDecoder.dense``: the dense outputs of the decoder's last decode (``decode``,
+    ``decode_device`` or ``decode_device32``), as torch tensors on its device.
+
+    ``out``: name -> a preallocated tensor, or ``(tensor, lengths tensor)``; for callers without
+    torch, name -> a raw device pointer or ``(pointer, lengths pointer)`` for every spec (then the
+    result holds the pointers, no counters are kept and ``stream`` -- a HIP stream handle, default
+    the decode's own stream -- is the consumer stream). ``strict``: ValueError naming the key when a
+    record is truncated, padded or holds several bytes elements (FixedLenFeature), KeyError for a key
+    the batch does not have, and the first failing record's exception when a record failed."""
+    specs = check_specs(specs)
+    n = getattr(dec, "_last_n", None)
+    info = None
+    if n is None or strict:
+        info = dec.info()
+        n = int(info.n_records)
+    if strict and info.n_errors:
+        _raise_first_error(dec, info)
+    raw = bool(out) and all(isinstance(v, (int, np.integer)) or (isinstance(v, tuple) and isinstance(v[0], (int, np.integer)))
+                            for v in out.values())
+    if raw:
+        if strict:
+            raise ValueError("strict needs the counters: pass torch tensors (or none) as out=")
+        items, values, lengths = [], {}, {}
+        for sp in specs:
+            v = out[sp.out_name]
+            ptr, lens = (v if isinstance(v, tuple) else (v, None))
+            slot = resolve_slot(dec, sp)
+            if slot is None:
+                raise KeyError(sp.key)
+            items.append((slot, DTYPES[sp.dtype][0], int(sp.width), sp.fill_bits, int(ptr), int(lens) if lens else None))
+            values[sp.out_name] = int(ptr)
+            if lens:
+                lengths[sp.out_name] = int(lens)
+        if n:
+            launch(dec, items, None, stream)
+        return DenseBatch(values, lengths, {})
+    col = _Collator(specs, n, dec.device, 1, out, stream)
+    col.run(dec, 0, n, 0, strict)
+    return col.finish(strict)
+
+
+def shard_dense(sd, plan: np.ndarray, specs: Sequence[Dense], *, strict: bool = False, out: Mapping | None = None,
+                stream: int | None = None) -> DenseBatch:
+    """``ShardDecoder.dense``: one output per spec over the whole plan of the last
+    ``decode_device`` / ``decode_device32``; batch k's context writes rows [plan[k, 0], plan[k, 1])
+    on its own stream."""
+    n = int(plan[-1, 1]) if len(plan) else 0
+    col = _Collator(specs, n, sd.device, len(plan), out, stream)
+    for k, (r0, r1, _, _) in enumerate(plan.tolist()):
+        d = sd.decs[k]
+        if strict:
+            info = d.info()
+            if info.n_errors:
+                _raise_first_error(d, info)
+        col.run(d, r0, r1, k, strict)
+    return col.finish(strict)
+
+
+def load_tensors(reader, selection, specs: Sequence[Dense], device: int | None = None) -> DenseBatch:
+    """``TFRecordDatasetReader.load_tensors``: the records of an index selection as dense tensors
+    with rows in selection order. The records are staged back to back in that order
+    (tfrg_gather_ranges), decoded in batches below the per-call cap with their CRC verdicts and
+    collated on the device. Raises the first failing record's exception, as ``load_records``."""
+    from tfr_reader import _frame as F  # noqa: PLC0415
+    from tfr_reader import _io, hip  # noqa: PLC0415
+    from tfr_reader import reader as R  # noqa: PLC0415
+
+    specs = check_specs(specs)
+    cols = F.columns(selection, ["tfrecord_filename", "tfrecord_start", "tfrecord_end"])
+    names = list(cols["tfrecord_filename"])
+    starts = np.asarray(cols["tfrecord_start"], np.uint64).reshape(-1)
+    ends = np.asarray(cols["tfrecord_end"], np.uint64).reshape(-1)
+    n = len(names)
+    dev = 0 if device is None else int(device)
+    dec = hip.default_decoder(dev)
+    images: dict = {}
+    for i, name in enumerate(names):
+        img = images.get(name)
+        if img is None:
+            path = R.join_path(reader.dataset_dir, name)
+            R._check_path(path)
+            img = images[name] = _io.file_image(path)
+        if int(starts[i]) >= img.size or ends[i] <= starts[i] or int(ends[i]) > img.size:
+            raise OSError(f"Failed to read data from {(int(starts[i]), int(ends[i]))}!")
+    lens = ends - starts
+    # batches of whole records below the per-call cap
+    cuts = [0]
+    acc = 0
+    for i in range(n):
+        if acc and acc + int(lens[i]) > R.MAX_BATCH_BYTES:
+            cuts.append(i)
+            acc = 0
+        acc += int(lens[i])
+    cuts.append(n)
+    col = _Collator(specs, n, dev, len(cuts) - 1)
+    lib = N.lib()
+    for k in range(len(cuts) - 1):
+        r0, r1 = cuts[k], cuts[k + 1]
+        if r1 <= r0:
+            continue
+        b_en = np.cumsum(lens[r0:r1], dtype=np.uint64)
+        b_st = b_en - lens[r0:r1]
+        buf = np.empty(int(b_en[-1]), np.uint8)
+        i = r0
+        while i < r1:  # one gather per run of records of one file
+            j = i + 1
+            while j < r1 and names[j] == names[i]:
+                j += 1
+            st, en = np.ascontiguousarray(starts[i:j]), np.ascontiguousarray(ends[i:j])
+            lib.tfrg_gather_ranges(N.ptr(images[names[i]]), N.ptr(st, N.u64p), N.ptr(en, N.u64p), j - i,
+                                   N.ptr(buf[int(b_st[i - r0]):]))
+            i = j
+        res = dec.decode(buf, b_st, b_en)
+        if res.status.any():
+            res.raise_for(int(np.flatnonzero(res.status)[0]))
+        col.run(dec, r0, r1, k)
+    return col.finish()

@@ -218,6 +218,7 @@ class HipDecoder:
             "tfrg_set_schema",
         )
         self._pushed = kt.version
+        self._pushed_slots = len(kt.slot_key)
 
     # ------------------------------------------------------------------ decode
     def _flags(self, payload_only: bool, crc: bool, strict_crc: bool = False, materialize_bytes: bool = False) -> int:
@@ -341,6 +342,7 @@ class HipDecoder:
                 # (another decoder sharing the key table may have interned the keys first)
                 if not self._learn_misses(buf, info) and self._pushed == self.keys.version:
                     raise N.NativeError("schema misses reported but no new key learned")
+            self._last_n, self._last_host = n, (buf, st, payload_only)
             return self._fetch(buf, st, en, info, payload_only, materialize_bytes)
 
     def decode_device(self, d_bytes: int, nbytes: int, d_start: int, d_end: int, n: int, *,
@@ -355,6 +357,7 @@ class HipDecoder:
             ),
             "tfrg_decode_device",
         )
+        self._last_n, self._last_host = n, None
 
     def decode_device32(self, d_bytes: int, nbytes: int, d_start32: int | None, d_end32: int, first_start: int,
                         n: int, *, payload_only: bool = False, crc: bool = True, stream: int | None = None,
@@ -370,6 +373,15 @@ class HipDecoder:
             ),
             "tfrg_decode_device32",
         )
+        self._last_n, self._last_host = n, None
+
+    def dense(self, specs, *, strict: bool = False, out=None, stream: int | None = None):
+        """The last decode (``decode``, ``decode_device`` or ``decode_device32``) as dense torch tensors
+        on this decoder's device, one ``[n, width]`` per ``tfr_reader.dense.Dense`` spec, collated by
+        one kernel on the decode's stream (tfrg_result_dense); see ``tfr_reader.dense.decoder_dense``."""
+        from tfr_reader import dense as D  # noqa: PLC0415
+
+        return D.decoder_dense(self, specs, strict=strict, out=out, stream=stream)
 
     def _fetch(self, buf, st, en, info: N.TfrgInfo, payload_only: bool, materialize: bool = False) -> BatchResult:
         n, ns = info.n_records, info.n_slots
@@ -614,6 +626,14 @@ class BatchResult:
 
     def crc_ok(self) -> np.ndarray:
         return (self.verdict & 6) == 6
+
+    def dense(self, specs, strict: bool = False):
+        """Dense ``[n, width]`` numpy arrays of ``tfr_reader.dense.Dense`` specs from the fetched
+        columns (the host counterpart of ``HipDecoder.dense``): a ``DenseBatch`` with ``.lengths`` and
+        ``.stats``."""
+        from tfr_reader import dense as D  # noqa: PLC0415
+
+        return D.batch_dense(self, specs, strict)
 
 
 class _Layout:

@@ -485,6 +485,14 @@ class TFRecordDatasetReader:
         paths = [join_path(self.dataset_dir, f) for f in cols["tfrecord_filename"]]
         return load_ranges(paths, cols["tfrecord_start"], cols["tfrecord_end"], devices)
 
+    def load_tensors(self, selection, specs, device: int | None = None):
+        """The records of an index selection as dense torch tensors on ``device`` (default 0), rows in
+        selection order: one ``[n, width]`` per ``tfr_reader.dense.Dense`` spec, decoded and collated on
+        the device (``tfr_reader.dense.load_tensors``). Raises like ``load_records``."""
+        from tfr_reader import dense as D  # noqa: PLC0415
+
+        return D.load_tensors(self, selection, specs, device)
+
     def _load_or_cache_index(self, index_path: str):
         if self.index_cache_dir is None:
             if not os.path.exists(index_path):

@@ -374,6 +374,14 @@ class ShardDecoder:
             decs[k].decode_device32(d_bytes + lo, hi - lo, d_start32 + 4 * r0 if d_start32 else None, d_end32 + 4 * r0,
                                     int(firsts[k]), r1 - r0, stream=s, **kw)
 
+    def dense(self, plan: np.ndarray, specs, *, strict: bool = False, out=None, stream: int | None = None):
+        """The last ``decode_device`` / ``decode_device32`` as dense torch tensors over the whole plan
+        (``tfr_reader.dense.Dense`` specs): batch k's context writes rows [plan[k, 0], plan[k, 1]) of
+        each output on its own stream, and the current torch stream waits for all of them."""
+        from tfr_reader import dense as D  # noqa: PLC0415
+
+        return D.shard_dense(self, plan, specs, strict=strict, out=out, stream=stream)
+
     def device_bytes(self) -> tuple[int, int]:
         """(device memory of every batch context, decodes re-run so far: a value hint too small or
         an optimistic decode that left records, tfrg_ctx_device_bytes)."""
