@@ -158,7 +158,7 @@ int tfrg_template_count(tfrg_ctx* ctx);
  * reference's test writers leave them: such a record takes its template with verdict
  * TFRG_V_LEN_MATCH). A sample with both kinds keeps a shape once per class. 0: no templates. */
 int tfrg_template_frames(tfrg_ctx* ctx);
-/* The learned templates in their window form (u32 words, layout in csrc/tfrg_internal.h): up to cap
+/* The learned templates in their window form (u32 words, layout in csrc/tfrg_layout.h): up to cap
  * words into out, the window size W (words) into *window_words; returns the template count. For
  * checking a template against records on the host. */
 int tfrg_template_words(tfrg_ctx* ctx, uint32_t* out, uint64_t cap, uint32_t* window_words);

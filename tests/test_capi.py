@@ -55,11 +55,11 @@ def test_status_messages_match_the_python_mirror():
 
 
 def test_header_template_limits_match_the_kernel_constants():
-    """include/tfrg.h's numeric template limits are the ones csrc/tfrg_internal.h builds with."""
+    """include/tfrg.h's numeric template limits are the ones csrc/tfrg_layout.h and the learner build with."""
     root = Path(__file__).resolve().parents[1]
     hdr = (root / "include" / "tfrg.h").read_text()
-    internal = (root / "tfrecords-reader_amd" / "csrc" / "tfrg_internal.h").read_text()
-    capi = (root / "tfrecords-reader_amd" / "csrc" / "tfrg_capi.cpp").read_text()
+    internal = (root / "tfrecords-reader_amd" / "csrc" / "tfrg_layout.h").read_text()
+    capi = (root / "tfrecords-reader_amd" / "csrc" / "tfrg_learn.cpp").read_text()
 
     def macro(name):
         return int(re.search(rf"#define {name} (\d+)", hdr).group(1))
@@ -71,6 +71,8 @@ def test_header_template_limits_match_the_kernel_constants():
     assert macro("TFRG_TPL_MAX_PAYLOAD") == const("kTplMaxL")
     assert macro("TFRG_TPL_MAX_ENTRIES") == const("kTplMaxEntries")
     assert macro("TFRG_TPL_MAX_SLOTS") == const("kLeanMaxSlots")
-    lim = re.search(r"const uint32_t lim = n < (\d+)u \? n : (\d+)u;", capi)
-    assert lim and int(lim.group(1)) == int(lim.group(2)) == macro("TFRG_TPL_SAMPLE")
+    # both learners (shapes, single slots) bound their sample by the one constant
+    assert len(re.findall(r"const uint32_t lim = n < kTplSample \? n : kTplSample;", capi)) == 2
+    assert not re.search(r"lim = n < \d", capi)
+    assert const("kTplSample") == macro("TFRG_TPL_SAMPLE")
     assert "Up to 4" not in hdr and "(0..4)" not in hdr

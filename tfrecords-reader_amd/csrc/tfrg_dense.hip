@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tfrg_dense.h"
+#include "tfrg_dev.h"
 #include "tfrg_internal.h"
 
 namespace tfrg {
@@ -27,12 +28,6 @@ namespace {
 
 typedef uint32_t dn_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint64_t dn_u64x2 __attribute__((ext_vector_type(2)));
-
-template <bool NT, class T>
-__device__ __forceinline__ void st_out(T* p, T v) {
-  if (NT) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
 
 // per-lane counters of the rows whose first element the lane wrote
 struct Tally {
@@ -252,14 +247,14 @@ __device__ __forceinline__ void dense_spec(const Sp& x, Tally& t, uint32_t wg) {
             o.y = v[1];
             o.z = v[2];
             o.w = v[3];
-            st_out<NT>(reinterpret_cast<dn_u32x4*>(p), o);
+            st_nt<NT>(reinterpret_cast<dn_u32x4*>(p), o);
           } else if constexpr (DT == kDenseI64) {
             uint64_t v[2];
             values_from<DT, 2>(x, t, r, j >> 3, v);
             dn_u64x2 o;
             o.x = v[0];
             o.y = v[1];
-            st_out<NT>(reinterpret_cast<dn_u64x2*>(p), o);
+            st_nt<NT>(reinterpret_cast<dn_u64x2*>(p), o);
           } else {
             uint32_t v[4];
             values_from<DT, 4>(x, t, r, j >> 2, v);
@@ -268,7 +263,7 @@ __device__ __forceinline__ void dense_spec(const Sp& x, Tally& t, uint32_t wg) {
             o.y = v[1];
             o.z = v[2];
             o.w = v[3];
-            st_out<NT>(reinterpret_cast<dn_u32x4*>(p), o);
+            st_nt<NT>(reinterpret_cast<dn_u32x4*>(p), o);
           }
         }
       }
@@ -298,7 +293,7 @@ __device__ __forceinline__ void dense_spec(const Sp& x, Tally& t, uint32_t wg) {
         BRow b = brow_of(x, r);
         w = u8_dword(x, t, r, j, b, pos + 4u < total);
       }
-      st_out<NT>(reinterpret_cast<uint32_t*>(out + pos), w);
+      st_nt<NT>(reinterpret_cast<uint32_t*>(out + pos), w);
     }
     done += dwords << 2;
     for (uint64_t i = (uint64_t)wg * 256u + tid; done + i < total; i += (uint64_t)nblk * 256u) {
@@ -316,7 +311,7 @@ __device__ __forceinline__ void dense_spec(const Sp& x, Tally& t, uint32_t wg) {
       const uint64_t r64 = i / W;
       T v;
       values_from<DT, 1>(x, t, (uint32_t)r64, (uint32_t)(i - r64 * W), &v);
-      st_out<NT>(reinterpret_cast<T*>(out) + i, v);
+      st_nt<NT>(reinterpret_cast<T*>(out) + i, v);
     }
   }
 }

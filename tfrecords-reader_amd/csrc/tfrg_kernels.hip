@@ -1,21 +1,8 @@
-// tfrg_kernels.hip — gfx950 kernels for the TFRecord -> tf.train.Example -> Feature path.
-//
-// Pipeline for one batch of framed records resident in HBM (launch_decode):
-//   1. k_lane_count  : one LANE per record. Records <= lane_max: the wave's contiguous span staged
-//                      in LDS, framing check, masked CRC-32C of length and payload (slice-by-4 LDS
-//                      tables), single-pass canonical walk of Example -> Features -> map entries ->
-//                      Feature -> list (decoder.pyx:53-300 on canonical input). Records above
-//                      lane_max: the same walk straight from HBM (their payload CRC is step 3).
-//                      Per-slot counts summed per 256-record tile. Everything else -> slow list.
-//   2. k_slow_count  : the exact reference walk (level-by-level error precedence, dict semantics,
-//                      schema misses) for the slow list, one lane per record.
-//   3. k_big_crc     : payload CRC of records above lane_max, one workgroup per record, the four
-//                      waves recombined with GF(2) shift operators (crc32c.h).
-//   4. k_spine       : exclusive scan of the tile sums per (slot, chunk) with a decoupled look-back
-//                      across chunks; per-kind column bases (last workgroup).
-//   5. k_down_gather : row splits (tile prefix + in-tile scan) and inline single values.
-//   6. k_list_gather / k_stage_gather / k_wave_gather : out-of-line lists of lane records and of
-//                      records above lane_max.
+// tfrg_kernels.hip — the gfx950 kernels of the record-walking decode stages after k_tpl_lane, with
+// their launchers: k_lane_count and k_body_count (one lane per record: framing, CRC-32C verdicts, the
+// canonical walk), k_tail_count (exact walk of the slow list, streaming payload CRC of large records,
+// large-record walk), k_tail_gather (out-of-line lists). The row-split scan between them is
+// tfrg_scan.hip. launch_decode (tfrg_decode.cpp) is their launch policy and describes the pipeline.
 //
 // The canonical walker and the exact walker share the count/gather sinks, so both paths produce
 // identical columns (tests/test_gpu_parity.py forces each path on the same inputs).
@@ -23,6 +10,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "tfrg_internal.h"
+#include "tfrg_dev.h"
 #include "crc32c.h"
 #include "tfrg_walk.h"
 #include "../../include/tfrg_status.h"
@@ -123,18 +111,6 @@ typedef __attribute__((address_space(3))) uint16_t lds_u16;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 // constant address space: loads at wave-uniform indices compile to scalar loads (s_load, SGPRs)
 typedef __attribute__((address_space(4))) const uint32_t cu32;
-
-// single value stored in the loc word by the count pass
-__device__ __forceinline__ void put_inline(const DevOut& o, uint32_t kind, uint2 lc, uint64_t dst) {
-  if (kind == TFRG_KIND_INT64) {
-    if (dst < o.cap_i64) o.i64[dst] = (int64_t)(((uint64_t)lc.y << 32) | lc.x);
-  } else if (kind == TFRG_KIND_FLOAT) {
-    if (dst < o.cap_f32) o.f32[dst] = lc.x;
-  } else if (dst < o.cap_b) {
-    o.b_off[dst] = lc.x;
-    o.b_len[dst] = lc.y;
-  }
-}
 
 // Speculative placement target of one slot (DevSchema::spec), staged in LDS by the lane kernel's
 // prologue: the value column addresses at n * rank and the records r < lim that fit its capacity.
@@ -390,32 +366,6 @@ struct MaskSink {
 // ------------------------------------------------------------------------------------------------
 // LDS table view with R-fold bank replication: entry (j, v) copy c at dword ((j*256+v)*R + c).
 // Lane l reads copy l % R, so up to R lanes of a 32-lane group never collide on a bank.
-// a ^ b ^ c in one VALU (gfx950 v_bitop3_b32, truth table 0x96; the compiler does not fuse XOR chains)
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
-// ((x >> 8K) & 0xff) * 4 in one VALU: a shift with an SDWA byte select of its source
-template <int K>
-__device__ __forceinline__ uint32_t byte_x4(uint32_t x) {
-  static_assert(K >= 0 && K < 4, "byte index");
-  uint32_t r;
-  const uint32_t two = 2u;
-  if constexpr (K == 0)
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
-        : "=v"(r) : "v"(two), "v"(x));
-  else if constexpr (K == 1)
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1"
-        : "=v"(r) : "v"(two), "v"(x));
-  else if constexpr (K == 2)
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2"
-        : "=v"(r) : "v"(two), "v"(x));
-  else
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3"
-        : "=v"(r) : "v"(two), "v"(x));
-  return r;
-}
-
 template <int R>
 struct LdsTab {
   const uint32_t* t;
@@ -522,7 +472,6 @@ __device__ __forceinline__ RecView rec_view(const DevBatch& B, uint32_t r) {
 // ------------------------------------------------------------------------------------------------
 // Kernels
 // ------------------------------------------------------------------------------------------------
-constexpr int kLaneBlock = 256;
 constexpr int kLaneCountBlock = 256;  // k_lane_count workgroup (its LDS tables are per workgroup)
 constexpr int kWaveBlock = 256;
 constexpr int kWavesPerBlock = kWaveBlock / 64;
@@ -638,18 +587,7 @@ __device__ __forceinline__ uint32_t lds_u32u(const uint8_t* l, uint32_t off) {
   return __builtin_amdgcn_alignbyte(w[a + 1], w[a], off & 3u);
 }
 
-// CRC-32C of stage bytes [a, b): byte steps to 4-alignment, slice-by-4 words, byte tail
-template <int R>
-__device__ uint32_t crc_lds(const uint8_t* l, uint32_t a, uint32_t b, const LdsTab<R>& T) {
-  uint32_t c = 0xffffffffu;
-  while (a < b && (a & 3u)) c = T.step1(c, l[a++]);
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(l);
-  for (; a + 4 <= b; a += 4) c = T.step4(c ^ w[a >> 2]);
-  while (a < b) c = T.step1(c, l[a++]);
-  return ~c;
-}
-
-// as crc_lds, 8 bytes per dependent step (T holds the slice-by-8 set), with no byte loops: the
+// CRC-32C of stage bytes [a, b), 8 bytes per dependent step (T holds the slice-by-8 set), with no byte loops: the
 // k = a & 3 bytes before `a` in its dword are read as zeros and the start state is ~0 (x) x^(-8k)
 // (prepending zero bytes to a message multiplies the state by x^8 each, crc32c.h), and the last
 // m = b & 3 bytes take one partial slicing step T[m-1][x0] ^ ... ^ T[0][x(m-1)] ^ (c >> 8m).
@@ -790,14 +728,6 @@ struct FastSrcG {
     return __builtin_amdgcn_alignbyte(w1, w0, (uint32_t)(a & 3u));
   }
 };
-
-// 7-bit groups of the bytes of w selected by byte mask m, compacted (a varint of <= 4 bytes)
-__device__ __forceinline__ uint32_t vgroups(uint32_t w, uint32_t m) {
-  w &= m;
-  return (w & 0x7fu) | ((w >> 1) & 0x3f80u) | ((w >> 2) & 0x1fc000u) | ((w >> 3) & 0xfe00000u);
-}
-// byte mask of the first nb (1..4) bytes: shifts only (a multiply by 7 would be quarter rate)
-__device__ __forceinline__ uint32_t bytes_mask(uint32_t nb) { return nb >= 4u ? 0xffffffffu : (1u << (nb << 3)) - 1u; }
 
 // varint of <= 4 bytes (values < 2^28: identical in compat and spec mode); false = bail
 __device__ __forceinline__ bool fv32(const FastSrc& s, uint32_t& pos, uint32_t& v) {
@@ -960,28 +890,6 @@ __device__ __forceinline__ bool count_packed(const FastSrcG<WIN>& s, uint32_t o,
   return true;
 }
 
-__device__ __forceinline__ bool fast_list_count(const FastSrc& s, uint32_t kind, uint32_t lo, uint32_t ll,
-                                                uint32_t& cnt) {
-  uint32_t q = lo, c = 0;
-  const uint32_t le = lo + ll;
-  while (q < le) {
-    uint32_t fn, co, cl;
-    if (!ffield(s, q, le, fn, co, cl) || fn != 1u) return false;
-    if (kind == TFRG_KIND_BYTES) {
-      ++c;
-    } else if (kind == TFRG_KIND_FLOAT) {
-      if (cl & 3u) return false;
-      c += cl >> 2;
-    } else {
-      uint32_t k;
-      if (!count_packed(s, co, co + cl, k)) return false;
-      c += k;
-    }
-  }
-  cnt = c;
-  return true;
-}
-
 // LDS copy of the key table for the fast path: hash table + packed key records
 struct LdsKeys {
   const uint32_t* ht;    // [mask+1] key id + 1
@@ -1060,31 +968,6 @@ __device__ __forceinline__ bool fast_value(const FastSrc& s, uint32_t& pos, uint
     val = (int64_t)((uint64_t)x | ((uint64_t)g4 << 28) | ((uint64_t)g5 << 35) | ((uint64_t)g6 << 42) |
                     ((uint64_t)g7 << 49) | ((uint64_t)g8 << 56) | ((uint64_t)g9 << 63));
   }
-  return true;
-}
-
-// A list holding exactly one value: the value itself, packed into the 8-byte loc word (int64 bits,
-// float bits in .x, or the bytes element's absolute (offset, length)). The gather then writes it
-// without touching the record again. false = keep the list location.
-template <bool COMPAT>
-__device__ __forceinline__ bool fast_single(const FastSrc& s, uint32_t kind, uint32_t lo, uint32_t ll, uint2& val) {
-  uint32_t q = lo, fn, co, cl;
-  if (!ffield(s, q, lo + ll, fn, co, cl) || fn != 1u || q != lo + ll) return false;
-  if (kind == TFRG_KIND_BYTES) {
-    val = make_uint2((uint32_t)(s.base + co), cl);
-    return true;
-  }
-  if (kind == TFRG_KIND_FLOAT) {
-    if (cl != 4u) return false;
-    val = make_uint2(lds_u32u(s.l, s.p + co), 0u);
-    return true;
-  }
-  // int64: one varint of <= 4 bytes filling the chunk (values < 2^28, same in both varint modes)
-  if (cl == 0u || cl > 4u) return false;
-  const uint32_t w = s.w4(co);
-  const uint32_t term = ~w & 0x80808080u;
-  if (!term || (__builtin_ctz(term) >> 3) + 1u != cl) return false;
-  val = make_uint2(vgroups(w, bytes_mask(cl)), 0u);
   return true;
 }
 
@@ -1276,21 +1159,6 @@ __device__ __forceinline__ void frame_verdicts(const DevBatch& B, RecView& v, co
   }
 }
 
-// Inclusive prefix sum over the wave (every lane active) in seven DPP adds, no LDS: rows of 16 by
-// row_shr 1, 2, 3 of the value, then 4 and 8 of the partial sums (bank masks: only the lanes that
-// still miss a part), then the row totals by row_bcast 15 / 31 (gfx9 DPP; lanes a mask leaves out
-// read `old` = 0). Replaces six ds_bpermute round trips of __shfl_up.
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, uint32_t) {
-  uint32_t s = v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);  // row_shr:1
-  s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);             // row_shr:2
-  s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x113, 0xf, 0xf, true);             // row_shr:3
-  s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x114, 0xf, 0xe, true);             // row_shr:4
-  s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x118, 0xf, 0xc, true);             // row_shr:8
-  s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x142, 0xa, 0xf, false);            // row_bcast:15
-  s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x143, 0xc, 0xf, false);            // row_bcast:31
-  return s;
-}
-
 // wave total (every lane active), wave-uniform: the scan's last lane
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) {
   return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(x, 0u), 63);
@@ -1342,10 +1210,6 @@ __device__ __forceinline__ uint32_t vgpr_launder(uint32_t x) {
   uint32_t y;
   asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "s"(x));
   return y;
-}
-__device__ __forceinline__ uint32_t rfl32(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ uint64_t rfl64(uint64_t x) {
-  return ((uint64_t)rfl32((uint32_t)(x >> 32)) << 32) | rfl32((uint32_t)x);
 }
 
 // Lane-per-record kernel, the general path. Each wave copies the contiguous span of its 64 records
@@ -1616,6 +1480,29 @@ __global__ __launch_bounds__(kLaneCountBlock, MODE == 0 ? 6 : 4) void k_lane_cou
   }
 }
 
+// Dynamic LDS bytes of k_lane_count in `mode`, beside the kernel because it must agree with the
+// carve-up at the kernel's top, in that order: the per-lane dict (cnt, ord; MODE 0), a stage per wave,
+// the key table and key records (schemas staged in LDS), then MODE 1's tile sums or MODE 0's spec
+// words and their targets. (The slicing tables are static LDS on top of this.)
+constexpr int kLaneRep = 1;  // CRC table bank replication in the lane kernel (slice-by-8: 8 KiB per copy)
+constexpr size_t kLaneLdsBudget = 64 * 1024;  // LDS of a workgroup: the per-lane dicts must fit it
+static inline size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
+static size_t lane_count_lds(const DevSchema& sc, int mode) {
+  const size_t S = sc.n_slots;
+  const bool fast_ok = schema_in_lds(sc);
+  const size_t dict = mode == 0 ? S * kLaneCountBlock * 4 + r16(S * kLaneCountBlock * 2) : 0;  // (cnt u32, ord u16)
+  const size_t stage = (size_t)kStageStride * (kLaneCountBlock / 64);
+  const size_t keys = fast_ok ? (((size_t)sc.ht_mask + 4) / 4 * 4 + (size_t)sc.n_keys * kKrWords) * 4 : 0;
+  const size_t tsl = mode == 1 ? (kLaneCountBlock / 64) * 64 * 4 : 0;
+  const size_t spec = mode == 0 && fast_ok && sc.spec ? ((S + 7) & ~(size_t)7) * 4 + S * kSpecTgtWords * 4 : 0;
+  return dict + stage + keys + tsl + spec;
+}
+
+int lane_count_mode(const DevSchema& sc) {
+  const size_t tab_lds = 256ull * kLaneSlice * kLaneRep * 4;  // (the static tables)
+  return tab_lds + lane_count_lds(sc, 0) <= kLaneLdsBudget ? 0 : sc.n_slots <= 64 ? 1 : 2;
+}
+
 // The columns a record accepted by the lane kernel wrote, withdrawn before the exact walker redoes it:
 // order / count of every slot cleared, the counts taken back from the tile sums, and every present
 // slot counted irregular (a speculatively placed value of the record is then re-placed by the scan).
@@ -1730,33 +1617,8 @@ __device__ __forceinline__ void role_slow_count(const DevBatch& B, const DevSche
 }
 
 // ------------------------------------------------------------------------------------------------
-// Records above lane_max: payload CRC (k_big_crc) and the helpers of their wavefront gathers.
+// Records above lane_max: the streaming payload CRC and the helpers of their wavefront gathers.
 // ------------------------------------------------------------------------------------------------
-
-// Scalar read of a canonical length-delimited field-1 header at `q`: tag 0x0a + length varint of
-// <= 3 bytes; sets the body offset/length (body inside the payload) or returns false (bail).
-__device__ __forceinline__ bool hdr_0a(const FastSrc& s, uint32_t q, uint32_t& bo, uint32_t& bl) {
-  if (q + 2 > s.L) return false;
-  const uint32_t w = __builtin_amdgcn_readfirstlane(s.w4(q));
-  if ((w & 0xffu) != 0x0au) return false;
-  const uint32_t b1 = (w >> 8) & 0xffu, b2 = (w >> 16) & 0xffu, b3 = w >> 24;
-  uint32_t h, len;
-  if (b1 < 0x80u) {
-    h = 2;
-    len = b1;
-  } else if (b2 < 0x80u) {
-    h = 3;
-    len = (b1 & 0x7fu) | (b2 << 7);
-  } else if (b3 < 0x80u) {
-    h = 4;
-    len = (b1 & 0x7fu) | ((b2 & 0x7fu) << 7) | (b3 << 14);
-  } else {
-    return false;
-  }
-  bo = q + h;
-  bl = len;
-  return bo <= s.L && len <= s.L - bo;
-}
 
 // Streaming payload CRC of the large records (k_tail_count role 2). The lane kernel lists every
 // accepted record above lane_max (crc_list_append) with its 1 KiB rounds counted into ONE flat
@@ -2354,7 +2216,7 @@ __device__ __forceinline__ void role_crc_stream(const DevBatch& B, const DevOut&
 constexpr uint32_t kTailBlock = 512;
 constexpr uint32_t kTailFinishWord = 19456 + kNumCst;  // two LDS words of the finishing workgroup
 
-// The end of an optimistic decode without record shapes (launch_all, `finish`: every slot placed
+// The end of an optimistic decode without record shapes (launch_decode, `finish`: every slot placed
 // speculatively, records above lane_max possible), by the last workgroup of k_tail_count. When the
 // lane kernel placed every record's every slot (no irregular record, irr[k] = 0), sent none to the
 // exact walker, missed no key and listed no record for the wave gathers, the passes after this one
@@ -2380,24 +2242,7 @@ __device__ __forceinline__ void tail_quiet_finish(const DevOut& o, const uint8_t
     if (threadIdx.x == 0) o.info[kInfoResid] = 1u;
     return;
   }
-  for (uint32_t k = threadIdx.x; k < n_slots; k += kTailBlock) {
-    o.totals[k] = n;
-    o.rs[(size_t)k * (n + 1u) + n] = n;
-  }
-  if (threadIdx.x == 0) {
-    uint64_t acc[4] = {0, 0, 0, 0};
-    for (uint32_t k = 0; k < n_slots; ++k) {
-      const uint32_t kd = slot_kind[k] & 3u;
-      o.slot_base[k] = acc[kd];
-      acc[kd] += n;
-    }
-    for (int k = 0; k < 4; ++k) o.kind_totals[k] = acc[k];
-    if (acc[TFRG_KIND_INT64] > o.cap_i64 || acc[TFRG_KIND_FLOAT] > o.cap_f32 || acc[TFRG_KIND_BYTES] > o.cap_b)
-      o.info[kInfoOverflow] = 1u;
-    const uint64_t pm = n_slots >= 64u ? ~0ull : (1ull << n_slots) - 1ull;
-    o.info[kInfoPlacedLo] = (uint32_t)pm;
-    o.info[kInfoPlacedHi] = (uint32_t)(pm >> 32);
-  }
+  all_placed_finish(o, slot_kind, n_slots, n, kTailBlock);
 }
 
 // Optimistic decodes without record shapes (k_tail_count's first `walk_blocks` workgroups): the
@@ -2416,7 +2261,7 @@ __device__ __forceinline__ void role_big_walk(const DevBatch& B, const DevSchema
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   constexpr uint32_t BLK = kTailBlock, kW = BLK / 64;
   const uint32_t S = sc.n_slots;
-  // layout (launch_all: walk_lds): slicing tables, per-lane dict (counts, ranks), keys, spec targets
+  // layout (big_walk_lds below): slicing tables, per-lane dict (counts, ranks), keys, spec targets
   uint32_t* tab = lds;
   uint32_t* cnt = tab + 256u * kLaneSlice;
   uint16_t* ord = reinterpret_cast<uint16_t*>(cnt + S * BLK);
@@ -2489,6 +2334,16 @@ __device__ __forceinline__ void role_big_walk(const DevBatch& B, const DevSchema
   if (miss && lane == 0) atomicAdd(&o.info[kInfoWalkMiss], miss);
 }
 
+// LDS bytes of role_big_walk, beside its carve-up above and in its order: slicing tables, per-lane
+// dict (counts, ranks), key table and key records, spec words and their targets (it runs only with
+// the schema staged in LDS and every slot placed speculatively).
+static size_t big_walk_lds(const DevSchema& sc) {
+  const size_t S = sc.n_slots;
+  return 256ull * kLaneSlice * 4 + S * kTailBlock * 4 + r16(S * kTailBlock * 2) +
+         (((size_t)sc.ht_mask + 4) / 4 * 4 + (size_t)sc.n_keys * kKrWords) * 4 + ((S + 7) & ~(size_t)7) * 4 +
+         S * kSpecTgtWords * 4;
+}
+
 // finish: (optimistic decode without shapes) the last workgroup ends the decode, tail_quiet_finish;
 // walk_blocks: its first workgroups walk the records above lane_max (role_big_walk), the others
 // stream the CRC
@@ -2511,6 +2366,22 @@ __global__ __launch_bounds__(kTailBlock, 2) void k_tail_count(DevBatch B, DevSch
     __syncthreads();
     if (sh[0]) tail_quiet_finish(o, sc.slot_kind, sc.n_slots, B.n, sh[1]);
   }
+}
+
+// Dynamic LDS bytes of a k_tail_count launch and its GORD argument, beside the kernel because they
+// must agree with the carve-ups of its roles: role 1's slicing tables (2048 words) and per-lane dicts
+// for kTailBlock threads (cnt u32 + ord u16), or its global-dict form (GORD) when those do not fit;
+// role 2's tables and constants, then the finishing words (kTailFinishWord).
+static size_t tail_count_lds(const DevSchema& sc, bool& gord) {
+  const size_t S = sc.n_slots;
+  const size_t slow_tail = 2048ull * 4 + S * kTailBlock * 4 + r16(S * kTailBlock * 2);
+  gord = slow_tail > kLaneLdsBudget;
+  return std::max<size_t>(gord ? 2048ull * 4 : slow_tail, (kTailFinishWord + 4) * 4);
+}
+
+bool tail_walk_fits(const DevSchema& sc) {
+  bool gord;  // (not needed here)
+  return big_walk_lds(sc) <= tail_count_lds(sc, gord);
 }
 
 // Record queue of a staged wavefront kernel, three stages deep: bytes of the next record (in
@@ -2561,221 +2432,6 @@ __device__ __forceinline__ void pref_store(const Pref& p, uint8_t* dst, uint64_t
 }
 #undef TFRG_PREF_LOAD
 #undef TFRG_PREF_STORE
-
-// ------------------------------------------------------------------------------------------------
-// Row-split scan, second level: the tile sums of every slot in chunks of 4096 tiles (1 M records),
-// one 256-thread workgroup per (slot, chunk), 16 tiles per thread, with a decoupled look-back
-// across the chunks of a slot: each workgroup publishes its chunk total (flag 1) at once, sums
-// its predecessors' totals back to the first inclusive prefix (flag 2), publishes its own
-// inclusive prefix and writes full exclusive prefixes over the tile sums in place. Chunks are
-// taken in ticket order, so every workgroup waited on has started. The last workgroup to finish
-// derives the per-kind column bases from the slot totals.
-// ------------------------------------------------------------------------------------------------
-constexpr int kSpineBlock = 256;
-constexpr int kSpineItems = 16;
-static_assert(kSpineBlock * kSpineItems == (1 << kSpineChunkShift), "one chunk per spine workgroup");
-
-// exclusive prefix of chunk `chunk` from its predecessors' look-back words (lb[0..chunk)), by one
-// wave: lane l reads predecessor chunk - 1 - l (64 words per round trip, not one), the nearest
-// inclusive prefix (flag 2) ends the sum; a predecessor in range that has not published its total
-// yet (flag 0; it has started: ticket order) makes the wave read the window again
-__device__ __forceinline__ uint32_t spine_look_back(const uint64_t* lb, uint32_t chunk, uint32_t lane) {
-  uint32_t excl = 0;
-  for (int64_t base = (int64_t)chunk - 1; base >= 0;) {  // (wave-uniform)
-    const int64_t j = base - (int64_t)lane;
-    const uint64_t w = j >= 0 ? __hip_atomic_load(&lb[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                              : (2ull << 32);  // (before the first chunk: an inclusive prefix of 0)
-    const uint32_t flag = (uint32_t)(w >> 32);
-    const uint64_t inc = __ballot(flag == 2u), unset = __ballot(flag == 0u);
-    const uint32_t stop = inc ? (uint32_t)__builtin_ctzll(inc) : 64u;  // lanes [0, stop] are summed
-    const uint64_t range = stop >= 63u ? ~0ull : (2ull << stop) - 1ull;
-    if (unset & range) {
-      __builtin_amdgcn_s_sleep(1);
-      continue;
-    }
-    uint32_t v = lane <= stop ? (uint32_t)w : 0u;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-    excl += v;
-    if (stop < 64u) break;
-    base -= 64;
-  }
-  return excl;
-}
-
-// DevSchema::spec: the speculative placement of slot k is not final -- some record of it or of an
-// earlier slot of its kind (all speculative: they form a prefix) was irregular. Otherwise every such
-// slot holds n values at rows 0..n-1, so the column base of slot k is n * rank, as placed.
-__device__ __forceinline__ bool spec_failed(const uint32_t* spec, const DevOut& o, uint32_t k) {
-  const uint32_t sw = spec ? spec[k] : 0u;
-  if (!sw) return false;
-  for (uint32_t j = 0; j <= k; ++j) {
-    const uint32_t sj = spec[j];
-    if (sj && ((sj ^ sw) & 3u) == 0u && o.irr[j]) return true;
-  }
-  return false;
-}
-__device__ __forceinline__ bool spec_placed(const uint32_t* spec, const DevOut& o, uint32_t k) {
-  return spec && spec[k] && !spec_failed(spec, o, k);
-}
-
-// grid n_chunks * n_slots (1-D). With DevSchema::spec, a workgroup of a slot whose speculative
-// placement failed first copies the placed single values of its chunk's records back into their loc
-// words (value columns -> loc: no overlap with k_down_gather's writes, which follow this kernel).
-__global__ __launch_bounds__(kSpineBlock) void k_spine(DevOut o, const uint8_t* __restrict__ slot_kind, uint32_t n_slots,
-                                                       uint32_t n_tiles, const uint32_t* __restrict__ spec, uint32_t n) {
-  __shared__ uint32_t s_w[kSpineBlock / 64];
-  __shared__ uint32_t s_ticket, s_excl, s_last;
-  __shared__ uint32_t s_w2[kSpineBlock];  // last workgroup: slot totals of one pass
-  __shared__ uint8_t s_kind[kSpineBlock];
-  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_ticket = atomicAdd(&o.info[kInfoSpineTicket], 1u);
-  // Every slot's placement final (a templated batch): no scan, no look-back and no last-workgroup
-  // pass, since the placement fixes every total (n) and column base. Read beside the ticket: one
-  // round trip to the device-scope words instead of three.
-  const bool allp = spec && n_slots <= (uint32_t)kSpineBlock &&
-                    __syncthreads_and(threadIdx.x >= n_slots || spec_placed(spec, o, threadIdx.x));
-  __syncthreads();
-  const uint32_t slot = s_ticket / o.n_chunks, chunk = s_ticket % o.n_chunks;
-  if (allp) {  // (workgroup-uniform) this chunk's tile sums zeroed for the next decode
-    uint32_t* t = o.tsum + (size_t)slot * o.tile_stride;
-    const uint32_t i0 = (chunk << kSpineChunkShift) + threadIdx.x * kSpineItems;
-#pragma unroll
-    for (int j = 0; j < kSpineItems; j += 4)
-      if (i0 + j < n_tiles) *reinterpret_cast<uint4*>(t + i0 + j) = make_uint4(0, 0, 0, 0);
-    if (s_ticket == 0u && threadIdx.x == 0) {  // totals, column bases, kind totals (as the last pass)
-      uint64_t acc[4] = {0, 0, 0, 0};
-      for (uint32_t k = 0; k < n_slots; ++k) {
-        const uint32_t kd = slot_kind[k] & 3u;
-        o.totals[k] = n;
-        o.slot_base[k] = acc[kd];
-        acc[kd] += n;
-      }
-      for (int k = 0; k < 4; ++k) o.kind_totals[k] = acc[k];
-      if (acc[TFRG_KIND_INT64] > o.cap_i64 || acc[TFRG_KIND_FLOAT] > o.cap_f32 || acc[TFRG_KIND_BYTES] > o.cap_b)
-        o.info[kInfoOverflow] = 1u;
-    }
-    return;
-  }
-  if (spec_failed(spec, o, slot)) {  // (workgroup-uniform; rare: an irregular batch)
-    const uint32_t sw = spec[slot];
-    const uint64_t sb = (uint64_t)n * ((sw >> 2) - 1u);
-    const uint64_t r0 = (uint64_t)chunk << (kSpineChunkShift + kTileShift);
-    const uint64_t r1 = r0 + (1ull << (kSpineChunkShift + kTileShift)) < n ? r0 + (1ull << (kSpineChunkShift + kTileShift)) : n;
-    for (uint64_t r = r0 + threadIdx.x; r < r1; r += kSpineBlock) {
-      const size_t at = (size_t)slot * n + r;
-      if (o.lmask && !((o.lmask[r >> 6] >> (r & 63u)) & 1ull)) {
-        o.count[at] = 1u | kCountInline;  // a k_tpl_lane record (placed, its count word not written)
-      } else if (o.count[at] != (1u | kCountInline)) {
-        continue;
-      }
-      const uint64_t p = sb + r;
-      uint2 lv = make_uint2(0, 0);
-      if ((sw & 3u) == TFRG_KIND_INT64) {
-        if (p < o.cap_i64) {
-          const uint64_t v = (uint64_t)o.i64[p];
-          lv = make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-        }
-      } else if ((sw & 3u) == TFRG_KIND_FLOAT) {
-        if (p < o.cap_f32) lv.x = o.f32[p];
-      } else if (p < o.cap_b) {
-        lv = make_uint2(o.b_off[p], o.b_len[p]);
-      }
-      o.loc[at] = lv;
-    }
-  }
-  uint32_t* t = o.tsum + (size_t)slot * o.tile_stride;
-  uint64_t* lb = o.spine_lb + (size_t)slot * o.n_chunks;
-  const uint32_t i0 = (chunk << kSpineChunkShift) + threadIdx.x * kSpineItems;
-  if (spec_placed(spec, o, slot)) {  // (workgroup-uniform) n values at rows 0..n-1 (spec_failed): no scan
-    // (k_down_gather skips the slot): its tile sums zeroed for the next decode, its look-back words
-    // never written
-#pragma unroll
-    for (int j = 0; j < kSpineItems; j += 4)
-      if (i0 + j < n_tiles) *reinterpret_cast<uint4*>(t + i0 + j) = make_uint4(0, 0, 0, 0);
-    if (chunk == o.n_chunks - 1u && threadIdx.x == 0) o.totals[slot] = n;
-  } else {
-  uint32_t v[kSpineItems];
-#pragma unroll
-  for (int j = 0; j < kSpineItems; j += 4) {  // tile_stride is a multiple of 4: whole uint4s are in bounds
-    uint4 q = make_uint4(0, 0, 0, 0);
-    if (i0 + j < n_tiles) q = *reinterpret_cast<const uint4*>(t + i0 + j);
-    v[j] = q.x;
-    v[j + 1] = i0 + j + 1 < n_tiles ? q.y : 0u;
-    v[j + 2] = i0 + j + 2 < n_tiles ? q.z : 0u;
-    v[j + 3] = i0 + j + 3 < n_tiles ? q.w : 0u;
-  }
-  uint32_t sum = 0;
-#pragma unroll
-  for (int j = 0; j < kSpineItems; ++j) sum += v[j];
-  const uint32_t incl = wave_incl_scan_u32(sum, lane);
-  if (lane == 63) s_w[wid] = incl;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kSpineBlock / 64; ++w) {
-    const uint32_t x = s_w[w];
-    pre += (uint32_t)w < wid ? x : 0u;
-    tot += x;
-  }
-  if (threadIdx.x < 64u) {  // wave 0
-    if (threadIdx.x == 0)
-      __hip_atomic_store(&lb[chunk], ((uint64_t)(chunk ? 1u : 2u) << 32) | tot, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t excl = spine_look_back(lb, chunk, lane);
-    if (threadIdx.x == 0) {
-      if (chunk) __hip_atomic_store(&lb[chunk], (2ull << 32) | (excl + tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (chunk == o.n_chunks - 1u) o.totals[slot] = excl + tot;
-      s_excl = excl;
-    }
-  }
-  __syncthreads();
-  uint32_t run = s_excl + pre + incl - sum;
-#pragma unroll
-  for (int j = 0; j < kSpineItems; j += 4) {
-    uint32_t w[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      w[m] = run;
-      run += v[j + m];
-    }
-    if (i0 + j < n_tiles) *reinterpret_cast<uint4*>(t + i0 + j) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  }
-  if (threadIdx.x == 0) {
-    __threadfence();
-    s_last = atomicAdd(&o.info[kInfoSpineDone], 1u) == gridDim.x - 1u;
-  }
-  __syncthreads();
-  if (!s_last) return;  // workgroup-uniform
-  __threadfence();      // every slot total is visible
-  // per pass of 256 slots, thread 0 derives the per-kind column bases from LDS copies
-  uint64_t acc[4] = {0, 0, 0, 0};  // thread 0
-  for (uint32_t b = 0; b < n_slots; b += kSpineBlock) {
-    const uint32_t k = b + threadIdx.x;
-    if (k < n_slots) {
-      s_w2[threadIdx.x] = __hip_atomic_load(&o.totals[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_kind[threadIdx.x] = slot_kind[k] & 3u;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const uint32_t m = n_slots - b < (uint32_t)kSpineBlock ? n_slots - b : (uint32_t)kSpineBlock;
-      for (uint32_t j = 0; j < m; ++j) {
-        const uint32_t kd = s_kind[j];
-        o.slot_base[b + j] = acc[kd];
-        acc[kd] += s_w2[j];
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    for (int k = 0; k < 4; ++k) o.kind_totals[k] = acc[k];
-    // capacities bound the values of disjoint ranges; overlapping / repeated ranges can exceed
-    // them (stores past a capacity are dropped): the host reports TFRG_E_LIMIT
-    if (acc[TFRG_KIND_INT64] > o.cap_i64 || acc[TFRG_KIND_FLOAT] > o.cap_f32 || acc[TFRG_KIND_BYTES] > o.cap_b)
-      o.info[kInfoOverflow] = 1u;
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // Gather: decode the (validated) list message of every present slot into its column.
@@ -2893,137 +2549,6 @@ __device__ __forceinline__ void gather_record(const DevBatch& B, const DevSchema
   }
 }
 
-// Row-split scan, last level, fused with the lane-record gather. One workgroup per 256-record tile:
-// per slot, the tile prefix (k_spine) + the in-tile exclusive scan of the counts give the row splits;
-// single values kept inline by the count pass are written straight from the loc word, other lists of
-// records <= lane_max are decoded from the wave's LDS stage. Records above lane_max belong to the
-// wavefront gather kernels, which run next and read these row splits.
-// kDT tiles per workgroup: kDT x kDG (count, loc) loads in flight per thread (4 for large batches,
-// 1 when that would leave CUs idle)
-
-template <bool COMPAT, uint32_t kDT>
-__global__ __launch_bounds__(kLaneBlock) void k_down_gather(DevBatch B, DevSchema sc, DevOut o, uint32_t lane_max,
-                                                            uint32_t n_tiles) {
-  // slots per scan group (one barrier each): 2 beside 4 tiles per workgroup, 8 with one tile (small
-  // batches and wide schemas: fewer barriers between the loads, same registers)
-  constexpr uint32_t kDG = kDT == 1 ? 8u : 2u;
-  __shared__ uint32_t s_w[2][kDT * kDG][4];  // wave totals, double-buffered across slot groups
-  const uint32_t lane = threadIdx.x & 63u, wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t S = sc.n_slots;
-  if (blockIdx.x == 0)
-    for (uint32_t k = threadIdx.x; k < S; k += kLaneBlock) o.rs[(size_t)k * (B.n + 1) + B.n] = o.totals[k];
-  // slots whose speculative placement by the lane kernel is final (DevSchema::spec): nothing to do.
-  // Read once (the first 64 slots as a mask): the tile-sum stores below may alias irr for the
-  // compiler, which would otherwise re-load spec / irr with their latency in every group.
-  // (lane k: slot k, so the words of all of them are loaded at once)
-  const uint64_t pmask = sc.spec ? (uint64_t)__ballot(lane < S && spec_placed(sc.spec, o, lane)) : 0ull;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // (for k_tail_gather, which clears irr)
-    o.info[kInfoPlacedLo] = (uint32_t)pmask;
-    o.info[kInfoPlacedHi] = (uint32_t)(pmask >> 32);
-  }
-  auto placed = [&](uint32_t k) -> bool {
-    return k < 64u ? ((pmask >> k) & 1ull) != 0ull : k < S && spec_placed(sc.spec, o, k);
-  };
-  // every slot placed: nothing to do (k_spine zeroed their tile sums; their look-back words were
-  // never written)
-  if (S <= 64u && pmask == (~0ull >> (64u - S))) return;
-  uint32_t buf = 0;
-  // a resident grid strides over the groups of kDT tiles (a launch of one workgroup per group spent
-  // most of its time dispatching workgroups that only zero their tile sums when every slot is placed)
-  const uint32_t n_groups = (n_tiles + kDT - 1) / kDT;
-  for (uint32_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {  // (workgroup-uniform)
-    const uint32_t tile0 = grp * kDT;
-    uint32_t r[kDT];
-    bool valid[kDT];
-  #pragma unroll
-    for (uint32_t t = 0; t < kDT; ++t) {
-      r[t] = ((tile0 + t) << kTileShift) + threadIdx.x;
-      valid[t] = r[t] < B.n;
-    }
-    // row splits of every slot + inline single values. A non-zero count implies a decoded record
-    // with the slot present (failed records and absent slots have count 0).
-    uint32_t need = 0;  // bit t: record r[t] has an out-of-line list
-    for (uint32_t k0 = 0; k0 < S; k0 += kDG) {
-      bool sk[kDG];
-      bool all = true;
-  #pragma unroll
-      for (uint32_t g = 0; g < kDG; ++g) {
-        sk[g] = placed(k0 + g);
-        all &= sk[g] || k0 + g >= S;
-      }
-      if (all) continue;  // (workgroup-uniform; buf toggles only with a barrier)
-      uint32_t c[kDT][kDG], ex[kDT][kDG];
-      uint2 lc[kDT][kDG];
-  #pragma unroll
-      for (uint32_t t = 0; t < kDT; ++t) {  // every load of the group issued before the barrier
-  #pragma unroll
-        for (uint32_t g = 0; g < kDG; ++g) {
-          const uint32_t k = k0 + g < S ? k0 + g : k0;
-          const bool in = valid[t] && k0 + g < S && !sk[g];
-          c[t][g] = in ? o.count[(size_t)k * B.n + r[t]] : 0u;
-          lc[t][g] = in ? o.loc[(size_t)k * B.n + r[t]] : make_uint2(0, 0);
-        }
-      }
-  #pragma unroll
-      for (uint32_t t = 0; t < kDT; ++t) {
-  #pragma unroll
-        for (uint32_t g = 0; g < kDG; ++g) {
-          const uint32_t x = c[t][g] & ~kCountInline;
-          // 0/1 counts (single values): the inclusive scan is a masked popcount of the ballot
-          const uint32_t incl = __ballot(x > 1u) ? wave_incl_scan_u32(x, lane)
-                                                 : (uint32_t)__popcll(__ballot(x != 0u) & (~0ull >> (63u - lane)));
-          ex[t][g] = incl - x;
-          if (lane == 63) s_w[buf][t * kDG + g][wib] = incl;
-        }
-      }
-      __syncthreads();  // (the other buffer is rewritten only after the next group's barrier)
-  #pragma unroll
-      for (uint32_t g = 0; g < kDG; ++g) {
-        const uint32_t k = k0 + g;
-        if (k >= S) break;
-        if (sk[g]) continue;
-        const uint32_t kind = sc.slot_kind[k];
-        const uint64_t sbase = o.slot_base[k];
-  #pragma unroll
-        for (uint32_t t = 0; t < kDT; ++t) {
-          if (tile0 + t >= n_tiles) break;
-          uint32_t pre = o.tsum[(size_t)k * o.tile_stride + tile0 + t];
-          for (uint32_t w = 0; w < wib; ++w) pre += s_w[buf][t * kDG + g][w];
-          const uint32_t rsv = pre + ex[t][g];
-          if (valid[t]) o.rs[(size_t)k * (B.n + 1) + r[t]] = rsv;
-          if (c[t][g] & kCountInline) put_inline(o, kind, lc[t][g], sbase + rsv);
-          else if (c[t][g]) need |= 1u << t;
-        }
-      }
-      buf ^= 1u;
-    }
-    // records with an out-of-line list: k_list_gather (kept out of this kernel so its register
-    // budget stays that of the scan); larger records are skipped there (wavefront gathers)
-  #pragma unroll
-    for (uint32_t t = 0; t < kDT; ++t) {
-      const bool nd = (need >> t) & 1u;
-      const uint64_t nm = __ballot(nd);
-      if (nm) {
-        const int f = __builtin_ctzll(nm);
-        uint32_t b0 = 0;
-        if (lane == (uint32_t)f) b0 = atomicAdd(&o.info[kInfoNeed], (uint32_t)__popcll(nm));
-        b0 = __shfl(b0, f, 64);
-        if (nd) o.slow_list[b0 + (uint32_t)__popcll(nm & ((1ull << lane) - 1ull))] = r[t];
-      }
-    }
-    // Leave the scan words zeroed for the next decode (no per-call memset): this group's tile
-    // prefixes of every slot (+ the stride padding after the last tile), and the spine's look-back
-    // words (workgroup 0; k_spine has finished).
-    __syncthreads();
-    const uint32_t t_end = tile0 + kDT < n_tiles ? tile0 + kDT : (tile0 < n_tiles ? o.tile_stride : tile0);
-    const uint32_t span = t_end - tile0;
-    for (uint32_t i = threadIdx.x; i < S * span; i += kLaneBlock)
-      o.tsum[(size_t)(i / span) * o.tile_stride + tile0 + i % span] = 0u;
-  }
-  if (blockIdx.x == 0)
-    for (uint32_t i = threadIdx.x; i < 2u * S * o.n_chunks; i += kLaneBlock) reinterpret_cast<uint32_t*>(o.spine_lb)[i] = 0u;
-}
-
 // Out-of-line lists of lane records (k_down_gather's list; lane order within a wave, so the records
 // of a wave are usually one contiguous span): staged in LDS and decoded by their own lane.
 template <bool COMPAT>
@@ -3116,8 +2641,8 @@ __device__ __forceinline__ uint64_t readlane_u64(uint64_t x, int k) {
 // are copied by the whole wave (lane j moves value j: contiguous stores), canonical packed int64
 // lists are decoded by the whole wave (int64_balanced); bytes lists and anything non-canonical are
 // decoded by their own lane.
-// Per-lane form of hdr_0a: the list at [lo, lo+ll) is exactly one canonical chunk (tag 0x0a, length
-// varint of <= 3 bytes) whose body is [bo, bo+bl).
+// hdr_0a_v: the list at [lo, lo+ll) is exactly one canonical chunk (tag 0x0a, length varint of <= 3
+// bytes) whose body is [bo, bo+bl).
 __device__ __forceinline__ bool hdr_0a_v(const FastSrc& s, uint32_t lo, uint32_t ll, uint32_t& bo, uint32_t& bl) {
   const uint32_t w = lo + 2 <= s.L ? s.w4(lo) : 0u;
   const uint32_t b1 = (w >> 8) & 0xffu, b2 = (w >> 16) & 0xffu, b3 = w >> 24;
@@ -3593,326 +3118,78 @@ __global__ __launch_bounds__(kWaveBlock) void k_tail_gather(DevBatch B, DevSchem
   role_wave_gather<COMPAT>(B, sc, o, placed);
 }
 
-// Debug hook (tfrg_ctx: env TFRG_DEBUG_POISON_LOC at context creation): after the count passes,
-// the list locations of up to 4 records are overwritten with a location far outside any record, as
-// a stale or corrupt word would be; the gathers must then fail those records (TFRG_ST_INTERNAL).
-__global__ void k_poison_loc(DevOut o, uint32_t n, uint32_t n_slots, uint4 recs) {
-  const uint32_t rr[4] = {recs.x, recs.y, recs.z, recs.w};
-  for (uint32_t k = threadIdx.x; k < n_slots; k += blockDim.x)
-    for (int i = 0; i < 4; ++i)
-      if (rr[i] < n) o.loc[(size_t)k * n + rr[i]] = make_uint2(0xfffff000u, 0x00ffffffu);
+// ------------------------------------------------------------------------------------------------
+// launchers: each picks its kernel's template arguments (COMPAT from b.flags), takes the dynamic LDS
+// from the function beside the kernel's carve-up and, where the grid is one round of resident
+// workgroups, queries the occupancy. They only enqueue; the policy (which stages run, the grid caps)
+// is launch_decode, tfrg_decode.cpp.
+// ------------------------------------------------------------------------------------------------
+// workgroups of one resident round of `fn`: a second, partial round would idle most CUs at its tail
+template <class F>
+static int resident_blocks(F fn, int block, size_t lds, int num_cus) {
+  int per_cu = 0;
+  const void* f = reinterpret_cast<const void*>(fn);
+  const bool ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, block, lds) == hipSuccess && per_cu >= 1;
+  return (ok ? per_cu : 1) * num_cus;
 }
-
-// ------------------------------------------------------------------------------------------------
-// launcher
-// ------------------------------------------------------------------------------------------------
-constexpr int kLaneRep = 1;  // CRC table bank replication in the lane kernel (slice-by-8: 8 KiB per copy)
-
-constexpr size_t kLaneLdsBudget = 64 * 1024; // lane kernels (occupancy): likewise
-
-const char* const kStageNames[kNumStages] = {"k_tpl_lane",    "k_lane_count",  "k_body_count", "k_tail_count", "k_spine",
-                                             "k_down_gather", "k_tail_gather", "k_bytes"};
-
-static inline size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 template <bool COMPAT>
-static hipError_t launch_all(const DevBatch& b, const DevSchema& sc, const DevOut& o, LaunchCfg& cfg,
-                             const uint32_t* d_tab, const uint32_t* d_consts, hipStream_t st, hipEvent_t* ev) {
-  auto mark = [&](int i) {
-    if (ev) (void)hipEventRecord(ev[i], st);
-  };
-  const size_t S = sc.n_slots;
-  const uint32_t n_tiles = (b.n + kTileRecs - 1) / kTileRecs;
-  const size_t dict_lane = S * kLaneCountBlock * 4 + r16(S * kLaneCountBlock * 2);  // cnt u32 + ord u16 per lane
-  const size_t tab_lds = 256ull * kLaneSlice * kLaneRep * 4;
-  const size_t stage_lds = (size_t)kStageStride * (kLaneCountBlock / 64);
-  const bool fast_ok = sc.n_keys <= kLdsMaxKeys && sc.ht_mask + 1 <= kLdsMaxHt;
-  const size_t keys_lds = fast_ok ? (((size_t)sc.ht_mask + 4) / 4 * 4 + (size_t)sc.n_keys * kKrWords) * 4 : 0;
-  // (MODE 0 only) spec words + their targets
-  const size_t spec_lds = fast_ok && sc.spec ? ((S + 7) & ~(size_t)7) * 4 + S * kSpecTgtWords * 4 : 0;
-  const size_t lane_lds = tab_lds + dict_lane + stage_lds + keys_lds + spec_lds;
-  // speculative placement only with the per-lane LDS dict (MODE 0); the later kernels see the same
-  DevSchema scx = sc;
-  if (lane_lds > kLaneLdsBudget || !fast_ok) scx.spec = nullptr;
-  const uint32_t wave_stage = cfg.wave_stage < kWStage ? cfg.wave_stage : kWStage;
-  // record-shape templates first (k_tpl_lane, tfrg_tpl.hip): framed records (with CRC verdicts or,
-  // kFlagNoCrc, the mask match alone), a schema of <= kLeanMaxSlots slots; k_lane_count then takes
-  // only the records it left
-  const bool lean = cfg.lean && sc.n_tpl && fast_ok && S <= kLeanMaxSlots && o.lmask && o.rlist &&
-                    (sc.tpl_w == 16 || sc.tpl_w == 32 || sc.tpl_w == 64) &&
-                    !(b.flags & kFlagPayloadOnly) && b.nbytes < 0xffffff00ull;
-  const bool tpl_nocrc = (b.flags & kFlagNoCrc) != 0, tpl_strict = (b.flags & kFlagStrictCrc) != 0;
-  // every record of the learning sample took a template and none is above lane_max: the passes after
-  // k_tpl_lane (residual lane records, slow walks, large-record CRCs, gathers of placed slots) are
-  // usually empty, and a full grid of workgroups that exit at once costs ~4 us per launch; they
-  // run with small grids instead (any work they do find is still done: every one strides)
-  const bool quiet = lean && cfg.tpl_full && !cfg.body_count;
-  // every slot speculatively placed (DevSchema::spec, a target for each)
-  bool all_spec = scx.spec && cfg.spec_h && S <= 64;
-  for (size_t k = 0; all_spec && k < S; ++k) all_spec = cfg.spec_h[k] != 0u;
-  // Optimistic: quiet with every slot placed (C1-shaped batches). A batch all of whose records take a
-  // template is complete after k_tpl_lane; the passes after it would only launch. The last
-  // workgroup of k_tpl_lane does their bookkeeping (tpl_quiet_finish), or flags the batch for a full
-  // re-run by the host (tfrg_result_info) if a record took no template. Saves five dependent
-  // launches (~4 us each) per batch.
-  // (not in strict mode with unchecked-frame templates: their records are errors there, for the full passes)
-  cfg.ran_optimistic = cfg.optimistic && quiet && all_spec && S > 0 && !(tpl_strict && cfg.tpl_unchecked);
-  // Optimistic without record shapes (C2: records above lane_max, every slot one inline value in the
-  // learning sample, placed speculatively by k_lane_count MODE 0): k_lane_count, k_tail_count, and
-  // the last workgroup of k_tail_count ends the decode (tail_quiet_finish) or flags it for a full
-  // re-run. Not in strict mode (a CRC failure withdraws a record's columns).
-  const bool quiet_big = cfg.optimistic && !lean && all_spec && S > 0 && lane_lds <= kLaneLdsBudget && fast_ok &&
-                         cfg.body_count && !(b.flags & kFlagStrictCrc) && b.n > 0;
-  cfg.ran_optimistic |= quiet_big;
-  cfg.ran_quiet_big = quiet_big;
-  // k_tail_count's LDS (role 1's per-lane dicts for kTailBlock threads, else its global-dict form;
-  // role 2's tables and the finishing words)
-  const size_t slow_tail = 2048ull * 4 + S * kTailBlock * 4 + r16(S * kTailBlock * 2);
-  const bool tail_gord = slow_tail > kLaneLdsBudget;
-  const size_t tail_lds = std::max<size_t>(tail_gord ? 2048ull * 4 : slow_tail, (kTailFinishWord + 4) * 4);
-  // quiet_big: the records above lane_max walked beside the streaming CRC by k_tail_count's first
-  // workgroups (role_big_walk) when its per-lane dicts fit the launch's LDS
-  const size_t walk_lds = 256ull * kLaneSlice * 4 + S * kTailBlock * 4 + r16(S * kTailBlock * 2) + keys_lds + spec_lds;
-  const bool walk_beside = quiet_big && cfg.walk_beside && walk_lds <= tail_lds;
-  cfg.implicit = 0;
-  DevOut ox = o;
-  if (!lean) {
-    ox.lmask = nullptr;
-    ox.rlist = nullptr;
-  }
-  mark(kStageTplLane);
-  if (lean) {
-    LeanArgs a{};
-    a.n_tpl = sc.n_tpl;
-    a.img_words = sc.tpl_img_words;
-    a.tab_words = tpl_nocrc ? 0u : sc.tpl_tab_words;
-    a.nocrc = tpl_nocrc ? 1u : 0u;
-    a.strict = tpl_strict ? 1u : 0u;
-    a.uframes = cfg.tpl_unchecked ? 1u : 0u;
-    a.cu_lds = cfg.tpl_cu_lds;
-    a.stage_any = cfg.tpl_stage_any ? 1u : 0u;
-    a.gpw_force = cfg.tpl_gpw;
-    a.lane_max = cfg.lane_max;
-    a.tsum = cfg.ran_optimistic ? nullptr : o.tsum;  // (placed slots: no scan; a re-run clears tsum)
-    a.finish = cfg.ran_optimistic ? sc.slot_kind : nullptr;
-    // (optimistic: status / verdict and constant order words are implicit, tfrg_info.implicit_cols;
-    // TFRG_IMPLICIT_STATUS says every verdict is 7: CRCs on and every template spec-framed, else
-    // k_tpl_lane stores status and verdict per record)
-    cfg.implicit = cfg.ran_optimistic ? (!tpl_nocrc && !cfg.tpl_unchecked ? TFRG_IMPLICIT_STATUS : 0u) |
-                                            (cfg.ord_const ? TFRG_IMPLICIT_ORDER : 0u) |
-                                            (cfg.len_const ? TFRG_IMPLICIT_BYTES_LEN : 0u)
-                                      : 0u;
-    a.implicit = cfg.implicit;
-    a.n_slots = (uint32_t)S;
-    a.tile_stride = o.tile_stride;
-    const uint64_t n = b.n;
-    for (uint32_t k = 0; k < S; ++k) {
-      LeanTgt& t = a.tg[k];
-      t.ord = o.order + k * n;
-      t.cnt = o.count + k * n;
-      t.loc = o.loc + k * n;
-      t.rs = o.rs + k * (n + 1);
-      const uint32_t sw = scx.spec && cfg.spec_h ? cfg.spec_h[k] : 0u;
-      if (sw) {  // as spec_target: column rows n * (rank - 1) + r, r below the capacity
-        const uint32_t kind = sw & 3u;
-        const uint64_t base = n * ((sw >> 2) - 1u);
-        const uint64_t cap = kind == TFRG_KIND_INT64 ? o.cap_i64 : kind == TFRG_KIND_FLOAT ? o.cap_f32 : o.cap_b;
-        t.lim = cap > base ? (uint32_t)std::min<uint64_t>(cap - base, n) : 0u;
-        t.kind = kind;
-        if (kind == TFRG_KIND_INT64) t.v1 = o.i64 + base;
-        else if (kind == TFRG_KIND_FLOAT) t.v1 = o.f32 + base;
-        else t.v1 = o.b_off + base;
-        t.v2 = o.b_len + base;
-      }
-    }
-    const hipError_t e = launch_tpl_lane(b, ox, a, sc.tpl_img, sc.tpl_w, cfg.num_cus, st);
-    if (e != hipSuccess) return e;
-  }
-  if (cfg.ran_optimistic && !quiet_big) {  // (k_tpl_lane's last workgroup finished the decode)
-    for (int i = kStageLaneCount; i <= kStageMaterialize; ++i) mark(i);
-    return hipGetLastError();
-  }
-  mark(kStageLaneCount);
-  // one round of resident workgroups (a second, partial round would idle most CUs at the tail)
-  auto resident_grid = [&](const void* fn, size_t lds, bool cap = true) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kLaneCountBlock, lds) != hipSuccess || per_cu < 1)
-      per_cu = 1;
-    const int g = per_cu * cfg.num_cus;
-    int need = (int)(((int64_t)cfg.lane_grid * 256 + kLaneCountBlock - 1) / kLaneCountBlock);
-    // (after a template pass that took its whole sample the residual pass is usually empty; it
-    // strides over whatever groups it finds. Not for records above lane_max: k_tpl_lane leaves
-    // every one of them, and walking them is this pass's work)
-    if (quiet) need = std::min(need, 64);
-    return g < need || !cap ? g : need;
-  };
-  if (lane_lds <= kLaneLdsBudget) {
-    const void* fn = reinterpret_cast<const void*>(&k_lane_count<kLaneRep, COMPAT, 0>);
-    hipLaunchKernelGGL((k_lane_count<kLaneRep, COMPAT, 0>), dim3(resident_grid(fn, lane_lds - tab_lds)),
-                       dim3(kLaneCountBlock), lane_lds - tab_lds, st, b, scx, ox, d_tab, cfg.lane_max, wave_stage,
-                       walk_beside ? 1u : 0u);
-  } else if (S <= 64) {
-    const size_t lds = stage_lds + keys_lds + (kLaneCountBlock / 64) * 64 * 4;  // (+ the static tables)
-    const void* fn = reinterpret_cast<const void*>(&k_lane_count<kLaneRep, COMPAT, 1>);
-    hipLaunchKernelGGL((k_lane_count<kLaneRep, COMPAT, 1>), dim3(resident_grid(fn, lds)), dim3(kLaneCountBlock), lds,
-                       st, b, scx, ox, d_tab, cfg.lane_max, wave_stage, 0u);
-  } else {
-    const size_t lds = stage_lds + keys_lds;  // (+ the static tables)
-    const void* fn = reinterpret_cast<const void*>(&k_lane_count<kLaneRep, COMPAT, 2>);
-    hipLaunchKernelGGL((k_lane_count<kLaneRep, COMPAT, 2>), dim3(resident_grid(fn, lds)), dim3(kLaneCountBlock), lds,
-                       st, b, scx, ox, d_tab, cfg.lane_max, wave_stage, 0u);
-  }
-  mark(kStageBodyCount);
-  if (cfg.body_count && lane_lds > kLaneLdsBudget) {  // deferred bodies (lane modes 1 and 2 only)
-    const uint32_t g = 8u * (uint32_t)cfg.num_cus;
-    hipLaunchKernelGGL(k_body_count, dim3(g), dim3(kBodyBlock), 0, st, b, ox);
-  }
-  mark(kStageTailCount);
-  // the exception paths before the scan: one launch, one round of resident workgroups (role 2 splits
-  // the large payloads evenly over the waves; role 1 grid-strides over the slow list)
-  {
-    const bool gord = tail_gord;
-    const size_t lds = tail_lds;
-    const void* fn = gord ? reinterpret_cast<const void*>(&k_tail_count<COMPAT, true>)
-                          : reinterpret_cast<const void*>(&k_tail_count<COMPAT, false>);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kTailBlock, lds) != hipSuccess || per_cu < 1)
-      per_cu = 1;
-    // (a small batch: fewer workgroups -- both roles stride -- so that an empty launch, the usual case
-    // of batches of small records, is not a full grid of dispatches)
-    uint32_t g = std::min((uint32_t)(per_cu * cfg.num_cus), std::max(8u, (uint32_t)(b.nbytes >> 16) + b.n / 4096u));
-    if (!cfg.body_count) g = std::min(g, 32u);  // (no record above lane_max: role 2 has nothing to stream)
-    const uint32_t fin = quiet_big ? 1u : 0u;
-    // the walking workgroups: one 64-record group per wave, at most 1/32 of the grid (the streaming
-    // CRC is bound by its workgroups' issue rate: each one it loses costs it 1/g of its time, while a
-    // walking wave takes several groups well within the CRC's time). Every workgroup of the grid is
-    // resident, the walkers dispatched first.
-    uint32_t wb = 0;
-    if (walk_beside) {
-      if (g < 2u) g = 2u;
-      const uint32_t ng = (uint32_t)((b.n + 63) / 64);
-      const uint32_t cap = cfg.walk_blocks ? cfg.walk_blocks : std::max(1u, g / 32u);
-      wb = std::max(1u, std::min({(ng + kTailBlock / 64 - 1) / (kTailBlock / 64), cap, g - 1u}));
-    }
-    if (gord)
-      hipLaunchKernelGGL((k_tail_count<COMPAT, true>), dim3(g), dim3(kTailBlock), lds, st, b, scx, ox, d_tab, d_consts,
-                         cfg.lane_max, fin, wb);
-    else
-      hipLaunchKernelGGL((k_tail_count<COMPAT, false>), dim3(g), dim3(kTailBlock), lds, st, b, scx, ox, d_tab,
-                         d_consts, cfg.lane_max, fin, wb);
-  }
-  if (quiet_big) {  // (k_tail_count's last workgroup finished the decode)
-    for (int i = kStageSpine; i <= kStageMaterialize; ++i) mark(i);
-    return hipGetLastError();
-  }
-  if (cfg.poison[0] != 0xffffffffu && S > 0)
-    hipLaunchKernelGGL(k_poison_loc, dim3(1), dim3(64), 0, st, ox, b.n, (uint32_t)S,
-                       make_uint4(cfg.poison[0], cfg.poison[1], cfg.poison[2], cfg.poison[3]));
-  mark(kStageSpine);
-  if (S > 0)
-    hipLaunchKernelGGL(k_spine, dim3(o.n_chunks * (uint32_t)S), dim3(kSpineBlock), 0, st, ox, sc.slot_kind, (uint32_t)S, n_tiles,
-                       scx.spec, b.n);
-  mark(kStageDownGather);
-  if (S > 0) {
-    // (at most 8 resident 256-thread workgroups per CU; larger batches stride). Every slot with a
-    // speculative target: usually all placed and nothing to do but the launch, one per CU (a failed
-    // placement strides over the tiles)
-    // (all placed: usually nothing to do but the launch; a small batch also strides with fewer)
-    uint32_t resident = all_spec ? std::min((uint32_t)cfg.num_cus, std::max(8u, n_tiles / 4u)) : 8u * (uint32_t)cfg.num_cus;
-    if (all_spec && quiet) resident = std::min(resident, 32u);
-    if (n_tiles >= 16u * (uint32_t)cfg.num_cus) {
-      const uint32_t ng = (n_tiles + 3) / 4;
-      hipLaunchKernelGGL((k_down_gather<COMPAT, 4>), dim3(ng < resident ? ng : resident), dim3(kLaneBlock), 0, st, b,
-                         scx, ox, cfg.lane_max, n_tiles);
-    } else {
-      hipLaunchKernelGGL((k_down_gather<COMPAT, 1>), dim3(n_tiles < resident ? n_tiles : resident), dim3(kLaneBlock),
-                         0, st, b, scx, ox, cfg.lane_max, n_tiles);
-    }
-  }
-  mark(kStageTailGather);
-  bool all_spec_t = scx.spec && cfg.spec_h && S <= 64;
-  for (size_t k = 0; all_spec_t && k < S; ++k) all_spec_t = cfg.spec_h[k] != 0u;
-  if (S > 0) {  // the gathers after the scan: lane records' lists, staged and huge large records
-    const size_t lds = (size_t)kWRegion * kWavesPerBlock;
-    const void* fn = reinterpret_cast<const void*>(&k_tail_gather<COMPAT>);
-    int per_cu = 0;  // one round of resident workgroups (3 per CU: a second round would run at 1/3)
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kWaveBlock, lds) != hipSuccess || per_cu < 1)
-      per_cu = 1;
-    int g = per_cu * cfg.num_cus < cfg.wave_grid ? per_cu * cfg.num_cus : cfg.wave_grid;
-    // (a small batch: its roles stride over fewer waves; large records keep the full grid)
-    g = (int)std::min<uint64_t>((uint64_t)g, std::max<uint64_t>(8u, std::max<uint64_t>(b.n / 1024u, b.nbytes >> 16)));
-    if (quiet && all_spec_t) g = std::min(g, 32);
-    hipLaunchKernelGGL((k_tail_gather<COMPAT>), dim3(g), dim3(kWaveBlock), lds, st, b, scx, ox, cfg.lane_max);
-  }
-  mark(kStageMaterialize);  // (the caller launches the optional materialize pass and marks the end)
-  return hipGetLastError();
+static auto lane_count_kernel(int mode) {
+  return mode == 0   ? &k_lane_count<kLaneRep, COMPAT, 0>
+         : mode == 1 ? &k_lane_count<kLaneRep, COMPAT, 1>
+                     : &k_lane_count<kLaneRep, COMPAT, 2>;
 }
 
-hipError_t launch_decode(const DevBatch& b, const DevSchema& sc, const DevOut& o, LaunchCfg& cfg,
-                         const uint32_t* d_tab, const uint32_t* d_consts, hipStream_t st, hipEvent_t* ev) {
-  if (b.flags & kFlagSpecVarint) return launch_all<false>(b, sc, o, cfg, d_tab, d_consts, st, ev);
-  return launch_all<true>(b, sc, o, cfg, d_tab, d_consts, st, ev);
+void launch_lane_count(const DevBatch& b, const DevSchema& sc, const DevOut& o, const uint32_t* d_tab,
+                       const LaunchCfg& cfg, bool defer_big, int mode, int max_blocks, hipStream_t st) {
+  static_assert(kLaneCountBlock == 256, "max_blocks comes from LaunchCfg::lane_grid, which counts 256-thread workgroups");
+  const auto fn = (b.flags & kFlagSpecVarint) ? lane_count_kernel<false>(mode) : lane_count_kernel<true>(mode);
+  const size_t lds = lane_count_lds(sc, mode);
+  const int g = std::min(resident_blocks(fn, kLaneCountBlock, lds, cfg.num_cus), max_blocks);
+  hipLaunchKernelGGL(fn, dim3(g), dim3(kLaneCountBlock), lds, st, b, sc, o, d_tab, cfg.lane_max,
+                     cfg.wave_stage < kWStage ? cfg.wave_stage : kWStage, defer_big ? 1u : 0u);
 }
 
-// Row splits of the finally placed slots (tfrg_info.placed_slots: the identity 0..n, never stored by
-// the decode) written into the device columns, for tfrg_result_device's view; the placed mask is
-// read from the decode's info words on the device (no host round trip).
-__global__ __launch_bounds__(256) void k_fill_placed_rows(uint32_t* __restrict__ rs, const uint32_t* __restrict__ info,
-                                                          uint32_t n_slots, uint32_t n) {
-  const uint64_t placed = ((uint64_t)info[kInfoPlacedHi] << 32) | info[kInfoPlacedLo];
-  const uint32_t k = blockIdx.y;
-  if (k >= 64u || k >= n_slots || !((placed >> k) & 1ull)) return;
-  uint32_t* row = rs + (size_t)k * (n + 1u);
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i <= n; i += gridDim.x * 256u) row[i] = i;
+void launch_body_count(const DevBatch& b, const DevOut& o, int num_cus, hipStream_t st) {
+  hipLaunchKernelGGL(k_body_count, dim3(8u * (uint32_t)num_cus), dim3(kBodyBlock), 0, st, b, o);
 }
 
-hipError_t launch_fill_placed_rows(uint32_t* rs, const uint32_t* info, uint32_t n_slots, uint32_t n, hipStream_t st) {
-  const uint32_t slots = n_slots < 64u ? n_slots : 64u;
-  if (!slots) return hipSuccess;
-  const uint32_t blocks = (n + 1u + 255u) / 256u;
-  hipLaunchKernelGGL(k_fill_placed_rows, dim3(blocks < 1024u ? blocks : 1024u, slots), dim3(256), 0, st, rs, info,
-                     n_slots, n);
-  return hipGetLastError();
-}
-
-// Streaming read (measurement only): each block reads a contiguous slab, U 16-byte loads in flight
-// per lane (all issued before any is consumed), nontemporal (the data is not reused).
-typedef uint32_t sr_u32x4 __attribute__((ext_vector_type(4)));
-template <int U>
-__global__ __launch_bounds__(256) void k_stream_read(const sr_u32x4* __restrict__ p, uint64_t n16, uint32_t* sink) {
-  uint32_t acc = 0;
-  const uint64_t per_block = (n16 + gridDim.x - 1) / gridDim.x;
-  const uint64_t b0 = (uint64_t)blockIdx.x * per_block;
-  const uint64_t b1 = b0 + per_block < n16 ? b0 + per_block : n16;
-  uint64_t i = b0 + threadIdx.x;
-  for (; i + (U - 1) * 256 < b1; i += U * 256) {
-    sr_u32x4 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(p + i + u * 256);
-#pragma unroll
-    for (int u = 0; u < U; ++u) acc ^= v[u].x ^ v[u].y ^ v[u].z ^ v[u].w;
+// max_blocks: the policy's cap on the grid (both roles stride). walk: the first workgroups walk the
+// records above lane_max (role_big_walk; cfg.walk_blocks caps them, 0: automatic).
+void launch_tail_count(const DevBatch& b, const DevSchema& sc, const DevOut& o, const uint32_t* d_tab,
+                       const uint32_t* d_consts, const LaunchCfg& cfg, bool finish, bool walk, uint32_t max_blocks,
+                       hipStream_t st) {
+  const bool compat = !(b.flags & kFlagSpecVarint);
+  bool gord;
+  const size_t lds = tail_count_lds(sc, gord);
+  const auto fn = compat ? (gord ? &k_tail_count<true, true> : &k_tail_count<true, false>)
+                         : (gord ? &k_tail_count<false, true> : &k_tail_count<false, false>);
+  // (role 2 splits the large payloads evenly over the waves; role 1 grid-strides over the slow list)
+  uint32_t g = std::min((uint32_t)resident_blocks(fn, kTailBlock, lds, cfg.num_cus), max_blocks);
+  // the walking workgroups: one 64-record group per wave, at most 1/32 of the grid (the streaming
+  // CRC is bound by its workgroups' issue rate: each one it loses costs it 1/g of its time, while a
+  // walking wave takes several groups well within the CRC's time). Every workgroup of the grid is
+  // resident, the walkers dispatched first.
+  uint32_t wb = 0;
+  if (walk) {
+    if (g < 2u) g = 2u;
+    const uint32_t ng = (uint32_t)((b.n + 63) / 64);
+    const uint32_t cap = cfg.walk_blocks ? cfg.walk_blocks : std::max(1u, g / 32u);
+    wb = std::max(1u, std::min({(ng + kTailBlock / 64 - 1) / (kTailBlock / 64), cap, g - 1u}));
   }
-  for (; i < b1; i += 256) {
-    const sr_u32x4 a = p[i];
-    acc ^= a.x ^ a.y ^ a.z ^ a.w;
-  }
-  if (acc == 0x9e3779b9u) atomicXor(sink, acc);  // practically never taken; keeps the loads live
+  hipLaunchKernelGGL(fn, dim3(g), dim3(kTailBlock), lds, st, b, sc, o, d_tab, d_consts, cfg.lane_max, finish ? 1u : 0u,
+                     wb);
 }
 
-// variant: 0 = 4 loads in flight, 16 blocks per CU; 1 = 8 loads, 8 blocks per CU; 2 = 8 loads, 16
-// blocks per CU; 3 = 16 loads, 4 blocks per CU (bench.py reports the fastest)
-hipError_t launch_stream_read(const void* d, uint64_t nbytes, uint32_t* sink, hipStream_t st, int variant) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const sr_u32x4* q = static_cast<const sr_u32x4*>(d);
-  switch (variant) {
-    case 0: hipLaunchKernelGGL(k_stream_read<4>, dim3(cus * 16), dim3(256), 0, st, q, nbytes / 16, sink); break;
-    case 1: hipLaunchKernelGGL(k_stream_read<8>, dim3(cus * 8), dim3(256), 0, st, q, nbytes / 16, sink); break;
-    case 2: hipLaunchKernelGGL(k_stream_read<8>, dim3(cus * 16), dim3(256), 0, st, q, nbytes / 16, sink); break;
-    default: hipLaunchKernelGGL(k_stream_read<16>, dim3(cus * 4), dim3(256), 0, st, q, nbytes / 16, sink); break;
-  }
-  return hipGetLastError();
+// max_blocks: the policy's cap on the grid (the roles stride). The dynamic LDS is one kWRegion per
+// wave (stage + int64_ring's ring: the carve-up at the top of k_tail_gather; 3 resident workgroups
+// per CU: a second round would run at 1/3).
+void launch_tail_gather(const DevBatch& b, const DevSchema& sc, const DevOut& o, const LaunchCfg& cfg, int max_blocks,
+                        hipStream_t st) {
+  const size_t lds = (size_t)kWRegion * kWavesPerBlock;
+  const auto fn = (b.flags & kFlagSpecVarint) ? &k_tail_gather<false> : &k_tail_gather<true>;
+  const int g = std::min(resident_blocks(fn, kWaveBlock, lds, cfg.num_cus), max_blocks);
+  hipLaunchKernelGGL(fn, dim3(g), dim3(kWaveBlock), lds, st, b, sc, o, cfg.lane_max);
 }
 
 }  // namespace tfrg

@@ -1,7 +1,7 @@
 // tfrg_tpl.hip — k_tpl_lane: the record-shape template path of the lane-per-record decode (gfx950).
 //
 // Records of one file almost always share one structure: the same keys in the same order with the
-// same header bytes; only list contents differ (tfrg_internal.h, "Record-shape template"). For such
+// same header bytes; only list contents differ (tfrg_layout.h, "Record-shape template"). For such
 // a record the reference's whole decode (decoder.pyx:107-300: Example -> Features -> map entries ->
 // Feature -> list) yields the template's dict, and the TFRecord framing checks reduce to constants:
 // the length field and its masked CRC-32C are template bytes, and the payload CRC-32C is
@@ -22,7 +22,7 @@
 //     count / loc or speculatively placed value (DevSchema::spec; the row split r implicit), taken
 //     from the window registers at the template's (wave-uniform) position, and a select keeps each
 //     lane's own; then the per-tile value counts.
-// Frame classes (tfrg_internal.h kLtFrame): a record whose two CRC fields are 0 (the reference's own
+// Frame classes (tfrg_layout.h kLtFrame): a record whose two CRC fields are 0 (the reference's own
 // writers) matches an unchecked-frame template of its shape, verdict TFRG_V_LEN_MATCH; a decode
 // without CRC verdicts (LeanArgs::nocrc) matches on the mask alone, with no tables in LDS.
 // A wave owns a contiguous range of groups (whole tiles, or half a tile on small batches).
@@ -31,6 +31,7 @@
 // (DevOut::rlist).
 #include <hip/hip_runtime.h>
 #include "tfrg_internal.h"
+#include "tfrg_dev.h"
 #include "crc32c.h"
 #include "../../include/tfrg_status.h"
 
@@ -82,40 +83,6 @@ typedef __attribute__((address_space(3))) void lds_void;
 #ifndef TFRG_TPL_STORE_NT
 #define TFRG_TPL_STORE_NT 1
 #endif
-template <bool NT, typename T>
-__device__ __forceinline__ void put(T* p, T v) {
-  if constexpr (NT)
-    __builtin_nontemporal_store(v, p);
-  else
-    *p = v;
-}
-
-__device__ __forceinline__ uint32_t rfl(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
-
-// ((x >> 8K) & 0xff) * 4 in one VALU (a shift with an SDWA byte select of its source)
-template <int K>
-__device__ __forceinline__ uint32_t bx4(uint32_t x) {
-  uint32_t r;
-  const uint32_t two = 2u;
-  if constexpr (K == 0)
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
-        : "=v"(r) : "v"(two), "v"(x));
-  else if constexpr (K == 1)
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1"
-        : "=v"(r) : "v"(two), "v"(x));
-  else if constexpr (K == 2)
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2"
-        : "=v"(r) : "v"(two), "v"(x));
-  else
-    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3"
-        : "=v"(r) : "v"(two), "v"(x));
-  return r;
-}
-
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
 // table Q of a packed table word at byte address bx (tw: the word's four tables in LDS, wave-uniform;
 // one add per lookup, the table's place in the word folds into the ds_read offset)
 template <int Q>
@@ -126,15 +93,8 @@ __device__ __forceinline__ uint32_t tl(const uint8_t* tw, uint32_t bx) {
 // linear CRC contribution of a word whose 4 bytes sit at distances D+3, D+2, D+1, D from the payload
 // end; tw: the tables T_D .. T_{D+3}
 __device__ __forceinline__ uint32_t lin_word(const uint8_t* tw, uint32_t x) {
-  return xor3(tl<3>(tw, bx4<0>(x)), tl<2>(tw, bx4<1>(x)), tl<1>(tw, bx4<2>(x))) ^ tl<0>(tw, bx4<3>(x));
+  return xor3(tl<3>(tw, byte_x4<0>(x)), tl<2>(tw, byte_x4<1>(x)), tl<1>(tw, byte_x4<2>(x))) ^ tl<0>(tw, byte_x4<3>(x));
 }
-
-// 7-bit groups of the bytes of w selected by byte mask m, compacted (a varint of <= 4 bytes)
-__device__ __forceinline__ uint32_t vgroups(uint32_t w, uint32_t m) {
-  w &= m;
-  return (w & 0x7fu) | ((w >> 1) & 0x3f80u) | ((w >> 2) & 0x1fc000u) | ((w >> 3) & 0xfe00000u);
-}
-__device__ __forceinline__ uint32_t bytes_mask(uint32_t nb) { return nb >= 4u ? 0xffffffffu : (1u << (nb << 3)) - 1u; }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -150,7 +110,7 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
   return x;
 }
 
-// The end of an optimistic decode (launch_all), by the last workgroup of k_tpl_lane: no 64-record
+// The end of an optimistic decode (launch_decode), by the last workgroup of k_tpl_lane: no 64-record
 // group was listed -- every record took a template -- so every slot's placement is final and the
 // passes after k_tpl_lane would have nothing to do but their bookkeeping, done here: the next
 // decode's info words zeroed (k_lane_count), slot totals n, column bases and kind totals (k_spine's
@@ -163,27 +123,10 @@ __device__ void tpl_quiet_finish(const DevOut& o, const uint8_t* slot_kind, uint
                                  uint32_t listed) {
   if (threadIdx.x < kInfoCount) o.info_next[threadIdx.x] = 0u;
   if (listed != 0u) return;  // (uniform; the host sees kInfoResid and re-runs the decode)
-  for (uint32_t k = threadIdx.x; k < n_slots; k += kTplBlock) {
-    o.totals[k] = n;
-    o.rs[(size_t)k * (n + 1u) + n] = n;
-  }
-  if (threadIdx.x == 0) {
-    uint64_t acc[4] = {0, 0, 0, 0};
-    for (uint32_t k = 0; k < n_slots; ++k) {
-      const uint32_t kd = slot_kind[k] & 3u;
-      o.slot_base[k] = acc[kd];
-      acc[kd] += n;
-    }
-    for (int k = 0; k < 4; ++k) o.kind_totals[k] = acc[k];
-    if (acc[TFRG_KIND_INT64] > o.cap_i64 || acc[TFRG_KIND_FLOAT] > o.cap_f32 || acc[TFRG_KIND_BYTES] > o.cap_b)
-      o.info[kInfoOverflow] = 1u;
-    const uint64_t pm = n_slots >= 64u ? ~0ull : (1ull << n_slots) - 1ull;
-    o.info[kInfoPlacedLo] = (uint32_t)pm;
-    o.info[kInfoPlacedHi] = (uint32_t)(pm >> 32);
-  }
+  all_placed_finish(o, slot_kind, n_slots, n, kTplBlock);
 }
 
-// UF: the launch knows frame classes (tfrg_internal.h kLtFrame) -- some template has an unchecked
+// UF: the launch knows frame classes (tfrg_layout.h kLtFrame) -- some template has an unchecked
 // frame, or the decode computes no CRCs (A.nocrc); a hit's verdict is then the lane's own. !UF: every
 // template is spec-framed and CRCs are on, the code of a spec-only context as it always was.
 template <int W, int OM, bool ST, bool UF>
@@ -200,7 +143,7 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
   uint32_t* const limg = tab + A.tab_words;
   constexpr uint32_t kWaves = kTplBlock / 64;
   constexpr uint32_t kTw = kLiTw(W);
-  const uint32_t lane = threadIdx.x & 63u, wib = rfl(threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63u, wib = rfl32(threadIdx.x >> 6);
   cu32* gimg = (cu32*)img;  // (the image's wave-uniform words: scalar loads)
   // (A.nocrc: no variable word enters a CRC, no table is read -- none is in LDS, tab_words 0)
   const bool nocrc = UF && A.nocrc;
@@ -288,7 +231,7 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
       const uint32_t pe = (uint32_t)__builtin_amdgcn_update_dpp((int)e, (int)e, 0x138, 0xf, 0xf, false);  // lane - 1's
       const bool bad = lane < nv && (e < pe || e > nb);
       if (nv && !__ballot(bad)) {
-        const uint32_t e0 = rfl(e), hi = (uint32_t)__builtin_amdgcn_readlane((int)e, (int)(nv - 1u));
+        const uint32_t e0 = rfl32(e), hi = (uint32_t)__builtin_amdgcn_readlane((int)e, (int)(nv - 1u));
         const uint32_t lo = (e0 >= 4u * W ? e0 - 4u * W : 0u) & ~15u;
         const uint32_t nch = (hi - lo + 15u) >> 4;  // 16-byte pieces
         // (the window reads run one dword past the lane's end)
@@ -471,10 +414,10 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
             if (r < T.lim) {
               constexpr bool kNt = ST && TFRG_TPL_STORE_NT;
               if (T.kind == TFRG_KIND_INT64) {
-                put<kNt>(reinterpret_cast<uint64_t*>(T.v1) + r, (uint64_t)lx);
+                st_nt<kNt>(reinterpret_cast<uint64_t*>(T.v1) + r, (uint64_t)lx);
               } else {
-                put<kNt>(reinterpret_cast<uint32_t*>(T.v1) + r, lx);
-                if (T.kind == TFRG_KIND_BYTES && !(A.implicit & TFRG_IMPLICIT_BYTES_LEN)) put<kNt>(T.v2 + r, ly);
+                st_nt<kNt>(reinterpret_cast<uint32_t*>(T.v1) + r, lx);
+                if (T.kind == TFRG_KIND_BYTES && !(A.implicit & TFRG_IMPLICIT_BYTES_LEN)) st_nt<kNt>(T.v2 + r, ly);
               }
             }
           } else {
