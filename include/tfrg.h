@@ -127,6 +127,9 @@ int tfrg_ctx_device_bytes(tfrg_ctx* ctx, uint64_t* bytes, uint64_t* hint_reruns)
 /* wavefront records spanning <= nbytes are staged in LDS (clamped to the kernel's 12 KiB stage;
  * 0 routes every wavefront record to the streaming kernels). A tuning/testing knob. */
 int tfrg_ctx_set_wave_stage(tfrg_ctx* ctx, uint32_t nbytes);
+/* chunk size of tfrg_index_device: a power of two from 64 to 65536, 0 = the default (4096). A
+ * tuning/testing knob: with small chunks small images exercise the multi-chunk logic. */
+int tfrg_ctx_set_index_chunk(tfrg_ctx* ctx, uint32_t bytes);
 
 /* Record-shape templates (no reference counterpart: a fast path under decoder.pyx:107-300). Up to
  * TFRG_TPL_MAX shapes of canonical records (payload <= TFRG_TPL_MAX_PAYLOAD bytes, at most
@@ -231,6 +234,41 @@ int tfrg_decode_device32(tfrg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes,
 /* Same from host memory: stages bytes/start/end into context-owned HBM (H2D on the stream). */
 int tfrg_decode_host(tfrg_ctx* ctx, const uint8_t* h_bytes, uint64_t nbytes, const uint64_t* h_start,
                      const uint64_t* h_end, uint32_t n, uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Framing index on the device (the walk of indexer.pyx:212-252, as tfrg_index_buffer runs it on the
+ * host, for file images that are already in HBM). d_bytes[0, nbytes) holds n_pieces images back to
+ * back (sum(piece_sizes) == nbytes < 2^32), readable to round_up(nbytes, 16) + 16. With fallback == 0
+ * the rows written are bit for bit those of the host walk over every piece, shifted by the piece's
+ * offset in the batch: a last record running past its piece is indexed, a tail of fewer than 8 bytes
+ * ends a piece, a header of 8..11 bytes at the tail is a record, len + 4 is taken as int64 and a
+ * seek that overflows or lands below 0 ends the piece after its record, start + 16 + len wraps in
+ * u64. The one difference: a length whose seek lands at or before its own record's start reports
+ * TFRG_INDEX_FB_SEEK (the host walk goes on from there and need not terminate).
+ * The pieces are cut into chunks that are walked in parallel from guessed entries; the chain of
+ * chunks from each piece's start is then verified and wrong guesses are re-walked, for a bounded
+ * number of rounds (TFRG_INDEX_FB_ROUNDS if mismatches remain). Up to cap rows are written to
+ * d_start / d_end / d_end32 (device, each may be NULL); piece_records (host, [n_pieces] or NULL)
+ * receives the records per piece. One host synchronisation: the summary comes back in one small D2H
+ * on stream (NULL: the context's). Scratch is the context's (tfrg_ctx_device_bytes counts it); the
+ * last decode's result is untouched. TFRG_E_ARG: nbytes >= 2^32, sizes that do not sum to nbytes, a
+ * NULL info. n_pieces == 0 or nbytes == 0: 0 records, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+#define TFRG_INDEX_FB_ROUNDS 1u
+#define TFRG_INDEX_FB_SEEK 2u
+typedef struct tfrg_index_info {
+  uint64_t n_records;       /* records of all pieces (may exceed cap: only cap rows are written) */
+  uint32_t fallback;        /* 0: the columns are exact. TFRG_INDEX_FB_ROUNDS: not proven within the
+                               repair bound. TFRG_INDEX_FB_SEEK: a length field seeks backwards.
+                               Nonzero: outputs undefined, index on the host */
+  uint32_t tiled;           /* 1: start[i] == end[i-1] for every i > 0 and every end < 2^32
+                               (d_end32 + first_start may drive tfrg_decode_device32 without starts) */
+  uint32_t first_start;
+  uint32_t n_chunks, repaired_chunks, repair_rounds;   /* diagnostics */
+} tfrg_index_info;
+int tfrg_index_device(tfrg_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* piece_sizes,
+                      uint32_t n_pieces, uint64_t* d_start, uint64_t* d_end, uint32_t* d_end32, uint64_t cap,
+                      uint64_t* piece_records, void* stream, tfrg_index_info* info);
 
 typedef struct tfrg_info {
   uint32_t n_records;
@@ -347,7 +385,8 @@ int tfrg_result_dense(tfrg_ctx* ctx, const tfrg_dense_spec* specs, uint32_t n_sp
  * read+decode for whole-dataset reads). Two slots, each with a pinned staging buffer of batch_bytes,
  * a device input buffer and its own decode context + stream. tfrg_stream_submit hands a batch (pieces:
  * file byte ranges or host memory, whole files or record-aligned runs of them) to the slot's worker
- * thread, which reads / copies it into the slot's pinned buffer (copy_threads threads), indexes every piece with the native framing walk,
+ * thread, which reads / copies it into the slot's pinned buffer (copy_threads threads), indexes every piece with the native framing walk
+ * (or on the device after the H2D copy: tfrg_stream_set_device_index),
  * enqueues the H2D copies and tfrg_decode_device on the slot's stream, and returns at once; so the
  * next batch stages while this one decodes. tfrg_stream_wait blocks until the slot's batch is
  * enqueued and gives its record count (and records per piece); results are then read from
@@ -375,6 +414,12 @@ int tfrg_stream_wait(tfrg_stream* s, int slot, uint64_t* n_records, uint64_t* nb
  * extended and the batch decoded again (tfrg_decode_host on the slot's context). */
 int tfrg_stream_result(tfrg_stream* s, int slot, tfrg_info* info, tfrg_columns* host);
 /* the slot's pinned copy of its batch (bytes_list views index into it) and its record ranges */
+/* on != 0: the slot workers build the framing index on the device (tfrg_index_device over the bytes
+ * just copied H2D; the (start, end) columns come back D2H beside the result columns) instead of
+ * walking the pieces on the host; a batch that reports a fallback is indexed on the host as before.
+ * Default 0. Call it while both slots are idle. stage_ms[1] is then the device index with its
+ * synchronisation (the bytes' H2D included: the index waits for it). */
+int tfrg_stream_set_device_index(tfrg_stream* s, int on);
 const uint8_t* tfrg_stream_host_buffer(tfrg_stream* s, int slot);
 int tfrg_stream_host_ranges(tfrg_stream* s, int slot, const uint64_t** starts, const uint64_t** ends);
 

@@ -15,6 +15,7 @@
 #include "../../include/tfrg.h"
 #include "crc32c.h"
 #include "tfrg_dense.h"
+#include "tfrg_frame.h"
 #include "tfrg_internal.h"
 #include "tfrg_learn.h"
 
@@ -175,6 +176,11 @@ struct tfrg_ctx {
     hipStream_t st;
   } last{};
   Offsets last_off{};
+  // tfrg_index_device: chunk table, piece rows + summary (device), their pinned host staging
+  uint32_t index_chunk = kIndexChunkDefault;  // tfrg_ctx_set_index_chunk
+  DBuf fr_tab, fr_dev;
+  void* fr_pin = nullptr;
+  size_t fr_pin_cap = 0;
   // debug hook: records whose list locations are poisoned after the count passes (tests)
   uint32_t poison[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
 };
@@ -276,7 +282,7 @@ int tfrg_ctx_destroy(tfrg_ctx* c) {
                  &c->order, &c->count, &c->loc, &c->rs, &c->ident, &c->slot_base, &c->totals, &c->kind_totals, &c->i64,
                  &c->f32, &c->b_off, &c->b_len, &c->big_list, &c->slow_list, &c->miss, &c->info, &c->tsum,
                  &c->bdata, &c->boff64, &c->blb, &c->bbig, &c->crc_rec, &c->crc_base, &c->crc_part, &c->tpl, &c->spec,
-                 &c->dq, &c->dq_cnt, &c->lmask, &c->rlist};
+                 &c->dq, &c->dq_cnt, &c->lmask, &c->rlist, &c->fr_tab, &c->fr_dev};
   for (DBuf* b : all) b->release();
   if (c->order_ev) (void)hipEventDestroy(c->order_ev);
   for (hipEvent_t e : c->dense_ev)
@@ -285,6 +291,7 @@ int tfrg_ctx_destroy(tfrg_ctx* c) {
     for (auto& e : c->ev) (void)hipEventDestroy(e);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   if (c->info_pin) (void)hipHostFree(c->info_pin);
+  if (c->fr_pin) (void)hipHostFree(c->fr_pin);
   delete c;
   return 0;
 }
@@ -317,7 +324,7 @@ int tfrg_ctx_device_bytes(tfrg_ctx* c, uint64_t* bytes, uint64_t* reruns) {
                        &c->totals, &c->kind_totals, &c->i64, &c->f32, &c->b_off, &c->b_len, &c->big_list,
                        &c->slow_list, &c->miss, &c->info, &c->tsum, &c->bdata, &c->boff64, &c->blb, &c->bbig,
                        &c->crc_rec, &c->crc_base, &c->crc_part, &c->tpl, &c->spec, &c->dq, &c->dq_cnt, &c->lmask,
-                       &c->rlist};
+                       &c->rlist, &c->fr_tab, &c->fr_dev};
   uint64_t t = 0;
   for (const DBuf* b : all) t += b->cap;
   if (bytes) *bytes = t;
@@ -328,6 +335,99 @@ int tfrg_ctx_device_bytes(tfrg_ctx* c, uint64_t* bytes, uint64_t* reruns) {
 int tfrg_ctx_set_wave_stage(tfrg_ctx* c, uint32_t nbytes) {
   if (!c) return TFRG_E_ARG;
   c->wave_stage = nbytes;
+  return 0;
+}
+
+int tfrg_ctx_set_index_chunk(tfrg_ctx* c, uint32_t bytes) {
+  if (!c) return TFRG_E_ARG;
+  if (bytes && (bytes < kIndexChunkMin || bytes > kIndexChunkMax || (bytes & (bytes - 1)))) {
+    set_error("index chunk must be a power of two from 64 to 65536 (0: the default)");
+    return TFRG_E_ARG;
+  }
+  c->index_chunk = bytes ? bytes : kIndexChunkDefault;
+  return 0;
+}
+
+// The framing index of n_pieces images in HBM (tfrg_frame.h: guess, walk, verify and repair, rank and
+// write). One host synchronisation: the summary words and piece rows come back in one D2H.
+int tfrg_index_device(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* piece_sizes,
+                      uint32_t n_pieces, uint64_t* d_start, uint64_t* d_end, uint32_t* d_end32, uint64_t cap,
+                      uint64_t* piece_records, void* stream, tfrg_index_info* info) {
+  if (!c || !info) {
+    set_error("tfrg_index_device: NULL context or info");
+    return TFRG_E_ARG;
+  }
+  memset(info, 0, sizeof(*info));
+  uint64_t sum = 0;
+  for (uint32_t i = 0; i < n_pieces; ++i) sum += piece_sizes[i];
+  if (nbytes >= (1ull << 32) || sum != nbytes) {
+    set_error(nbytes >= (1ull << 32) ? "tfrg_index_device: batch larger than 4 GiB: split it"
+                                     : "tfrg_index_device: the piece sizes do not sum to nbytes");
+    return TFRG_E_ARG;
+  }
+  for (uint32_t i = 0; piece_records && i < n_pieces; ++i) piece_records[i] = 0;
+  info->tiled = 1;
+  if (!n_pieces || !nbytes) return 0;
+  if (!d_bytes) return TFRG_E_ARG;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+  uint32_t shift = 0;
+  while ((1u << shift) < c->index_chunk) ++shift;
+  // pinned staging: the piece table (in), then the summary words and the piece rows (out)
+  const size_t in_bytes = ((size_t)n_pieces * sizeof(FrPiece) + 63) & ~(size_t)63;
+  const size_t out_bytes = kFsWords * 4 + (size_t)n_pieces * sizeof(FrPieceOut);
+  if (c->fr_pin_cap < in_bytes + out_bytes) {
+    if (c->fr_pin) (void)hipHostFree(c->fr_pin);
+    c->fr_pin = nullptr;
+    c->fr_pin_cap = 0;
+    const size_t want = 2 * (in_bytes + out_bytes) + 4096;
+    if (hipHostMalloc(&c->fr_pin, want) != hipSuccess) {
+      set_error("pinned index staging allocation failed");
+      return TFRG_E_NOMEM;
+    }
+    c->fr_pin_cap = want;
+  }
+  FrPiece* const h_pieces = (FrPiece*)c->fr_pin;
+  uint8_t* const h_out = (uint8_t*)c->fr_pin + in_bytes;
+  FrTab T{};
+  const uint64_t nc = fr_layout(piece_sizes, n_pieces, shift, h_pieces, &T.jumps);
+  if (nc >= 0xffffffffull) {
+    set_error("tfrg_index_device: too many pieces");
+    return TFRG_E_LIMIT;
+  }
+  const uint32_t n = (uint32_t)nc;
+  const uint32_t nb = (n + kFrBlock - 1) / kFrBlock;
+  // (every earlier index call has been synchronised: growing frees nothing in use)
+  HIP_TRY(c->fr_tab.ensure(((size_t)n * 10 + nb) * 4));
+  HIP_TRY(c->fr_dev.ensure(in_bytes + out_bytes));
+  uint8_t* const d_in = c->fr_dev.as<uint8_t>();
+  uint8_t* const d_out = d_in + in_bytes;
+  HIP_TRY(hipMemcpyAsync(d_in, h_pieces, (size_t)n_pieces * sizeof(FrPiece), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(d_out, 0, out_bytes, st));
+  T.bytes = d_bytes;
+  T.pieces = (const FrPiece*)d_in;
+  T.n_pieces = n_pieces;
+  T.n_chunks = n;
+  T.shift = shift;
+  uint32_t* w = c->fr_tab.as<uint32_t>();
+  uint32_t** cols[] = {&T.entry, &T.exit, &T.count, &T.cflags, &T.cpiece, &T.mark, &T.jump[0], &T.jump[1], &T.pend, &T.pend2};
+  for (uint32_t** col : cols) {
+    *col = w;
+    w += n;
+  }
+  T.bsum = w;
+  T.summ = (uint32_t*)d_out;
+  T.pout = (FrPieceOut*)(d_out + kFsWords * 4);
+  T.crc_t0 = c->crc_tab.as<uint32_t>();  // the byte table leads the context's CRC tables
+  T.start = d_start;
+  T.end = d_end;
+  T.end32 = d_end32;
+  T.cap = cap;
+  HIP_TRY(launch_frame_index(T, c->num_cus, st));
+  HIP_TRY(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  fr_finish((const uint32_t*)h_out, (const FrPieceOut*)(h_out + kFsWords * 4), h_pieces, n_pieces, n, piece_records,
+            info);
   return 0;
 }
 

@@ -320,6 +320,9 @@ void launch_tail_gather(const DevBatch& b, const DevSchema& sc, const DevOut& o,
                         hipStream_t st);
 hipError_t launch_fill_placed_rows(uint32_t* rs, const uint32_t* info, uint32_t n_slots, uint32_t n, hipStream_t st);
 hipError_t launch_stream_read(const void* d, uint64_t nbytes, uint32_t* sink, hipStream_t st, int variant);
+// tfrg_frame.hip: every phase of the chunked framing index (tfrg_frame.h) enqueued on st
+struct FrTab;
+hipError_t launch_frame_index(const FrTab& T, int num_cus, hipStream_t st);
 // tfrg_decode.cpp: the launch policy of one decode. ev: optional kNumStages + 1 events recorded on
 // `stream` before each stage and after the last.
 hipError_t launch_decode(const DevBatch& b, const DevSchema& sc, const DevOut& o, LaunchCfg& cfg,

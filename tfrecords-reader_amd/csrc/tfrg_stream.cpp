@@ -76,6 +76,7 @@ struct tfrg_stream {
   uint64_t cap = 0;       // staging bytes per slot
   uint64_t max_rec = 0;   // records per slot (a framed record is >= 16 bytes)
   int copy_threads = 4;
+  bool device_index = false;  // tfrg_stream_set_device_index
   tfrg_ctx* ctx[2] = {nullptr, nullptr};
   uint8_t* h_buf[2] = {nullptr, nullptr};
   uint64_t* h_se[2] = {nullptr, nullptr};  // pinned [start..., end...]
@@ -182,47 +183,84 @@ static int stage_and_decode(tfrg_stream* s, const Job& j, double* ph) {
     set_error("reading a TFRecord file piece failed");
     return TFRG_E_IO;
   }
-  // framing index of every piece (bit-exact with indexer.pyx:212-252), pieces in parallel: a count
-  // walk, then a second walk writing each piece's (start, end) columns, shifted to its offset in the
-  // batch, straight into the pinned staging index (both walks touch 8 bytes per record)
   const size_t P = j.pieces.size();
   std::vector<uint64_t> base(P + 1, 0), cnt(P, 0), first(P + 1, 0);
   for (size_t i = 0; i < P; ++i) base[i + 1] = base[i] + j.pieces[i].size;
-  const int T = std::max(1, std::min<int>(s->copy_threads, (int)P));
-  auto run = [&](auto&& body) {
-    std::vector<std::thread> ts;
-    for (int q = 1; q < T; ++q) ts.emplace_back(body, q);
-    body(0);
-    for (auto& th : ts) th.join();
-  };
-  run([&](int q) {
-    for (size_t i = q; i < P; i += T) {
-      const int64_t c = tfrg_index_buffer(s->h_buf[k] + base[i], j.pieces[i].size, nullptr, 0);
-      cnt[i] = c > 0 ? (uint64_t)c : 0u;
-    }
-  });
-  for (size_t i = 0; i < P; ++i) first[i + 1] = first[i] + cnt[i];
-  const uint64_t n = first[P];
-  if (n > s->max_rec) {
-    set_error("too many records for the stream's staging buffer");
-    return TFRG_E_LIMIT;
-  }
-  uint64_t* st = s->h_se[k];
-  run([&](int q) {
-    for (size_t i = q; i < P; i += T)
-      if (cnt[i])
-        tfrg_index_split(s->h_buf[k] + base[i], j.pieces[i].size, base[i], st + first[i],
-                         st + s->max_rec + first[i], (int64_t)cnt[i]);
-  });
-  s->piece_recs[k].assign(cnt.begin(), cnt.end());
-  ph[1] = ms_since(t);
   memset(s->h_buf[k] + total, 0, 16);  // readable padding past the last record
   const uint64_t pad = (total + 15) & ~15ull;
-  if (hipMemcpyAsync(s->d_buf[k], s->h_buf[k], pad + 16, hipMemcpyHostToDevice,
-                     s->stream[k]) != hipSuccess ||
-      (n && hipMemcpyAsync(s->d_se[k], st, n * 8, hipMemcpyHostToDevice, s->stream[k]) != hipSuccess) ||
-      (n && hipMemcpyAsync(s->d_se[k] + s->max_rec, st + s->max_rec, n * 8, hipMemcpyHostToDevice, s->stream[k]) !=
-                hipSuccess)) {
+  uint64_t* st = s->h_se[k];
+  uint64_t n = 0;
+  bool on_device = false;
+  if (s->device_index) {  // (total <= the staging capacity < 4 GiB)
+    // the framing index on the device, over the bytes just sent (tfrg_index_device: one
+    // synchronisation); its (start, end) columns come back beside the result columns
+    if (hipMemcpyAsync(s->d_buf[k], s->h_buf[k], pad + 16, hipMemcpyHostToDevice, s->stream[k]) != hipSuccess) {
+      set_error("H2D copy failed");
+      return TFRG_E_HIP;
+    }
+    std::vector<uint64_t> sizes(P);
+    for (size_t i = 0; i < P; ++i) sizes[i] = j.pieces[i].size;
+    tfrg_index_info ii;
+    const int rc = tfrg_index_device(s->ctx[k], s->d_buf[k], total, sizes.data(), (uint32_t)P, s->d_se[k],
+                                     s->d_se[k] + s->max_rec, nullptr, s->max_rec, cnt.data(), s->stream[k], &ii);
+    if (rc) return rc;
+    if (!ii.fallback) {
+      on_device = true;
+      n = ii.n_records;
+      if (n > s->max_rec) {
+        set_error("too many records for the stream's staging buffer");
+        return TFRG_E_LIMIT;
+      }
+      if (n && (hipMemcpyAsync(st, s->d_se[k], n * 8, hipMemcpyDeviceToHost, s->stream[k]) != hipSuccess ||
+                hipMemcpyAsync(st + s->max_rec, s->d_se[k] + s->max_rec, n * 8, hipMemcpyDeviceToHost,
+                               s->stream[k]) != hipSuccess)) {
+        set_error("D2H copy of the index failed");
+        return TFRG_E_HIP;
+      }
+    }
+  }
+  if (!on_device) {
+    // framing index of every piece (bit-exact with indexer.pyx:212-252), pieces in parallel: a count
+    // walk, then a second walk writing each piece's (start, end) columns, shifted to its offset in the
+    // batch, straight into the pinned staging index (both walks touch 8 bytes per record)
+    const int T = std::max(1, std::min<int>(s->copy_threads, (int)P));
+    auto run = [&](auto&& body) {
+      std::vector<std::thread> ts;
+      for (int q = 1; q < T; ++q) ts.emplace_back(body, q);
+      body(0);
+      for (auto& th : ts) th.join();
+    };
+    run([&](int q) {
+      for (size_t i = q; i < P; i += T) {
+        const int64_t c = tfrg_index_buffer(s->h_buf[k] + base[i], j.pieces[i].size, nullptr, 0);
+        cnt[i] = c > 0 ? (uint64_t)c : 0u;
+      }
+    });
+    for (size_t i = 0; i < P; ++i) first[i + 1] = first[i] + cnt[i];
+    n = first[P];
+    if (n > s->max_rec) {
+      set_error("too many records for the stream's staging buffer");
+      return TFRG_E_LIMIT;
+    }
+    run([&](int q) {
+      for (size_t i = q; i < P; i += T)
+        if (cnt[i])
+          tfrg_index_split(s->h_buf[k] + base[i], j.pieces[i].size, base[i], st + first[i],
+                           st + s->max_rec + first[i], (int64_t)cnt[i]);
+    });
+  }
+  s->piece_recs[k].assign(cnt.begin(), cnt.end());
+  ph[1] = ms_since(t);
+  // (with the device index on, the bytes are in place already, a fallback included)
+  if (!s->device_index &&
+      hipMemcpyAsync(s->d_buf[k], s->h_buf[k], pad + 16, hipMemcpyHostToDevice, s->stream[k]) != hipSuccess) {
+    set_error("H2D copy failed");
+    return TFRG_E_HIP;
+  }
+  if (!on_device && n &&
+      (hipMemcpyAsync(s->d_se[k], st, n * 8, hipMemcpyHostToDevice, s->stream[k]) != hipSuccess ||
+       hipMemcpyAsync(s->d_se[k] + s->max_rec, st + s->max_rec, n * 8, hipMemcpyHostToDevice, s->stream[k]) !=
+           hipSuccess)) {
     set_error("H2D copy failed");
     return TFRG_E_HIP;
   }
@@ -434,6 +472,17 @@ int tfrg_stream_wait(tfrg_stream* s, int slot, uint64_t* n_records, uint64_t* nb
     for (int q = 0; q < 4; ++q) stage_ms[q] = s->phase_ms[slot][q];
   const auto& pr = s->piece_recs[slot];
   for (int i = 0; i < cap && i < (int)pr.size(); ++i) piece_records[i] = pr[i];
+  return 0;
+}
+
+int tfrg_stream_set_device_index(tfrg_stream* s, int on) {
+  if (!s) return TFRG_E_ARG;
+  std::lock_guard<std::mutex> lk(s->m);
+  if (s->state[0] == kStaging || s->state[1] == kStaging) {
+    set_error("tfrg_stream_set_device_index: a slot is staging a batch");
+    return TFRG_E_ARG;
+  }
+  s->device_index = on != 0;
   return 0;
 }
 

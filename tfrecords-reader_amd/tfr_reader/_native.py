@@ -80,6 +80,22 @@ class TfrgColumns(C.Structure):
     ]
 
 
+class TfrgIndexInfo(C.Structure):
+    _fields_ = [
+        ("n_records", C.c_uint64),
+        ("fallback", C.c_uint32),
+        ("tiled", C.c_uint32),
+        ("first_start", C.c_uint32),
+        ("n_chunks", C.c_uint32),
+        ("repaired_chunks", C.c_uint32),
+        ("repair_rounds", C.c_uint32),
+    ]
+
+
+INDEX_FB_ROUNDS = 1
+INDEX_FB_SEEK = 2
+
+
 class TfrgDenseSpec(C.Structure):
     _fields_ = [
         ("slot", C.c_uint32),
@@ -166,6 +182,10 @@ SIGNATURES: dict[str, tuple] = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_uint64, u64p, u64p, C.c_uint32, C.c_uint32, C.c_void_p],
     ),
+    "tfrg_ctx_set_index_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "tfrg_index_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.POINTER(TfrgIndexInfo)]),
+    "tfrg_stream_set_device_index": (C.c_int, [C.c_void_p, C.c_int]),
     "tfrg_result_info": (C.c_int, [C.c_void_p, C.POINTER(TfrgInfo)]),
     "tfrg_result_device": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),
     "tfrg_result_fetch": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),

@@ -375,6 +375,115 @@ class HipDecoder:
         )
         self._last_n, self._last_host = n, None
 
+    # ------------------------------------------------------------------ framing index on the device
+    def set_index_chunk(self, nbytes: int) -> None:
+        """Chunk size of ``index_device`` (a power of two from 64 to 65536; 0: the default 4096)."""
+        N.check(self._lib.tfrg_ctx_set_index_chunk(self._ctx, int(nbytes)), "tfrg_ctx_set_index_chunk")
+
+    def index_device(self, d_bytes, nbytes: int | None = None, piece_sizes=None, *, stream: int | None = None):
+        """The framing index of file images that are already in HBM (tfrg_index_device): ``d_bytes`` is
+        a uint8 torch tensor on this decoder's device holding the images back to back (readable to
+        ``round_up(nbytes, 16) + 16``), ``piece_sizes`` their sizes (default: one image of ``nbytes``).
+        Returns a ``DeviceIndex``; with ``fallback != 0`` its columns are undefined and the images must
+        be indexed on the host."""
+        import torch  # noqa: PLC0415
+
+        nbytes = int(d_bytes.numel() if nbytes is None else nbytes)
+        sizes = np.ascontiguousarray([nbytes] if piece_sizes is None else piece_sizes, dtype=np.uint64)
+        dev = d_bytes.device
+        info = N.TfrgIndexInfo()
+        pr = np.zeros(max(sizes.size, 1), np.uint64)
+        # rows for well-formed images (a framed record spans >= 16 bytes, a piece's tail may hold one
+        # more); wrapping length fields can start records a byte apart: such an image is indexed again
+        # with the count the first run returned
+        cap = nbytes // 16 + int(sizes.size) + 1
+        while True:
+            st = torch.empty(cap, dtype=torch.int64, device=dev)
+            en = torch.empty(cap, dtype=torch.int64, device=dev)
+            e32 = torch.empty(cap, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()  # (the allocator may have work pending on the tensors)
+            N.check(self._lib.tfrg_index_device(self._ctx, C.c_void_p(d_bytes.data_ptr()), nbytes,
+                                                N.ptr(sizes, N.u64p), sizes.size, C.c_void_p(st.data_ptr()),
+                                                C.c_void_p(en.data_ptr()), C.c_void_p(e32.data_ptr()), cap,
+                                                N.ptr(pr, N.u64p), C.c_void_p(stream) if stream else None,
+                                                C.byref(info)),
+                    "tfrg_index_device")
+            if info.fallback or info.n_records <= cap:
+                break
+            cap = int(info.n_records)
+        cap = 0 if info.fallback else int(info.n_records)
+        return DeviceIndex(info, st[:cap], en[:cap], e32[:cap], pr[: sizes.size].astype(np.int64))
+
+    def decode_image(self, buf, piece_sizes=None, *, crc: bool = True, strict_crc: bool = False,
+                     materialize_bytes: bool = False) -> BatchResult:
+        """Decode whole file images without a host index: ``buf`` (host bytes / uint8 array, uploaded
+        here, or a uint8 torch tensor already on this decoder's device, readable 32 bytes past its
+        end) holds the images back to back, ``piece_sizes`` their sizes. The framing index is built on
+        the device (``index_device``; on a fallback, by ``indexer.index_buffer`` per piece on the
+        host) and the records are decoded from their u32 ends when the index is ``tiled``, else from
+        the u64 columns. The result equals ``decode(buf, starts, ends)`` over the host index."""
+        import torch  # noqa: PLC0415
+
+        dev = torch.device("cuda", self.device)
+        if isinstance(buf, torch.Tensor):
+            d_all, host = buf, None
+            nbytes = int(buf.numel()) - 32
+            if nbytes < 0:
+                raise ValueError("a device image needs 32 readable bytes past its end")
+        else:
+            host = _as_u8(buf)
+            nbytes = int(host.size)
+            pad = np.zeros(((nbytes + 15) & ~15) + 32, np.uint8)
+            pad[:nbytes] = host
+            d_all = torch.from_numpy(pad).to(dev)
+        sizes = np.ascontiguousarray([nbytes] if piece_sizes is None else piece_sizes, dtype=np.uint64)
+        if int(sizes.sum()) != nbytes:
+            raise ValueError("piece_sizes do not sum to the image bytes")
+        flags = self._flags(False, crc, strict_crc, materialize_bytes)
+        with self._lock:
+            ix = self.index_device(d_all[:nbytes] if nbytes else d_all[:0], nbytes, sizes)
+            if host is None:
+                host = d_all[:nbytes].cpu().numpy()
+            if ix.fallback:
+                from tfr_reader.cython import indexer as native  # noqa: PLC0415
+
+                parts, base = [], 0
+                for sz in sizes.tolist():
+                    parts.append(native.index_buffer(host[base : base + sz])[:, :2] + np.uint64(base))
+                    base += sz
+                se = np.concatenate(parts) if parts else np.zeros((0, 2), np.uint64)
+                st = np.ascontiguousarray(se[:, 0], np.uint64)
+                en = np.ascontiguousarray(se[:, 1], np.uint64)
+                d_st = torch.from_numpy(st.view(np.int64)).to(dev)
+                d_en = torch.from_numpy(en.view(np.int64)).to(dev)
+                tiled = False
+            else:
+                st = ix.start.cpu().numpy().view(np.uint64)
+                en = ix.end.cpu().numpy().view(np.uint64)
+                d_st, d_en, tiled = ix.start, ix.end, bool(ix.tiled)
+            n = int(st.size)
+            self._seed_keys(host, st, en, flags)
+            torch.cuda.current_stream(dev).synchronize()  # the uploads above, before the context's stream reads
+            self.last_image_mode = "u32_ends" if tiled else "u64"
+            while True:
+                self.push_schema()
+                if tiled:
+                    rc = self._lib.tfrg_decode_device32(self._ctx, C.c_void_p(d_all.data_ptr()), nbytes, None,
+                                                        C.c_void_p(ix.end32.data_ptr()), ix.first_start, n, flags,
+                                                        None)
+                else:
+                    rc = self._lib.tfrg_decode_device(self._ctx, C.c_void_p(d_all.data_ptr()), nbytes,
+                                                      C.c_void_p(d_st.data_ptr()), C.c_void_p(d_en.data_ptr()), n,
+                                                      flags, None)
+                N.check(rc, "tfrg_decode_device")
+                info = self.info()
+                if info.n_miss_records == 0:
+                    break
+                if not self._learn_misses(host, info) and self._pushed == self.keys.version:
+                    raise N.NativeError("schema misses reported but no new key learned")
+            self._last_n, self._last_host = n, (host, st, False)
+            return self._fetch(host, st, en, info, False, materialize_bytes)
+
     def dense(self, specs, *, strict: bool = False, out=None, stream: int | None = None):
         """The last decode (``decode``, ``decode_device`` or ``decode_device32``) as dense torch tensors
         on this decoder's device, one ``[n, width]`` per ``tfr_reader.dense.Dense`` spec, collated by
@@ -413,6 +522,23 @@ class HipDecoder:
         r.slot_kind = list(self.keys.slot_kind[:ns])
         r.info = info
         return r
+
+
+class DeviceIndex:
+    """``HipDecoder.index_device``'s result: ``n`` records, their ``start`` / ``end`` (int64 tensors
+    holding the u64 offsets) and ``end32`` (int32 tensors holding the u32 ends) on the device,
+    ``piece_records`` per piece, and the summary of tfrg_index_info."""
+
+    def __init__(self, info, start, end, end32, piece_records) -> None:
+        self.n = int(info.n_records)
+        self.start, self.end, self.end32 = start, end, end32
+        self.piece_records = piece_records
+        self.fallback = int(info.fallback)
+        self.tiled = int(info.tiled)
+        self.first_start = int(info.first_start)
+        self.n_chunks = int(info.n_chunks)
+        self.repaired_chunks = int(info.repaired_chunks)
+        self.repair_rounds = int(info.repair_rounds)
 
 
 class BatchResult:

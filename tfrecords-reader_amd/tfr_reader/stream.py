@@ -45,7 +45,7 @@ class StreamDecoder:
 
     def __init__(self, device: int = 0, batch_bytes: int = 256 << 20, copy_threads: int = 8,
                  spec_varint: bool = False, materialize_bytes: bool = True, crc: bool = True,
-                 copy_results: bool = True, devices=None) -> None:
+                 copy_results: bool = True, devices=None, device_index: bool = False) -> None:
         from tfr_reader import shard
 
         self._lib = N.lib()
@@ -55,9 +55,12 @@ class StreamDecoder:
         for d in devs:
             h = C.c_void_p()
             N.check(self._lib.tfrg_stream_create(d, batch_bytes, copy_threads, C.byref(h)), "tfrg_stream_create")
+            if device_index:  # the framing index of every batch on the device (tfrg_index_device)
+                N.check(self._lib.tfrg_stream_set_device_index(h, 1), "tfrg_stream_set_device_index")
             decs = [hip.HipDecoder.wrap(self._lib.tfrg_stream_ctx(h, k), d, self.keys, spec_varint) for k in (0, 1)]
             self._lanes.append((h, decs))
         self.devices = devs
+        self.device_index = bool(device_index)
         self._s = self._lanes[0][0]
         self.dec = self._lanes[0][1]
         self.batch_bytes = batch_bytes

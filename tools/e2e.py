@@ -43,6 +43,40 @@ def write_dir(d: Path, config: str, n_files: int) -> list[str]:
     return paths
 
 
+def alternate(paths, a) -> dict:
+    """a.alternate timed passes per index mode, host and device alternating: per mode the walls (s), the
+    summed index stage (worker_ms[1]) and all four stages of every pass, and whether every device pass
+    beat every host pass on wall and index stage (the only ground for calling it faster). With the
+    device index the bytes' H2D is part of the index stage (the index waits for it) and no longer of
+    the H2D + decode stage: compare the two stages' sum across modes."""
+    sds = {m: stream.StreamDecoder(0, batch_bytes=a.batch_mib << 20, copy_threads=8, copy_results=a.copy,
+                                   device_index=(m == "device")) for m in ("host", "device")}
+    res = {m: {"wall_s": [], "index_ms": [], "stage_ms": [], "records": 0} for m in sds}
+    for sd in sds.values():  # warm-up: contexts, keys, pinned buffers, index scratch
+        for _ in range(2):
+            for _b in sd.batches(paths):
+                pass
+    for _ in range(a.alternate):
+        for m, sd in sds.items():
+            t0 = time.perf_counter()
+            ms = np.zeros(4)
+            n = 0
+            for b in sd.batches(paths):
+                assert not b.result.status.any()
+                ms += np.array(b.stage_ms)
+                n += len(b.result)
+            res[m]["wall_s"].append(round(time.perf_counter() - t0, 4))
+            res[m]["index_ms"].append(round(float(ms[1]), 2))
+            res[m]["stage_ms"].append(np.round(ms, 2).tolist())  # read+copy, index, H2D + decode, D2H
+            res[m]["records"] = n
+    for sd in sds.values():
+        sd.close()
+    assert res["host"]["records"] == res["device"]["records"]
+    res["device_faster_every_run"] = bool(max(res["device"]["wall_s"]) < min(res["host"]["wall_s"]) and
+                                          max(res["device"]["index_ms"]) < min(res["host"]["index_ms"]))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c1", choices=["c1", "c2", "c3"])
@@ -54,12 +88,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--copy", action="store_true", help="copy each batch's columns out of the pinned buffers")
     ap.add_argument("--passes", type=int, default=7, help="timed passes over the directory (median reported)")
+    ap.add_argument("--device-index", action="store_true",
+                    help="build every batch's framing index on the device (StreamDecoder(device_index=True))")
+    ap.add_argument("--alternate", type=int, default=0, metavar="N",
+                    help="after the report: N timed passes of each index mode (host, device), alternating in this "
+                         "process over the same directory; their walls and index stage times are reported side by side")
     a = ap.parse_args()
     n_files = a.files or {"c1": 16, "c2": 32, "c3": 16}[a.config]
     with tempfile.TemporaryDirectory(dir="/tmp") as td:
         paths = write_dir(Path(td), a.config, n_files)
         file_bytes = sum(Path(p).stat().st_size for p in paths)
-        sd = stream.StreamDecoder(0, batch_bytes=a.batch_mib << 20, copy_threads=8, copy_results=a.copy)
+        sd = stream.StreamDecoder(0, batch_bytes=a.batch_mib << 20, copy_threads=8, copy_results=a.copy,
+                                  device_index=a.device_index)
         # warm-up pass over the whole directory, not timed: device contexts, key learning, and the
         # pinned result buffers of both slots grown to full batches (steady state)
         for _ in range(2):  # (the first pass learns the keys: its first batch's results are partial)
@@ -98,6 +138,7 @@ def main():
         py_s = time.perf_counter() - t1
         del feats, last
         sd.close()
+        alt = alternate(paths, a) if a.alternate > 0 else None
     out = {
         "config": a.config,
         "files": n_files,
@@ -115,6 +156,8 @@ def main():
         "python_features": {"records": k, "values": nv, "s": round(py_s, 4),
                             "records_per_s": round(k / py_s, 1)},
         "copy_results": a.copy,
+        "device_index": bool(a.device_index),
+        **({"alternate": alt} if alt else {}),
         "note": "median of the timed passes (wall_s; worker_ms of that pass), files on disk in the warm page cache -> every value in host memory: numpy "
                 "columns over the stream's pinned result buffers (copied out with --copy); bytes_list payloads "
                 "gathered on the device and copied back",
