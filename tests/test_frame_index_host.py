@@ -138,7 +138,7 @@ def test_argument_errors():
     assert info.n_records == 0 and info.fallback == 0
 
 
-FUZZ_SEED = 20240  # images FUZZ_SEED .. FUZZ_SEED + 199
+FUZZ_SEED = F.FUZZ_SEED  # images FUZZ_SEED .. FUZZ_SEED + 199
 
 
 def test_random_images_are_exact_or_fall_back():
@@ -161,3 +161,105 @@ def test_random_images_are_exact_or_fall_back():
         fallbacks += fb
     assert ran >= 150
     assert fallbacks <= 10, fallbacks  # at most 5 % of the 200
+
+
+def test_random_images_packed_as_pieces():
+    """25 fuzzed images to a call: every piece but the first has neighbours and an unaligned base."""
+    imgs = F.fuzz_images()
+    assert all(F.walk_terminates(d, 4 * len(d)) for d in imgs)  # (before any host walk)
+    for g in range(0, len(imgs), F.FUZZ_PACK):
+        pack = imgs[g : g + F.FUZZ_PACK]
+        sizes = [len(b) for b in pack]
+        assert any(sum(sizes[:i]) % 64 for i in range(1, len(sizes)))
+        for chunk in CHUNKS:
+            info = _check_exact(b"".join(pack), sizes, chunk)
+            assert info.repaired_chunks > 0, (g, chunk)
+
+
+# ------------------------------------------------------------------- past the single-iteration sizes
+def _check_rows(data, sizes, chunk, host):
+    """_check_exact with the host walk's count as the cap, naming the first differing row"""
+    h_st, h_en, h_cnt = host
+    info, st, en, pr = F.chunked(data, sizes, chunk, cap=int(h_st.size))
+    shift = (chunk or 4096).bit_length() - 1
+    assert info.fallback == 0 and info.n_records == h_st.size
+    for got, want, what in ((st, h_st, "start"), (en, h_en, "end")):
+        msg = F.first_difference(got, want, h_st, shift, what)
+        assert msg is None, msg
+    assert np.array_equal(pr, h_cnt)
+    assert info.tiled == F.tiled_of(h_st, h_en)
+    return info
+
+
+def test_scale_image_coverage():
+    F.assert_scale_coverage(64)
+
+
+@pytest.mark.parametrize("chunk", (64, 0), ids=("chunk64", "default"))
+def test_scale_image(chunk):
+    c = F.scale_case()
+    info = _check_rows(c["data"], None, chunk, c["one"])
+    assert info.repaired_chunks > 0 and info.tiled == 1
+    info = _check_rows(c["data"], c["sizes"], chunk, c["cut"])
+    assert info.repaired_chunks > 0 and info.tiled == 0
+    if chunk:
+        assert info.n_chunks > F.SCALE_BLOCKS * 256
+
+
+# ------------------------------------------------------------------ records shorter than their frame
+def test_ff_run_needs_more_rows_than_bytes_over_16():
+    data = F.ff_run()
+    assert F.walk_terminates(data, 4 * len(data))
+    h_st, h_en, _ = F.host_index(data)
+    assert h_st.size == 606 > len(data) // 16 + 2  # (index_device's first cap for one piece)
+    assert (h_en - h_st == 15).sum() == 600
+    info = _check_exact(data)
+    assert info.tiled == 1 and info.repair_rounds == 2
+    assert F.chunked(data, None, 64)[0].fallback == F.FB_ROUNDS
+
+
+@pytest.mark.parametrize("name", sorted(F.SHORT_SEEKS))
+def test_short_forward_seeks(name):
+    data = F.length_edge(F.SHORT_SEEKS[name])
+    assert F.walk_terminates(data, 64)
+    h_st, h_en, _ = F.host_index(data)
+    assert int(h_en[3] - h_st[3]) == {"seek12": 12, "seek10": 10, "seek1": 1}[name]
+    for chunk in CHUNKS:
+        _check_exact(data, None, chunk)
+
+
+# ---------------------------------------------------------------- zero-CRC images with zero bytes
+@pytest.mark.parametrize("chunk", CHUNKS)
+@pytest.mark.parametrize("kind", ("zeros", "zeros90", "lists"))
+def test_zero_crc_images_with_zero_runs(kind, chunk):
+    fallbacks = 0
+    for data in F.zero_images(kind, chunk):
+        assert F.walk_terminates(data, 4 * len(data))
+        assert 40 * chunk <= len(data) < 43 * chunk + 16
+        info, *_ = F.chunked(data, None, chunk)
+        if info.fallback:
+            assert info.fallback == F.FB_ROUNDS
+            fallbacks += 1
+        else:
+            _check_exact(data, None, chunk)
+    assert fallbacks == F.ZERO_FALLBACKS[kind, chunk]
+    if kind == "lists":
+        assert fallbacks == 0
+    elif kind == "zeros":
+        assert 0 < fallbacks < F.ZERO_IMAGES  # both outcomes
+
+
+# ------------------------------------------------------------------- two proposals to one chunk
+@pytest.mark.parametrize("low_first", (True, False))
+def test_the_lowest_of_two_proposals_is_kept(low_first):
+    """F.two_proposals: the chunks before an entry-less chunk propose its true entry and a false one
+    8 bytes on. The lower one is kept whichever chunk proposes it, and saves a round; the false one
+    alone costs the repair that no proposal costs."""
+    both = (0, 8) if low_first else (8, 0)
+    want = {both: (1, 1), (0, None): (1, 1), (None, 0): (1, 1),
+            (8, None): (2, 2), (None, 8): (2, 2), (None, None): (2, 2)}
+    for offs, counters in want.items():
+        data = F.two_proposals(*offs)
+        assert F.walk_terminates(data, 64)
+        info = _check_exact(data, None, 256)
+        assert (info.repaired_chunks, info.repair_rounds) == counters, offs

@@ -502,7 +502,7 @@ class HipDecoder:
         r.verdict = np.empty(n, np.uint8)
         r.order = np.empty((ns, n), np.uint16)
         r.row_splits = np.empty((ns, n + 1), np.uint32)
-        r.slot_base = np.empty(max(ns, 1), np.uint64)
+        r.slot_base = np.zeros(max(ns, 1), np.uint64)  # (no slot: the one element is not fetched)
         r.i64 = np.empty(kt[3], np.int64)
         r.f32 = np.empty(kt[2], np.uint32)
         r.bytes_off = np.empty(kt[1], np.uint32)
