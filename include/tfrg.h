@@ -380,6 +380,27 @@ typedef struct tfrg_dense_spec {
 int tfrg_result_dense(tfrg_ctx* ctx, const tfrg_dense_spec* specs, uint32_t n_specs, uint32_t* d_stats,
                       void* consumer_stream);
 
+/* Row-selected dense tensors: the same outputs for a list of records, a shuffled, sampled or filtered
+ * minibatch of the last result. Outputs are [m][width], lengths [m]; output row k < m is record
+ * g = d_rows[k] - row0 and holds exactly what tfrg_result_dense writes for row g. d_rows is a device
+ * array of m int32 (TFRG_ROWS_I32) or int64 (TFRG_ROWS_I64) entries, ready on consumer_stream. An
+ * entry with g outside [0, n) -- negative, INT64_MIN and INT64_MAX included -- is skipped: row k of
+ * the outputs and lengths[k] are left as they were, no column is read for it, it counts in no d_stats
+ * counter and adds 1 to d_skipped[spec] (device, [n_specs] u32, or NULL). d_stats and d_skipped are
+ * zeroed by the call on the stream; lengths and d_stats are per output row written, so a record
+ * drawn twice counts twice. row0 lets several contexts that hold consecutive runs of a row space
+ * take one global row list: each writes the rows that are its own.
+ * Confirmation of an optimistic or hinted decode (the only host synchronisation, once per decode),
+ * stream order, any number of calls per decode and the full view afterwards are as for
+ * tfrg_result_dense. m == 0 launches nothing; with n == 0 every row is skipped.
+ * TFRG_E_ARG (text in tfrg_last_error): everything tfrg_result_dense refuses, a NULL d_rows with
+ * m > 0, an unknown rows_dtype, m >= 2^31. */
+#define TFRG_ROWS_I32 0
+#define TFRG_ROWS_I64 1
+int tfrg_result_dense_rows(tfrg_ctx* ctx, const tfrg_dense_spec* specs, uint32_t n_specs, const void* d_rows,
+                           uint32_t rows_dtype, uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped,
+                           void* consumer_stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Double-buffered host -> HBM decode stream (replaces reader.py:212-247's per-record ThreadPool
  * read+decode for whole-dataset reads). Two slots, each with a pinned staging buffer of batch_bytes,

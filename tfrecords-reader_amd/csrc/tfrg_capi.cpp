@@ -1108,10 +1108,18 @@ int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
   return 0;
 }
 
-int tfrg_result_dense(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_specs, uint32_t* d_stats,
-                      void* consumer_stream) {
-  auto bad = [](const std::string& why) {
-    set_error("tfrg_result_dense: " + why);
+// The row list of tfrg_result_dense_rows (d_rows null: tfrg_result_dense, every record in order)
+struct DenseRows {
+  const void* d_rows = nullptr;
+  uint32_t dtype = 0, m = 0;
+  int64_t row0 = 0;
+  uint32_t* d_skipped = nullptr;
+};
+
+static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_specs,
+                        const DenseRows& rows, uint32_t* d_stats, void* consumer_stream) {
+  auto bad = [fn](const std::string& why) {
+    set_error(std::string(fn) + ": " + why);
     return TFRG_E_ARG;
   };
   if (!c) return bad("no context");
@@ -1136,10 +1144,25 @@ int tfrg_result_dense(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_spec
     if (!s.out) return bad(at + "out is NULL");
     if (s.reserved) return bad(at + "reserved must be 0");
   }
-  if (c->n == 0) return 0;
+  if (by_rows) {
+    if (rows.dtype != TFRG_ROWS_I32 && rows.dtype != TFRG_ROWS_I64)
+      return bad("rows_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(rows.dtype));
+    if (rows.m >= 0x80000000u) return bad("m must be below 2^31");
+    if (rows.m && !rows.d_rows) return bad("d_rows is NULL");
+  }
+  if (!by_rows && c->n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   if (const int rc = confirm_pending(c)) return rc;
+  // the rows of every output
+  const uint32_t out_rows = by_rows ? rows.m : c->n;
   DenseArgs a{};
+  if (by_rows) {
+    a.rows = rows.d_rows;
+    a.rows64 = rows.dtype == TFRG_ROWS_I64;
+    a.m = rows.m;
+    a.row0 = rows.row0;
+    a.skipped = rows.d_skipped;
+  }
   a.rs = c->rs.as<uint32_t>();
   a.slot_base = c->slot_base.as<uint64_t>();
   // (k_dense reads element 0 of a value array for a record without a value, and drops it: an array
@@ -1181,7 +1204,7 @@ int tfrg_result_dense(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_spec
     d.const_len = kDenseNoLen;  // (as implicit_len_runs: the column is not stored, the shapes' length holds)
     if (const_len && s.dtype == TFRG_DENSE_U8) d.const_len = s.slot < c->const_len.size() ? c->const_len[s.slot] : 0u;
     const uint64_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
-    const uint64_t total = (uint64_t)c->n * s.width * isz;
+    const uint64_t total = (uint64_t)out_rows * s.width * isz;
     // 16-byte units, or single elements where the output's base is not 16-byte aligned
     const uint64_t work = ((uintptr_t)s.out & 15u) ? total / isz : (total >> 4) + 16;
     d.blk0 = blocks;
@@ -1196,13 +1219,35 @@ int tfrg_result_dense(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_spec
     HIP_TRY(hipEventRecord(c->dense_ev[0], cs));
     HIP_TRY(hipStreamWaitEvent(st, c->dense_ev[0], 0));
   }
-  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
-  HIP_TRY(launch_dense(a, blocks, st));
+  // (counters that lie back to back, stats first, are zeroed by one memset: one launch less per step)
+  const bool one_memset = by_rows && c->n && d_stats && rows.d_skipped == d_stats + 4 * (size_t)n_specs;
+  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * (one_memset ? 20 : 16), st));
+  // (a row list over an empty result: no record to read, every row is skipped)
+  if (by_rows && rows.d_skipped && !one_memset)
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rows.d_skipped), c->n ? 0 : (int)rows.m, n_specs, st));
+  if (out_rows && c->n) HIP_TRY(launch_dense(a, blocks, st));
   if (cs != st) {
     HIP_TRY(hipEventRecord(c->dense_ev[1], st));
     HIP_TRY(hipStreamWaitEvent(cs, c->dense_ev[1], 0));
   }
   return 0;
+}
+
+int tfrg_result_dense(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_specs, uint32_t* d_stats,
+                      void* consumer_stream) {
+  return result_dense("tfrg_result_dense", false, c, specs, n_specs, DenseRows{}, d_stats, consumer_stream);
+}
+
+int tfrg_result_dense_rows(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_specs, const void* d_rows,
+                           uint32_t rows_dtype, uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped,
+                           void* consumer_stream) {
+  DenseRows rows;
+  rows.d_rows = d_rows;
+  rows.dtype = rows_dtype;
+  rows.m = m;
+  rows.row0 = row0;
+  rows.d_skipped = d_skipped;
+  return result_dense("tfrg_result_dense_rows", true, c, specs, n_specs, rows, d_stats, consumer_stream);
 }
 
 int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {

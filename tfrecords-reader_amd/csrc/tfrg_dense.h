@@ -1,5 +1,6 @@
-// tfrg_dense.h — arguments of k_dense (tfrg_dense.hip), the collate kernel behind tfrg_result_dense:
-// ragged result columns -> fixed-shape [n][width] outputs. Shared with tfrg_capi.cpp only.
+// tfrg_dense.h — arguments of k_dense (tfrg_dense.hip), the collate kernel behind tfrg_result_dense
+// and tfrg_result_dense_rows: ragged result columns -> fixed-shape [n][width] outputs, or [m][width]
+// outputs whose row k is record rows[k] - row0. Shared with tfrg_capi.cpp only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -17,8 +18,8 @@ constexpr uint32_t kDenseChunk = 1024;
 // One requested output. Workgroups [blk0, blk0 + nblk) of the launch work inside it, workgroup b on
 // chunks b - blk0, b - blk0 + nblk, ... of its flat row-major bytes.
 struct DenseSpec {
-  void* out;           // [n][width] of the dtype
-  int32_t* lengths;    // [n] or null
+  void* out;           // [n][width] of the dtype ([m][width] with a row list)
+  int32_t* lengths;    // [n] ([m]) or null
   uint64_t fill;       // raw low bits of the pad value
   uint32_t slot;
   uint32_t dtype;      // DenseType
@@ -40,6 +41,13 @@ struct DenseArgs {
   const uint8_t* in;           // the batch (views) or the materialized byte column
   const uint32_t* info;        // the decode's info words (kInfoPlacedLo / Hi read on the device)
   uint32_t* stats;             // [n_specs][4] or null
+  // the row list (k_dense_rows only): output row k < m is record rows[k] - row0 where that is
+  // in [0, n), and is left unwritten and counted in skipped[spec] where it is not
+  const void* rows;            // [m] int32, or int64 with rows64
+  uint32_t* skipped;           // [n_specs] or null
+  int64_t row0;
+  uint32_t m;
+  uint32_t rows64;
   uint32_t in_bound;           // readable bytes of `in` (a multiple of 4): reads past it give 0
   uint32_t n;
   uint32_t n_specs;

@@ -17,6 +17,14 @@
 // single value), the bytes_len column of a slot whose length is constant (DenseSpec::const_len),
 // status / aux / verdict / order. The input of the bytes views is read through a buffer resource
 // bounded to the batch: a view that runs past it reads zeros.
+//
+// k_dense_rows (tfrg_result_dense_rows) is the same kernel behind one level of indirection:
+// the output has m rows, and row k is record g = rows[k] - row0 (rec_of). The row list is a per-lane
+// vector load and one phase of its own, ahead of the row splits. A k whose g is not in [0, n) is a
+// skipped row: nothing indexed by g is loaded for it (it reads record 0, whose columns every
+// non-empty result has, as a record without a value reads element 0), none of its output elements
+// and no lengths[k] are stored, and it counts in skipped[spec] alone. A 16-byte unit with a skipped
+// row in it stores the elements of its other rows one by one; every other unit keeps the one store.
 #include <hip/hip_runtime.h>
 
 #include "tfrg_dense.h"
@@ -29,9 +37,9 @@ namespace {
 typedef uint32_t dn_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint64_t dn_u64x2 __attribute__((ext_vector_type(2)));
 
-// per-lane counters of the rows whose first element the lane wrote
+// per-lane counters of the rows whose first element the lane wrote (skip: or left out)
 struct Tally {
-  uint32_t trunc = 0, pad = 0, zero = 0, multi = 0;
+  uint32_t trunc = 0, pad = 0, zero = 0, multi = 0, skip = 0;
 };
 
 // The kernel argument is read in place, in the constant address space (scalar loads): a by-value
@@ -47,9 +55,39 @@ struct Sp {
   uint64_t base;       // slot_base[slot]
   uint32_t W;
   __amdgpu_buffer_rsrc_t in;
+  // the row list (ROWS only): entry k is the dword at rows + (k << rsh), and for int64 entries the
+  // dword rhi bytes after it (rhi 0: an int32 entry, whose second load repeats the first)
+  const uint8_t* rows;
+  int64_t row0;
+  uint32_t rsh, rhi;
 };
 
-// first value index and value count of record r
+// The record of output row r. Without a row list it is r. With one, r < m and the record is
+// rows[r] - row0; ok: that is in [0, n) (compared before the subtraction, whose unsigned result is
+// then the true difference: no entry, INT64_MIN and INT64_MAX included, wraps into range).
+struct Rec {
+  uint32_t g;
+  uint32_t ok;  // 0 / 1, in a vector register: a lane mask per row in flight would cost two scalar ones
+};
+
+template <bool ROWS>
+__device__ __forceinline__ Rec rec_of(const Sp& x, uint32_t r) {
+  if constexpr (!ROWS) {
+    return Rec{r, 1u};
+  } else {
+    const uint8_t* const p = x.rows + ((uint64_t)r << x.rsh);
+    const uint32_t lo = *reinterpret_cast<const uint32_t*>(p);
+    const uint32_t hi = *reinterpret_cast<const uint32_t*>(p + x.rhi);
+    const int64_t v = x.rhi ? (int64_t)(((uint64_t)hi << 32) | lo) : (int64_t)(int32_t)lo;
+    const uint64_t d = (uint64_t)v - (uint64_t)x.row0;
+    const bool ok = v >= x.row0 && d < (uint64_t)x.a->n;
+    uint32_t okv = ok ? 1u : 0u;
+    asm("" : "+v"(okv));  // (kept as a value: see Rec)
+    return Rec{ok ? (uint32_t)d : 0u, okv};
+  }
+}
+
+// first value index and value count of record g (g < n)
 __device__ __forceinline__ void row_of(const Sp& x, uint32_t r, uint64_t& e, uint32_t& c) {
   if (!x.rs) {
     e = x.base + r;
@@ -61,11 +99,28 @@ __device__ __forceinline__ void row_of(const Sp& x, uint32_t r, uint64_t& e, uin
   c = hi - lo;
 }
 
-__device__ __forceinline__ void note_row(const Sp& x, Tally& t, uint32_t r, uint32_t count, uint32_t len) {
-  if (x.s->lengths) x.s->lengths[r] = (int32_t)len;
-  t.trunc += len > x.W;
-  t.pad += len < x.W;
-  t.zero += count == 0;
+// (a skipped row is a record without a value to everything that loads)
+__device__ __forceinline__ void row_of(const Sp& x, const Rec& q, uint64_t& e, uint32_t& c) {
+  row_of(x, q.g, e, c);
+  c = q.ok ? c : 0u;
+}
+
+template <bool ROWS>
+__device__ __forceinline__ void note_row(const Sp& x, Tally& t, uint32_t r, uint32_t okv, uint32_t count, uint32_t len) {
+  if constexpr (ROWS) {
+    // (branch-free but for the store: a skipped row counts in `skip` alone)
+    const bool ok = okv != 0u;
+    if (ok && x.s->lengths) x.s->lengths[r] = (int32_t)len;
+    t.trunc += ok && len > x.W;
+    t.pad += ok && len < x.W;
+    t.zero += ok && count == 0;
+    t.skip += !ok;
+  } else {
+    if (x.s->lengths) x.s->lengths[r] = (int32_t)len;
+    t.trunc += len > x.W;
+    t.pad += len < x.W;
+    t.zero += count == 0;
+  }
 }
 
 // ------------------------------------------------------------------ int64_list / float_list slots
@@ -89,22 +144,53 @@ __device__ __forceinline__ typename ValT<DT>::type value_at(const Sp& x, uint64_
   return ok ? v : (T)x.s->fill;
 }
 
-// K consecutive elements from (r, j) on; r < n for each of them (the caller's range is inside the output)
-template <uint32_t DT, int K>
-__device__ __forceinline__ void values_from(const Sp& x, Tally& t, uint32_t r, uint32_t j,
-                                            typename ValT<DT>::type* v) {
-  uint64_t e;
-  uint32_t c;
-  row_of(x, r, e, c);
+// K consecutive elements from (r, j) on; r < n for each of them (the caller's range is inside the
+// output). Returns the mask of the elements whose row is not skipped.
+template <uint32_t DT, int K, bool ROWS>
+__device__ __forceinline__ uint32_t values_from(const Sp& x, Tally& t, uint32_t r, uint32_t j,
+                                                typename ValT<DT>::type* v) {
+  if constexpr (!ROWS) {
+    uint64_t e;
+    uint32_t c;
+    row_of(x, r, e, c);
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    if (j == 0) note_row(x, t, r, c, c);
-    v[k] = value_at<DT>(x, e, c, j);
-    if (++j == x.W) {
-      j = 0;
-      ++r;
-      if (k + 1 < K) row_of(x, r, e, c);
+    for (int k = 0; k < K; ++k) {
+      if (j == 0) note_row<false>(x, t, r, 1u, c, c);
+      v[k] = value_at<DT>(x, e, c, j);
+      if (++j == x.W) {
+        j = 0;
+        ++r;
+        if (k + 1 < K) row_of(x, r, e, c);
+      }
     }
+    return (1u << K) - 1u;
+  } else {
+    // in phases: the elements' row-list entries, their row splits, their values, then the lengths
+    // and counters (an element that shares its row with the one before it repeats that one's loads)
+    uint32_t rr[K], jj[K], c[K];
+    uint64_t e[K];
+    Rec q[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      rr[k] = r;
+      jj[k] = j;
+      const bool wrap = ++j == x.W;
+      r += wrap;
+      j = wrap ? 0u : j;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) q[k] = rec_of<true>(x, rr[k]);
+#pragma unroll
+    for (int k = 0; k < K; ++k) row_of(x, q[k], e[k], c[k]);
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = value_at<DT>(x, e[k], c[k], jj[k]);
+    uint32_t okm = 0u;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      okm |= q[k].ok << k;
+      if (jj[k] == 0) note_row<true>(x, t, rr[k], q[k].ok, c[k], c[k]);
+    }
+    return okm;
   }
 }
 
@@ -114,10 +200,10 @@ struct BRow {
 };
 
 // (branch-free per lane: a record without an element reads element 0's view and drops it)
-__device__ __forceinline__ BRow brow_of(const Sp& x, uint32_t r) {
+__device__ __forceinline__ BRow brow_of(const Sp& x, const Rec& q) {
   uint64_t e;
   uint32_t c;
-  row_of(x, r, e, c);
+  row_of(x, q, e, c);
   const uint64_t es = c ? e : 0ull;
   BRow b{0u, 0u, c};
   if (x.a->b_off64) {
@@ -133,9 +219,17 @@ __device__ __forceinline__ BRow brow_of(const Sp& x, uint32_t r) {
   return b;
 }
 
-__device__ __forceinline__ void note_brow(const Sp& x, Tally& t, uint32_t r, const BRow& b) {
-  note_row(x, t, r, b.cnt, b.len);
-  t.multi += b.cnt > 1u;
+template <bool ROWS>
+__device__ __forceinline__ BRow brow_of(const Sp& x, uint32_t r, uint32_t& ok) {
+  const Rec q = rec_of<ROWS>(x, r);
+  ok = q.ok;
+  return brow_of(x, q);
+}
+
+template <bool ROWS>
+__device__ __forceinline__ void note_brow(const Sp& x, Tally& t, uint32_t r, uint32_t ok, const BRow& b) {
+  note_row<ROWS>(x, t, r, ok, b.cnt, b.len);
+  t.multi += b.cnt > 1u;  // (a skipped row's count is 0)
 }
 
 // byte j of the row's element (j < len), zero past the input
@@ -147,13 +241,15 @@ __device__ __forceinline__ uint32_t in_byte(const Sp& x, const BRow& b, uint32_t
 
 // K consecutive output dwords from byte j (a multiple of 4) of row r on, for widths that are a
 // multiple of 4: each dword lies inside one row and is built from two aligned input dwords. In
-// phases -- the rows' views, then every input dword, then the lengths and counters -- so that the
-// loads of a phase are in flight together; a dword with nothing to read (padding, or a view past
-// the input) loads from past the buffer's bound, which gives zeros without a memory access.
-template <int K>
-__device__ __forceinline__ void u8_dwords4(const Sp& x, Tally& t, uint32_t r, uint32_t j, uint32_t* w) {
+// phases -- (the rows' entries in the row list,) the rows' views, then every input dword, then the
+// lengths and counters -- so that the loads of a phase are in flight together; a dword with nothing
+// to read (padding, a skipped row, or a view past the input) loads from past the buffer's bound,
+// which gives zeros without a memory access. Returns the mask of the dwords whose row is not skipped.
+template <int K, bool ROWS>
+__device__ __forceinline__ uint32_t u8_dwords4(const Sp& x, Tally& t, uint32_t r, uint32_t j, uint32_t* w) {
   uint32_t rr[K], jj[K];
   BRow bb[K];
+  Rec q[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     rr[k] = r;
@@ -164,7 +260,9 @@ __device__ __forceinline__ void u8_dwords4(const Sp& x, Tally& t, uint32_t r, ui
     j = wrap ? 0u : j;
   }
 #pragma unroll
-  for (int k = 0; k < K; ++k) bb[k] = brow_of(x, rr[k]);
+  for (int k = 0; k < K; ++k) q[k] = rec_of<ROWS>(x, rr[k]);
+#pragma unroll
+  for (int k = 0; k < K; ++k) bb[k] = brow_of(x, q[k]);
   uint32_t d0[K], d1[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -182,34 +280,57 @@ __device__ __forceinline__ void u8_dwords4(const Sp& x, Tally& t, uint32_t r, ui
     const uint32_t d = __builtin_amdgcn_alignbyte(d1[k], d0[k], (bb[k].off + jj[k]) & 3u);
     w[k] = (d & m) | (fill & ~m);
   }
+  uint32_t okm = 0u;
 #pragma unroll
-  for (int k = 0; k < K; ++k)
-    if (jj[k] == 0) note_brow(x, t, rr[k], bb[k]);
+  for (int k = 0; k < K; ++k) {
+    okm |= q[k].ok << k;
+    if (jj[k] == 0) note_brow<ROWS>(x, t, rr[k], q[k].ok, bb[k]);
+  }
+  return okm;
 }
 
 // The output dword at bytes j .. j + 3 of row r for any other width: byte by byte over row ends.
-// Advances (r, j, b) past it; `more`: the output goes on after it (the next row exists).
-__device__ __forceinline__ uint32_t u8_dword(const Sp& x, Tally& t, uint32_t& r, uint32_t& j, BRow& b, bool more) {
+// Advances (r, j, b, ok) past it; `more`: the output goes on after it (the next row exists). Bit k of
+// `okm` is set where byte k's row is not skipped.
+template <bool ROWS>
+__device__ __forceinline__ uint32_t u8_dword(const Sp& x, Tally& t, uint32_t& r, uint32_t& j, BRow& b, uint32_t& ok,
+                                             bool more, uint32_t& okm) {
   const uint32_t fill = (uint32_t)x.s->fill & 0xffu;
   uint32_t w = 0u;
+  okm = 0u;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    if (j == 0) note_brow(x, t, r, b);
+    if (j == 0) note_brow<ROWS>(x, t, r, ok, b);
     w |= (j < b.len ? in_byte(x, b, j) : fill) << (8 * k);
+    okm |= ok << k;
     if (++j == x.W) {
       j = 0;
       ++r;
-      if (more || k < 3) b = brow_of(x, r);
+      if (more || k < 3) b = brow_of<ROWS>(x, r, ok);
     }
   }
   return w;
 }
 
+// ------------------------------------------------------------------ stores of a unit with skipped rows
+// the bytes of dword w at p whose bit in okm (4 bits) is set
+template <bool NT>
+__device__ __forceinline__ void st_bytes(uint8_t* p, uint32_t w, uint32_t okm) {
+  if (okm == 0xfu) {
+    st_nt<NT>(reinterpret_cast<uint32_t*>(p), w);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if ((okm >> k) & 1u) p[k] = (uint8_t)(w >> (8 * k));
+}
+
 // ------------------------------------------------------------------ one workgroup's share of a spec
-template <uint32_t DT, bool NT>
+template <uint32_t DT, bool NT, bool ROWS>
 __device__ __forceinline__ void dense_spec(const Sp& x, Tally& t, uint32_t wg) {
   constexpr uint32_t isz = DT == kDenseI64 ? 8u : DT == kDenseU8 ? 1u : 4u;
-  const uint32_t n = x.a->n, W = x.W, nblk = x.s->nblk, tid = threadIdx.x;
+  // (n: the output's rows)
+  const uint32_t n = ROWS ? x.a->m : x.a->n, W = x.W, nblk = x.s->nblk, tid = threadIdx.x;
   const uint32_t rowb = W * isz;                  // <= 32 KiB
   const uint64_t total = (uint64_t)n * rowb;      // bytes of the output
   uint8_t* const out = static_cast<uint8_t*>(x.s->out);
@@ -232,38 +353,58 @@ __device__ __forceinline__ void dense_spec(const Sp& x, Tally& t, uint32_t wg) {
           uint32_t r = (uint32_t)(r0 + q), j = lo - q * rowb;
           uint8_t* const p = out + ((u0 + lu) << 4);
           if constexpr (DT == kDenseU8) {
-            uint32_t v[4];
+            uint32_t v[4], okm[4];
             if ((W & 3u) == 0u) {
-              u8_dwords4<4>(x, t, r, j, v);
+              const uint32_t o4 = u8_dwords4<4, ROWS>(x, t, r, j, v);
+#pragma unroll
+              for (int k = 0; k < 4; ++k) okm[k] = ((o4 >> k) & 1u) ? 0xfu : 0u;
             } else {
-              BRow b = brow_of(x, r);
-              v[0] = u8_dword(x, t, r, j, b, true);
-              v[1] = u8_dword(x, t, r, j, b, true);
-              v[2] = u8_dword(x, t, r, j, b, true);
-              v[3] = u8_dword(x, t, r, j, b, false);
+              uint32_t ok;
+              BRow b = brow_of<ROWS>(x, r, ok);
+              v[0] = u8_dword<ROWS>(x, t, r, j, b, ok, true, okm[0]);
+              v[1] = u8_dword<ROWS>(x, t, r, j, b, ok, true, okm[1]);
+              v[2] = u8_dword<ROWS>(x, t, r, j, b, ok, true, okm[2]);
+              v[3] = u8_dword<ROWS>(x, t, r, j, b, ok, false, okm[3]);
             }
-            dn_u32x4 o;
-            o.x = v[0];
-            o.y = v[1];
-            o.z = v[2];
-            o.w = v[3];
-            st_nt<NT>(reinterpret_cast<dn_u32x4*>(p), o);
+            if (!ROWS || (okm[0] & okm[1] & okm[2] & okm[3]) == 0xfu) {
+              dn_u32x4 o;
+              o.x = v[0];
+              o.y = v[1];
+              o.z = v[2];
+              o.w = v[3];
+              st_nt<NT>(reinterpret_cast<dn_u32x4*>(p), o);
+            } else {
+#pragma unroll
+              for (int k = 0; k < 4; ++k) st_bytes<NT>(p + 4 * k, v[k], okm[k]);
+            }
           } else if constexpr (DT == kDenseI64) {
             uint64_t v[2];
-            values_from<DT, 2>(x, t, r, j >> 3, v);
-            dn_u64x2 o;
-            o.x = v[0];
-            o.y = v[1];
-            st_nt<NT>(reinterpret_cast<dn_u64x2*>(p), o);
+            const uint32_t okm = values_from<DT, 2, ROWS>(x, t, r, j >> 3, v);
+            if (!ROWS || okm == 3u) {
+              dn_u64x2 o;
+              o.x = v[0];
+              o.y = v[1];
+              st_nt<NT>(reinterpret_cast<dn_u64x2*>(p), o);
+            } else {
+#pragma unroll
+              for (int k = 0; k < 2; ++k)
+                if ((okm >> k) & 1u) st_nt<NT>(reinterpret_cast<uint64_t*>(p) + k, v[k]);
+            }
           } else {
             uint32_t v[4];
-            values_from<DT, 4>(x, t, r, j >> 2, v);
-            dn_u32x4 o;
-            o.x = v[0];
-            o.y = v[1];
-            o.z = v[2];
-            o.w = v[3];
-            st_nt<NT>(reinterpret_cast<dn_u32x4*>(p), o);
+            const uint32_t okm = values_from<DT, 4, ROWS>(x, t, r, j >> 2, v);
+            if (!ROWS || okm == 0xfu) {
+              dn_u32x4 o;
+              o.x = v[0];
+              o.y = v[1];
+              o.z = v[2];
+              o.w = v[3];
+              st_nt<NT>(reinterpret_cast<dn_u32x4*>(p), o);
+            } else {
+#pragma unroll
+              for (int k = 0; k < 4; ++k)
+                if ((okm >> k) & 1u) st_nt<NT>(reinterpret_cast<uint32_t*>(p) + k, v[k]);
+            }
           }
         }
       }
@@ -284,25 +425,28 @@ __device__ __forceinline__ void dense_spec(const Sp& x, Tally& t, uint32_t wg) {
       const uint64_t pos = done + (i << 2);
       const uint64_t r64 = pos / W;
       uint32_t r = (uint32_t)r64, j = (uint32_t)(pos - r64 * W);
-      uint32_t w;
+      uint32_t w, okm;
       if ((W & 3u) == 0u) {
-        u8_dwords4<1>(x, t, r, j, &w);
+        okm = u8_dwords4<1, ROWS>(x, t, r, j, &w) ? 0xfu : 0u;
       } else {
         // (every row the dword's four bytes touch is inside the output; a row after its last byte
         // exists only if the output goes on)
-        BRow b = brow_of(x, r);
-        w = u8_dword(x, t, r, j, b, pos + 4u < total);
+        uint32_t ok;
+        BRow b = brow_of<ROWS>(x, r, ok);
+        w = u8_dword<ROWS>(x, t, r, j, b, ok, pos + 4u < total, okm);
       }
-      st_nt<NT>(reinterpret_cast<uint32_t*>(out + pos), w);
+      if constexpr (ROWS) st_bytes<NT>(out + pos, w, okm);
+      else st_nt<NT>(reinterpret_cast<uint32_t*>(out + pos), w);
     }
     done += dwords << 2;
     for (uint64_t i = (uint64_t)wg * 256u + tid; done + i < total; i += (uint64_t)nblk * 256u) {
       const uint64_t pos = done + i;
       const uint64_t r64 = pos / W;
       const uint32_t r = (uint32_t)r64, j = (uint32_t)(pos - r64 * W);
-      const BRow b = brow_of(x, r);
-      if (j == 0) note_brow(x, t, r, b);
-      out[pos] = (uint8_t)(j < b.len ? in_byte(x, b, j) : ((uint32_t)x.s->fill & 0xffu));
+      uint32_t ok;
+      const BRow b = brow_of<ROWS>(x, r, ok);
+      if (j == 0) note_brow<ROWS>(x, t, r, ok, b);
+      if (ok) out[pos] = (uint8_t)(j < b.len ? in_byte(x, b, j) : ((uint32_t)x.s->fill & 0xffu));
     }
   } else {
     using T = typename ValT<DT>::type;
@@ -310,8 +454,8 @@ __device__ __forceinline__ void dense_spec(const Sp& x, Tally& t, uint32_t wg) {
     for (uint64_t i = e0 + (uint64_t)wg * 256u + tid; i < elems; i += (uint64_t)nblk * 256u) {
       const uint64_t r64 = i / W;
       T v;
-      values_from<DT, 1>(x, t, (uint32_t)r64, (uint32_t)(i - r64 * W), &v);
-      st_nt<NT>(reinterpret_cast<T*>(out) + i, v);
+      if (values_from<DT, 1, ROWS>(x, t, (uint32_t)r64, (uint32_t)(i - r64 * W), &v))
+        st_nt<NT>(reinterpret_cast<T*>(out) + i, v);
     }
   }
 }
@@ -322,8 +466,8 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   return v;
 }
 
-template <bool NT>
-__global__ __launch_bounds__(256) void k_dense(const DenseArgs) {
+template <bool NT, bool ROWS>
+__device__ __forceinline__ void dense_body() {
   const KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();  // (the only argument)
   // the workgroup's spec: the last one whose first block is not after this block
   uint32_t si = 0;
@@ -339,13 +483,25 @@ __global__ __launch_bounds__(256) void k_dense(const DenseArgs) {
   x.base = a->slot_base[slot];
   x.rs = (slot < 64u && ((placed >> slot) & 1ull)) ? nullptr : a->rs + (uint64_t)slot * ((uint64_t)a->n + 1u);
   x.in = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a->in), (short)0, (int)a->in_bound, 0x00020000);
+  if constexpr (ROWS) {
+    x.rows = static_cast<const uint8_t*>(a->rows);
+    x.row0 = a->row0;
+    x.rsh = a->rows64 ? 3u : 2u;
+    x.rhi = a->rows64 ? 4u : 0u;
+  }
   const uint32_t wg = blockIdx.x - s->blk0;
   Tally t;
   switch (s->dtype) {
-    case kDenseI64: dense_spec<kDenseI64, NT>(x, t, wg); break;
-    case kDenseI32: dense_spec<kDenseI32, NT>(x, t, wg); break;
-    case kDenseF32: dense_spec<kDenseF32, NT>(x, t, wg); break;
-    default: dense_spec<kDenseU8, NT>(x, t, wg); break;
+    case kDenseI64: dense_spec<kDenseI64, NT, ROWS>(x, t, wg); break;
+    case kDenseI32: dense_spec<kDenseI32, NT, ROWS>(x, t, wg); break;
+    case kDenseF32: dense_spec<kDenseF32, NT, ROWS>(x, t, wg); break;
+    default: dense_spec<kDenseU8, NT, ROWS>(x, t, wg); break;
+  }
+  if constexpr (ROWS) {
+    if (a->skipped) {
+      const uint32_t sk = wave_sum(t.skip);
+      if ((threadIdx.x & 63u) == 0u && sk) atomicAdd(a->skipped + si, sk);
+    }
   }
   uint32_t* const stats = a->stats;
   if (!stats) return;
@@ -360,12 +516,28 @@ __global__ __launch_bounds__(256) void k_dense(const DenseArgs) {
   }
 }
 
+template <bool NT>
+__global__ __launch_bounds__(256) void k_dense(const DenseArgs) {
+  dense_body<NT, false>();
+}
+
+// (behind tfrg_result_dense_rows)
+template <bool NT>
+__global__ __launch_bounds__(256) void k_dense_rows(const DenseArgs) {
+  dense_body<NT, true>();
+}
+
 }  // namespace
 
 hipError_t launch_dense(const DenseArgs& a, uint32_t blocks, hipStream_t st) {
   if (!blocks) return hipSuccess;
-  if (a.nt) hipLaunchKernelGGL(k_dense<true>, dim3(blocks), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_dense<false>, dim3(blocks), dim3(256), 0, st, a);
+  if (a.rows) {
+    if (a.nt) hipLaunchKernelGGL(k_dense_rows<true>, dim3(blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_dense_rows<false>, dim3(blocks), dim3(256), 0, st, a);
+  } else {
+    if (a.nt) hipLaunchKernelGGL(k_dense<true>, dim3(blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_dense<false>, dim3(blocks), dim3(256), 0, st, a);
+  }
   return hipGetLastError();
 }
 

@@ -114,6 +114,8 @@ DENSE_F32 = 2
 DENSE_U8 = 3
 DENSE_MAX_SPECS = 64
 DENSE_MAX_WIDTH = 4096
+ROWS_I32 = 0  # tfrg_result_dense_rows: the row list's element type (TFRG_ROWS_*)
+ROWS_I64 = 1
 
 # name -> (restype, argtypes); the exact list of exported symbols declared in include/tfrg.h
 SIGNATURES: dict[str, tuple] = {
@@ -190,6 +192,8 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_result_device": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),
     "tfrg_result_fetch": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),
     "tfrg_result_dense": (C.c_int, [C.c_void_p, C.POINTER(TfrgDenseSpec), C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tfrg_result_dense_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgDenseSpec), C.c_uint32, C.c_void_p, C.c_uint32,
+                                         C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 FLAG_PAYLOAD_ONLY = 1

@@ -11,6 +11,11 @@ with ``fill`` or truncated, in the dtype the model wants -- and
 * ``BatchResult.dense`` / ``densify`` compute the same function with numpy from fetched columns (the
   host path, and the reference the device path is tested against).
 
+Row lists: every entry point takes ``rows=``, and then output row k is record ``rows[k]`` of the
+decode -- a shuffled, sampled or filtered minibatch. On the device that is one launch per decoded
+batch over columns that stay where the decode left them (``tfrg_result_dense_rows``), so a shard is
+decoded once and ``minibatches`` draws an epoch of batches from it.
+
 Per output: ``lengths[r]`` is the record's untruncated value count (bytes: the byte length of the
 list's first element, 0 if the list is empty or absent) and ``stats`` the four counters
 ``(truncated, padded, empty, multi)``: records whose count (bytes: length) is above / below the
@@ -100,12 +105,21 @@ def check_specs(specs: Sequence[Dense]) -> list[Dense]:
 class DenseBatch(dict):
     """name -> ``[n, width]`` array (torch tensors on the decoder's device, numpy arrays on the host
     path); ``lengths[name]`` for the specs that asked for them; ``stats[name]`` the four counters
-    ``STAT_NAMES`` as a uint32 array (read back from the device on first access)."""
+    ``STAT_NAMES`` as a uint32 array (read back from the device on first access); ``skipped``: how
+    many entries of a device row list were out of range, their output rows left unwritten (read back
+    on first access too)."""
 
-    def __init__(self, values: Mapping, lengths: Mapping, stats) -> None:
+    def __init__(self, values: Mapping, lengths: Mapping, stats, skipped=0) -> None:
         super().__init__(values)
         self.lengths = dict(lengths)
         self._stats = stats  # a dict, or a function returning it
+        self._skipped = skipped  # an int, or a function returning it
+
+    @property
+    def skipped(self) -> int:
+        if callable(self._skipped):
+            self._skipped = int(self._skipped())
+        return self._skipped
 
     @property
     def stats(self) -> dict[str, np.ndarray]:
@@ -124,6 +138,23 @@ def check_strict(specs: Sequence[Dense], stats: Mapping[str, np.ndarray]) -> Non
                              f"{m} with more than one element")
 
 
+def host_rows(rows, n: int) -> np.ndarray:
+    """A host row list as a 1-D int64 array, range-checked against ``n`` records (ValueError for
+    anything but a 1-D integer sequence, IndexError naming the first index outside [0, n))."""
+    a = np.asarray(rows)
+    if a.ndim != 1:
+        raise ValueError(f"rows must be one-dimensional, not of shape {a.shape}")
+    if a.size == 0:
+        return np.zeros(0, np.int64)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"rows must be integers, not {a.dtype}")
+    bad = (a < 0) | (a >= n)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise IndexError(f"rows[{k}] = {int(a[k])} is out of range for {n} records")
+    return np.ascontiguousarray(a, np.int64)
+
+
 # ---------------------------------------------------------------------- host path (numpy)
 def find_slot(slot_key: Sequence[str | None], slot_kind: Sequence[int], key: str, kind: int) -> int | None:
     for s, (k, kd) in enumerate(zip(slot_key, slot_kind)):
@@ -136,13 +167,17 @@ def densify(specs: Sequence[Dense], *, n: int, slot_key: Sequence[str | None], s
             row_splits: np.ndarray, slot_base: np.ndarray, i64: np.ndarray, f32: np.ndarray,
             bytes_off: np.ndarray | None = None, bytes_len: np.ndarray | None = None, buf: np.ndarray | None = None,
             bytes_data: np.ndarray | None = None, bytes_offsets: np.ndarray | None = None,
-            strict: bool = False) -> DenseBatch:
+            strict: bool = False, rows=None) -> DenseBatch:
     """The dense outputs of ``specs`` from plain result columns (``BatchResult``'s: ``row_splits``
     ``[n_slots][n + 1]``, ``slot_base``, the value arrays; bytes as ``(bytes_off, bytes_len)`` views
     into ``buf``, or ``bytes_data`` / ``bytes_offsets``), record by record. A key without a slot
-    gives an all-``fill`` output (``strict``: KeyError)."""
+    gives an all-``fill`` output (``strict``: KeyError). ``rows``: output row k is record
+    ``rows[k]`` (any order, repeats allowed; IndexError for one outside [0, n)), and the lengths and
+    counters are those of the output's rows."""
     specs = check_specs(specs)
     values, lengths, stats = {}, {}, {}
+    picked = list(range(n)) if rows is None else host_rows(rows, n).tolist()
+    n = len(picked)  # (from here on: the output's rows)
     for sp in specs:
         _, kind, dt, udt = DTYPES[sp.dtype]
         W = int(sp.width)
@@ -157,8 +192,8 @@ def densify(specs: Sequence[Dense], *, n: int, slot_key: Sequence[str | None], s
         else:
             base = int(slot_base[s])
             rs = np.asarray(row_splits[s]).astype(np.int64)
-            for r in range(n):
-                lo, c = base + int(rs[r]), int(rs[r + 1] - rs[r])
+            for r, g in enumerate(picked):
+                lo, c = base + int(rs[g]), int(rs[g + 1] - rs[g])
                 if kind == 1:
                     ln = 0
                     if c:
@@ -190,14 +225,14 @@ def densify(specs: Sequence[Dense], *, n: int, slot_key: Sequence[str | None], s
     return DenseBatch(values, lengths, stats)
 
 
-def batch_dense(res, specs: Sequence[Dense], strict: bool = False) -> DenseBatch:
+def batch_dense(res, specs: Sequence[Dense], strict: bool = False, rows=None) -> DenseBatch:
     """``BatchResult.dense``: ``densify`` over a fetched result's columns."""
     if strict and res.status.any():
         res.raise_for(int(np.flatnonzero(res.status)[0]))
     return densify(specs, n=len(res), slot_key=res.slot_key, slot_kind=res.slot_kind, row_splits=res.row_splits,
                    slot_base=res.slot_base, i64=res.i64, f32=res.f32, bytes_off=res.bytes_off,
                    bytes_len=res.bytes_len, buf=res.buf, bytes_data=res.bytes_data, bytes_offsets=res.bytes_offsets,
-                   strict=strict)
+                   strict=strict, rows=rows)
 
 
 # ---------------------------------------------------------------------- device path
@@ -213,14 +248,51 @@ def resolve_slot(dec, sp: Dense) -> int | None:
     return s
 
 
-def launch(dec, items: Sequence[tuple], stats_ptr: int | None, consumer: int | None) -> None:
+def _vp(p: int | None):
+    return C.c_void_p(p) if p else None
+
+
+def launch(dec, items: Sequence[tuple], stats_ptr: int | None, consumer: int | None, rows: tuple | None = None,
+           row0: int = 0, skipped_ptr: int | None = None) -> None:
     """One ``tfrg_result_dense`` call: items are (slot, TFRG_DENSE_* id, width, fill bits, out
-    pointer, lengths pointer or None)."""
+    pointer, lengths pointer or None). ``rows``: (device pointer, m, TFRG_ROWS_* id), and the call is
+    ``tfrg_result_dense_rows`` with ``row0`` and the ``[len(items)]`` skipped counters."""
     arr = (N.TfrgDenseSpec * len(items))()
     for a, (slot, dt, width, fill, out, lens) in zip(arr, items):
         a.slot, a.dtype, a.width, a.reserved, a.fill, a.out, a.lengths = slot, dt, width, 0, fill, out, lens
-    N.check(dec._lib.tfrg_result_dense(dec._ctx, arr, len(items), C.c_void_p(stats_ptr) if stats_ptr else None,
-                                       C.c_void_p(consumer) if consumer else None), "tfrg_result_dense")
+    if rows is None:
+        N.check(dec._lib.tfrg_result_dense(dec._ctx, arr, len(items), _vp(stats_ptr), _vp(consumer)), "tfrg_result_dense")
+        return
+    ptr, m, rdt = rows
+    N.check(dec._lib.tfrg_result_dense_rows(dec._ctx, arr, len(items), _vp(ptr), rdt, m, row0, _vp(stats_ptr),
+                                            _vp(skipped_ptr), _vp(consumer)), "tfrg_result_dense_rows")
+
+
+ROW_DTYPES = {"int32": N.ROWS_I32, "int64": N.ROWS_I64}
+
+
+def device_rows(rows, n: int, device: int):
+    """A row list for the device path, as (torch tensor, m). A 1-D contiguous int32 / int64 tensor on
+    ``cuda:device`` is used where it is (no copy, no synchronisation: entries out of range are
+    skipped and counted by the kernel). A host sequence is range-checked against ``n`` (IndexError)
+    and uploaded as int64 on the current stream."""
+    import torch  # noqa: PLC0415
+
+    dev = torch.device("cuda", device)
+    if isinstance(rows, torch.Tensor):
+        if rows.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"rows must be an int32 or int64 tensor, not {rows.dtype}")
+        if rows.device != dev:
+            raise ValueError(f"rows is on {rows.device}, the decoder on {dev}")
+        if rows.dim() != 1 or not rows.is_contiguous():
+            raise ValueError(f"rows must be one-dimensional and contiguous, not of shape {tuple(rows.shape)} "
+                             f"with strides {tuple(rows.stride())}")
+        if rows.numel() >= 1 << 31:
+            raise ValueError("rows must hold fewer than 2^31 entries")
+        return rows, int(rows.numel())
+    a = host_rows(rows, n)
+    with torch.cuda.device(dev):
+        return torch.from_numpy(a).to(dev, non_blocking=True), int(a.size)
 
 
 _SIDE_STREAMS: dict = {}
@@ -234,13 +306,19 @@ class _Collator:
     them, so the tensors are used like any other torch result."""
 
     def __init__(self, specs: Sequence[Dense], n: int, device: int, n_batches: int, out: Mapping | None = None,
-                 stream: int | None = None) -> None:
+                 stream: int | None = None, rows=None) -> None:
         import torch  # noqa: PLC0415
 
         self.torch = torch
         self.specs = check_specs(specs)
-        self.n = n
         self.dev = torch.device("cuda", device)
+        # with a row list (``rows``: over the n rows of all batches) the outputs have its m rows, and
+        # every batch gets the whole list: batch k writes the rows whose record is its own
+        self.rows = None
+        self.n_records = n
+        if rows is not None:
+            self.rows, n = device_rows(rows, n, device)
+        self.n = n
         tdt = {"int64": torch.int64, "int32": torch.int32, "float32": torch.float32, "uint8": torch.uint8}
         self.values, self.lengths = {}, {}
         with torch.cuda.device(self.dev):
@@ -261,7 +339,15 @@ class _Collator:
                     self.lengths[sp.out_name] = lens
                 self.values[sp.out_name] = given
             self.k = len(self.specs)
-            self.stats = torch.zeros((max(n_batches, 1), self.k, 4), dtype=torch.int32, device=self.dev)
+            # (the library zeroes the counters of every call, and only those are read back. With a row
+            # list, batch b's [k][4] counters are followed by its [k] skipped counters -- the entries
+            # of the list that are not the batch's -- so that one memset clears both)
+            per = 5 if self.rows is not None else 4
+            counters = torch.empty((max(n_batches, 1), self.k * per), dtype=torch.int32, device=self.dev)
+            self.stats = counters[:, : self.k * 4]
+            self.skips = counters[:, self.k * 4 :] if self.rows is not None else None
+            self.ran = 0  # batches that took the row list
+            self.masks: list = []  # (spec index, how many rows of the list an absent slot's batch holds)
             self.absent = np.zeros((self.k, 4), np.int64)  # counters of the (batch, spec) pairs without a slot
             self.calls: list = []  # (batch, spec indices of the call's counters)
             # the consumer stream; the legacy default stream (handle 0, which NULL would not name) is
@@ -279,59 +365,101 @@ class _Collator:
         if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self.dev or not t.is_contiguous():
             raise ValueError(f"out[{what!r}] must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.dev}")
 
-    def _fill(self, t, sp: Dense) -> None:
+    def _fill(self, t, sp: Dense, mine=None) -> None:
+        """The spec's fill into ``t``, or into its rows where ``mine`` is set."""
         torch = self.torch
         bits = sp.fill_bits
-        if sp.dtype == "uint8":
+        if sp.dtype == "int64":
+            bits = bits - (1 << 64) if bits >= 1 << 63 else bits
+        elif sp.dtype != "uint8":
+            t = t.view(torch.int32)
+            bits = bits - (1 << 32) if bits >= 1 << 31 else bits
+        if mine is None:
             t.fill_(bits)
-        elif sp.dtype == "int64":
-            t.fill_(bits - (1 << 64) if bits >= 1 << 63 else bits)
         else:
-            t.view(torch.int32).fill_(bits - (1 << 32) if bits >= 1 << 31 else bits)
+            t.masked_fill_(mine[:, None], bits)
 
     def run(self, dec, r0: int, r1: int, k: int, strict: bool = False) -> None:
         """Rows [r0, r1) from ``dec``'s last decode (r1 - r0 records), as batch k."""
-        if r1 <= r0:
+        by_rows = self.rows is not None
+        if (not self.n) if by_rows else (r1 <= r0):  # (an empty batch still skips every row of a list)
             return
+        self.ran += by_rows
         items, rows = [], []
         for i, sp in enumerate(self.specs):
             t = self.values[sp.out_name]
             lens = self.lengths.get(sp.out_name)
-            slot = resolve_slot(dec, sp)
+            slot = resolve_slot(dec, sp) if r1 > r0 else None
             if slot is None:
-                if strict:
+                if strict and r1 > r0:
                     raise KeyError(sp.key)
                 with self.torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
-                    self._fill(t[r0:r1], sp)
-                    if lens is not None:
-                        lens[r0:r1].zero_()
-                self.absent[i, 1] += r1 - r0
-                self.absent[i, 2] += r1 - r0
+                    if by_rows:
+                        # the rows of the list that are this batch's (none of an empty batch)
+                        mine = (self.rows >= r0) & (self.rows < r1)
+                        self._fill(t, sp, mine)
+                        if lens is not None:
+                            lens.masked_fill_(mine, 0)
+                        self.masks.append((i, mine.sum()))
+                    else:
+                        self._fill(t[r0:r1], sp)
+                        if lens is not None:
+                            lens[r0:r1].zero_()
+                if not by_rows:
+                    self.absent[i, 1] += r1 - r0
+                    self.absent[i, 2] += r1 - r0
                 continue
             rows.append(i)
+            at = 0 if by_rows else r0
             items.append((slot, DTYPES[sp.dtype][0], int(sp.width), sp.fill_bits,
-                          t.data_ptr() + r0 * t.stride(0) * t.element_size(),
-                          lens.data_ptr() + 4 * r0 if lens is not None else None))
+                          t.data_ptr() + at * t.stride(0) * t.element_size(),
+                          lens.data_ptr() + 4 * at if lens is not None else None))
         if items:
             # (the library's counters are per spec of the call: its rows map back on the host)
-            launch(dec, items, self.stats[k].data_ptr(), self.consumer)
+            if by_rows:
+                rdt = N.ROWS_I64 if self.rows.dtype == self.torch.int64 else N.ROWS_I32
+                launch(dec, items, self.stats[k].data_ptr(), self.consumer, (self.rows.data_ptr(), self.n, rdt), r0,
+                       self.skips[k].data_ptr())
+            else:
+                launch(dec, items, self.stats[k].data_ptr(), self.consumer)
             self.calls.append((k, rows))
 
     def finish(self, strict: bool = False) -> DenseBatch:
         if self.side is not None:
             self.cur.wait_stream(self.side)
         specs, stats_t, absent, calls = self.specs, self.stats, self.absent, self.calls
+        skips_t, masks, m, ran = self.skips, self.masks, self.n, self.ran
 
         def stats() -> dict:
-            got = stats_t.cpu().numpy().view(np.uint32)
+            got = stats_t.cpu().numpy().view(np.uint32).reshape(len(stats_t), -1)
             tot = absent.copy()
             for k, rows in calls:
-                tot[rows] += got[k, : len(rows)]
+                tot[rows] += got[k, : 4 * len(rows)].reshape(-1, 4)
+            for i, cnt in masks:  # (a key without a slot: its rows are padded and empty)
+                tot[i, 1:3] += int(cnt)
             return {sp.out_name: tot[i].astype(np.uint32) for i, sp in enumerate(specs)}
 
-        b = DenseBatch(self.values, self.lengths, stats)
+        def skipped() -> int:
+            # Every batch skips what is not its own: per spec the sum over the batches is the entries
+            # in no batch plus (batches - 1) * m. (A batch without the key, or without a launch,
+            # counts through its mask; the specs agree, the first one answers.)
+            if skips_t is None or not m:
+                return 0
+            if not ran:  # (a plan without a batch holds no row)
+                return m
+            got = skips_t.cpu().numpy().view(np.uint32).astype(np.int64)
+            tot = np.zeros(len(specs), np.int64)
+            for k, rows in calls:
+                tot[rows] += got[k, : len(rows)]
+            for i, cnt in masks:
+                tot[i] += m - int(cnt)
+            return int(tot[0]) - (ran - 1) * m
+
+        b = DenseBatch(self.values, self.lengths, stats, skipped)
         if strict:
             check_strict(specs, b.stats)
+            if b.skipped:
+                raise IndexError(f"{b.skipped} of the {m} rows are outside the {self.n_records} records")
         return b
 
 
@@ -355,7 +483,7 @@ def _raise_first_error(dec, info) -> None:
 
 
 def decoder_dense(dec, specs: Sequence[Dense], *, strict: bool = False, out: Mapping | None = None,
-                  stream: int | None = None) -> DenseBatch:
+                  stream: int | None = None, rows=None) -> DenseBatch:
     """``HipDecoder.dense``: the dense outputs of the decoder's last decode (``decode``,
     ``decode_device`` or ``decode_device32``), as torch tensors on its device.
 
@@ -364,7 +492,13 @@ def decoder_dense(dec, specs: Sequence[Dense], *, strict: bool = False, out: Map
     result holds the pointers, no counters are kept and ``stream`` -- a HIP stream handle, default
     the decode's own stream -- is the consumer stream). ``strict``: ValueError naming the key when a
     record is truncated, padded or holds several bytes elements (FixedLenFeature), KeyError for a key
-    the batch does not have, and the first failing record's exception when a record failed."""
+    the batch does not have, and the first failing record's exception when a record failed.
+
+    ``rows``: the outputs have one row per entry, output row k holding record ``rows[k]`` -- a 1-D
+    contiguous int32 / int64 tensor on the device, used where it is and ordered with the current
+    stream (an entry out of range leaves its row unwritten and counts in ``.skipped``; ``strict``:
+    IndexError), or a host sequence, range-checked here (IndexError) and uploaded. With raw pointers
+    as ``out=`` it is ``(device pointer, m, "int32" | "int64")``."""
     specs = check_specs(specs)
     n = getattr(dec, "_last_n", None)
     info = None
@@ -389,21 +523,28 @@ def decoder_dense(dec, specs: Sequence[Dense], *, strict: bool = False, out: Map
             values[sp.out_name] = int(ptr)
             if lens:
                 lengths[sp.out_name] = int(lens)
-        if n:
+        if rows is not None:
+            if not (isinstance(rows, tuple) and len(rows) == 3 and isinstance(rows[0], (int, np.integer))):
+                raise TypeError('with raw pointers as out=, rows is (device pointer, m, "int32" | "int64")')
+            if rows[2] not in ROW_DTYPES:
+                raise ValueError(f"rows dtype must be one of {sorted(ROW_DTYPES)}, not {rows[2]!r}")
+            launch(dec, items, None, stream, (int(rows[0]), int(rows[1]), ROW_DTYPES[rows[2]]))
+        elif n:
             launch(dec, items, None, stream)
         return DenseBatch(values, lengths, {})
-    col = _Collator(specs, n, dec.device, 1, out, stream)
+    col = _Collator(specs, n, dec.device, 1, out, stream, rows)
     col.run(dec, 0, n, 0, strict)
     return col.finish(strict)
 
 
 def shard_dense(sd, plan: np.ndarray, specs: Sequence[Dense], *, strict: bool = False, out: Mapping | None = None,
-                stream: int | None = None) -> DenseBatch:
+                stream: int | None = None, rows=None) -> DenseBatch:
     """``ShardDecoder.dense``: one output per spec over the whole plan of the last
     ``decode_device`` / ``decode_device32``; batch k's context writes rows [plan[k, 0], plan[k, 1])
-    on its own stream."""
+    on its own stream. ``rows`` (as ``decoder_dense``'s, numbering the plan's rows): every context
+    takes the whole list with ``row0 = plan[k, 0]`` and writes the rows whose record it holds."""
     n = int(plan[-1, 1]) if len(plan) else 0
-    col = _Collator(specs, n, sd.device, len(plan), out, stream)
+    col = _Collator(specs, n, sd.device, len(plan), out, stream, rows)
     for k, (r0, r1, _, _) in enumerate(plan.tolist()):
         d = sd.decs[k]
         if strict:
@@ -412,6 +553,36 @@ def shard_dense(sd, plan: np.ndarray, specs: Sequence[Dense], *, strict: bool = 
                 _raise_first_error(d, info)
         col.run(d, r0, r1, k, strict)
     return col.finish(strict)
+
+
+def minibatches(dec, specs: Sequence[Dense], batch_size: int, *, plan: np.ndarray | None = None, seed: int = 0,
+                drop_last: bool = False):
+    """One epoch of shuffled minibatches over the last decode of ``dec`` (a ``HipDecoder``, or a
+    ``ShardDecoder`` with its ``plan``): yields one ``DenseBatch`` of ``batch_size`` rows per step
+    (the last one shorter, or left out with ``drop_last``). The order is a ``torch.randperm`` on the
+    device from a generator seeded with ``seed``; every step is one launch per decoded batch over the
+    columns where the decode left them, with no host synchronisation after the first."""
+    import torch  # noqa: PLC0415
+
+    if not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+        raise ValueError(f"batch_size must be a positive integer, not {batch_size!r}")
+    specs = check_specs(specs)
+    if plan is not None:
+        n = int(plan[-1, 1]) if len(plan) else 0
+    else:
+        n = getattr(dec, "_last_n", None)
+        if n is None:
+            n = int(dec.info().n_records)
+    dev = torch.device("cuda", dec.device)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    perm = torch.randperm(n, generator=gen, device=dev)
+    for lo in range(0, n, int(batch_size)):
+        hi = min(lo + int(batch_size), n)
+        if drop_last and hi - lo < batch_size:
+            return
+        rows = perm[lo:hi]
+        yield shard_dense(dec, plan, specs, rows=rows) if plan is not None else decoder_dense(dec, specs, rows=rows)
 
 
 def load_tensors(reader, selection, specs: Sequence[Dense], device: int | None = None) -> DenseBatch:

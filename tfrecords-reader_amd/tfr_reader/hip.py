@@ -484,13 +484,21 @@ class HipDecoder:
             self._last_n, self._last_host = n, (host, st, False)
             return self._fetch(host, st, en, info, False, materialize_bytes)
 
-    def dense(self, specs, *, strict: bool = False, out=None, stream: int | None = None):
+    def dense(self, specs, *, strict: bool = False, out=None, stream: int | None = None, rows=None):
         """The last decode (``decode``, ``decode_device`` or ``decode_device32``) as dense torch tensors
         on this decoder's device, one ``[n, width]`` per ``tfr_reader.dense.Dense`` spec, collated by
-        one kernel on the decode's stream (tfrg_result_dense); see ``tfr_reader.dense.decoder_dense``."""
+        one kernel on the decode's stream (tfrg_result_dense); see ``tfr_reader.dense.decoder_dense``.
+        ``rows``: one output row per entry, row k holding record ``rows[k]`` (tfrg_result_dense_rows)."""
         from tfr_reader import dense as D  # noqa: PLC0415
 
-        return D.decoder_dense(self, specs, strict=strict, out=out, stream=stream)
+        return D.decoder_dense(self, specs, strict=strict, out=out, stream=stream, rows=rows)
+
+    def minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False):
+        """One epoch of shuffled ``batch_size``-row ``DenseBatch``es over the last decode, one launch
+        per step; see ``tfr_reader.dense.minibatches``."""
+        from tfr_reader import dense as D  # noqa: PLC0415
+
+        return D.minibatches(self, specs, batch_size, seed=seed, drop_last=drop_last)
 
     def _fetch(self, buf, st, en, info: N.TfrgInfo, payload_only: bool, materialize: bool = False) -> BatchResult:
         n, ns = info.n_records, info.n_slots
@@ -753,13 +761,13 @@ class BatchResult:
     def crc_ok(self) -> np.ndarray:
         return (self.verdict & 6) == 6
 
-    def dense(self, specs, strict: bool = False):
+    def dense(self, specs, strict: bool = False, rows=None):
         """Dense ``[n, width]`` numpy arrays of ``tfr_reader.dense.Dense`` specs from the fetched
         columns (the host counterpart of ``HipDecoder.dense``): a ``DenseBatch`` with ``.lengths`` and
-        ``.stats``."""
+        ``.stats``. ``rows``: output row k is record ``rows[k]`` (IndexError for one out of range)."""
         from tfr_reader import dense as D  # noqa: PLC0415
 
-        return D.batch_dense(self, specs, strict)
+        return D.batch_dense(self, specs, strict, rows)
 
 
 class _Layout:

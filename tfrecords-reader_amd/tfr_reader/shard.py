@@ -374,13 +374,23 @@ class ShardDecoder:
             decs[k].decode_device32(d_bytes + lo, hi - lo, d_start32 + 4 * r0 if d_start32 else None, d_end32 + 4 * r0,
                                     int(firsts[k]), r1 - r0, stream=s, **kw)
 
-    def dense(self, plan: np.ndarray, specs, *, strict: bool = False, out=None, stream: int | None = None):
+    def dense(self, plan: np.ndarray, specs, *, strict: bool = False, out=None, stream: int | None = None,
+              rows=None):
         """The last ``decode_device`` / ``decode_device32`` as dense torch tensors over the whole plan
         (``tfr_reader.dense.Dense`` specs): batch k's context writes rows [plan[k, 0], plan[k, 1]) of
-        each output on its own stream, and the current torch stream waits for all of them."""
+        each output on its own stream, and the current torch stream waits for all of them. ``rows``:
+        one output row per entry, row k holding row ``rows[k]`` of the plan, from whichever batch it
+        is in."""
         from tfr_reader import dense as D  # noqa: PLC0415
 
-        return D.shard_dense(self, plan, specs, strict=strict, out=out, stream=stream)
+        return D.shard_dense(self, plan, specs, strict=strict, out=out, stream=stream, rows=rows)
+
+    def minibatches(self, plan: np.ndarray, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False):
+        """One epoch of shuffled ``batch_size``-row ``DenseBatch``es over the plan's last decode; see
+        ``tfr_reader.dense.minibatches``."""
+        from tfr_reader import dense as D  # noqa: PLC0415
+
+        return D.minibatches(self, specs, batch_size, plan=plan, seed=seed, drop_last=drop_last)
 
     def device_bytes(self) -> tuple[int, int]:
         """(device memory of every batch context, decodes re-run so far: a value hint too small or
