@@ -401,6 +401,51 @@ int tfrg_result_dense_rows(tfrg_ctx* ctx, const tfrg_dense_spec* specs, uint32_t
                            uint32_t rows_dtype, uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped,
                            void* consumer_stream);
 
+/* Ragged minibatches: packed values and offsets for a list of rows (the tf.io.parse_example
+ * VarLenFeature / RaggedTensor side, next to the FixedLenFeature side above; the packed form varlen
+ * attention, jagged tensors and EmbeddingBag take). Per spec and output row k < m, with
+ * g = entry(k) - row0 and entry(k) = d_rows[k] (TFRG_ROWS_I32 / TFRG_ROWS_I64), or k itself when
+ * d_rows is NULL (every record in order; rows_dtype is then ignored):
+ *   L(k): record g's value count (int64_list / float_list slots), or the byte length of element 0 of
+ *     its list, 0 if the list is empty or absent (bytes_list slots, TFRG_DENSE_U8);
+ *   len(k): 0 where g is outside [0, n) (a skipped row, by tfrg_result_dense_rows's rule: INT64_MIN
+ *     and INT64_MAX included); else L(k), or min(L(k), max_len) with max_len != 0;
+ *   offsets[0] = 0, offsets[k + 1] = offsets[k] + len(k): all m + 1 are written, whatever cap is (a
+ *     skipped row is an empty row here: a packed output has no row to leave alone);
+ *   values[offsets[k] + j] for j < len(k): value j of record g, converted as by tfrg_result_dense
+ *     (I32: the low 32 bits, F32: the raw bits, U8: byte j of element 0, zero past the readable input).
+ *     Only positions < cap are stored and nothing else in values is written: with offsets[m] > cap the
+ *     stored prefix is still correct, and the total shows the overflow.
+ * d_totals (device, [n_specs] u64, or NULL): offsets[m] per spec. d_stats (device, [n_specs][4] u32, or
+ * NULL; zeroed by the call on the stream): over the rows that are not skipped, rows with L > max_len
+ * != 0 (truncated), rows without a value (empty), bytes rows with more than one element (multi); the
+ * fourth counter is the skipped rows. A record drawn twice counts twice.
+ * m == 0: offsets[0] = 0, totals 0, no kernel. n == 0: every row is skipped, all offsets are 0.
+ * Three launches on the decode's stream (lengths per tile of rows, a scan of the tile sums, the
+ * gather); no device value is read back. Stream order, confirmation of an optimistic or hinted decode
+ * (the only host synchronisation, once per decode), the columns that are neither written nor read, the
+ * full view afterwards and any number of calls per decode are as for tfrg_result_dense.
+ * TFRG_E_ARG (text in tfrg_last_error): no context, no result, n_specs outside
+ * 1..TFRG_RAGGED_MAX_SPECS, a slot >= n_slots, a dtype that does not fit the slot's kind, a NULL
+ * offsets, values or offsets not aligned to their element size, a nonzero reserved, an unknown
+ * rows_dtype with a non-NULL d_rows, m >= 2^31. */
+#define TFRG_RAGGED_MAX_SPECS 64
+typedef struct tfrg_ragged_spec {
+  uint32_t slot;      /* column, as in tfrg_set_schema */
+  uint32_t dtype;     /* TFRG_DENSE_*; must fit the slot's kind, as tfrg_dense_spec.dtype */
+  uint32_t max_len;   /* 0: whole rows; else a row contributes at most max_len elements */
+  uint32_t reserved;  /* 0 */
+  uint64_t cap;       /* elements that values can hold */
+  void* values;       /* device [cap] of the dtype, caller-owned; NULL: offsets and counters only */
+  int64_t* offsets;   /* device [m + 1], caller-owned, not NULL */
+} tfrg_ragged_spec;
+int tfrg_result_ragged_rows(tfrg_ctx* ctx, const tfrg_ragged_spec* specs, uint32_t n_specs,
+                            const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
+                            uint64_t* d_totals, uint32_t* d_stats, void* consumer_stream);
+/* rows per workgroup tile of tfrg_result_ragged_rows: a power of two from 64 to 4096, 0 = the default
+ * (1024). A tuning/testing knob: with small tiles small row lists exercise the multi-tile logic. */
+int tfrg_ctx_set_ragged_tile(tfrg_ctx* ctx, uint32_t rows);
+
 /* ---------------------------------------------------------------------------------------------
  * Double-buffered host -> HBM decode stream (replaces reader.py:212-247's per-record ThreadPool
  * read+decode for whole-dataset reads). Two slots, each with a pinned staging buffer of batch_bytes,

@@ -15,6 +15,7 @@
 #include "../../include/tfrg.h"
 #include "crc32c.h"
 #include "tfrg_dense.h"
+#include "tfrg_ragged.h"
 #include "tfrg_frame.h"
 #include "tfrg_internal.h"
 #include "tfrg_learn.h"
@@ -179,6 +180,9 @@ struct tfrg_ctx {
   // tfrg_index_device: chunk table, piece rows + summary (device), their pinned host staging
   uint32_t index_chunk = kIndexChunkDefault;  // tfrg_ctx_set_index_chunk
   DBuf fr_tab, fr_dev;
+  // tfrg_result_ragged_rows: rows per tile (tfrg_ctx_set_ragged_tile), the per-tile sums
+  uint32_t ragged_tile = kRaggedTileDefault;
+  DBuf rg_tsum;
   void* fr_pin = nullptr;
   size_t fr_pin_cap = 0;
   // debug hook: records whose list locations are poisoned after the count passes (tests)
@@ -282,7 +286,7 @@ int tfrg_ctx_destroy(tfrg_ctx* c) {
                  &c->order, &c->count, &c->loc, &c->rs, &c->ident, &c->slot_base, &c->totals, &c->kind_totals, &c->i64,
                  &c->f32, &c->b_off, &c->b_len, &c->big_list, &c->slow_list, &c->miss, &c->info, &c->tsum,
                  &c->bdata, &c->boff64, &c->blb, &c->bbig, &c->crc_rec, &c->crc_base, &c->crc_part, &c->tpl, &c->spec,
-                 &c->dq, &c->dq_cnt, &c->lmask, &c->rlist, &c->fr_tab, &c->fr_dev};
+                 &c->dq, &c->dq_cnt, &c->lmask, &c->rlist, &c->fr_tab, &c->fr_dev, &c->rg_tsum};
   for (DBuf* b : all) b->release();
   if (c->order_ev) (void)hipEventDestroy(c->order_ev);
   for (hipEvent_t e : c->dense_ev)
@@ -324,7 +328,7 @@ int tfrg_ctx_device_bytes(tfrg_ctx* c, uint64_t* bytes, uint64_t* reruns) {
                        &c->totals, &c->kind_totals, &c->i64, &c->f32, &c->b_off, &c->b_len, &c->big_list,
                        &c->slow_list, &c->miss, &c->info, &c->tsum, &c->bdata, &c->boff64, &c->blb, &c->bbig,
                        &c->crc_rec, &c->crc_base, &c->crc_part, &c->tpl, &c->spec, &c->dq, &c->dq_cnt, &c->lmask,
-                       &c->rlist, &c->fr_tab, &c->fr_dev};
+                       &c->rlist, &c->fr_tab, &c->fr_dev, &c->rg_tsum};
   uint64_t t = 0;
   for (const DBuf* b : all) t += b->cap;
   if (bytes) *bytes = t;
@@ -345,6 +349,16 @@ int tfrg_ctx_set_index_chunk(tfrg_ctx* c, uint32_t bytes) {
     return TFRG_E_ARG;
   }
   c->index_chunk = bytes ? bytes : kIndexChunkDefault;
+  return 0;
+}
+
+int tfrg_ctx_set_ragged_tile(tfrg_ctx* c, uint32_t rows) {
+  if (!c) return TFRG_E_ARG;
+  if (rows && (rows < kRaggedTileMin || rows > kRaggedTileMax || (rows & (rows - 1)))) {
+    set_error("ragged tile must be a power of two from 64 to 4096 (0: the default)");
+    return TFRG_E_ARG;
+  }
+  c->ragged_tile = rows ? rows : kRaggedTileDefault;
   return 0;
 }
 
@@ -1248,6 +1262,127 @@ int tfrg_result_dense_rows(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n
   rows.row0 = row0;
   rows.d_skipped = d_skipped;
   return result_dense("tfrg_result_dense_rows", true, c, specs, n_specs, rows, d_stats, consumer_stream);
+}
+
+// Packed values + offsets for a list of rows (tfrg_ragged.h: lengths, tile scan, gather). Every grid
+// size comes from m, n_specs, the tile and the split: nothing is read back from the device.
+int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t n_specs, const void* d_rows,
+                            uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
+                            void* consumer_stream) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_result_ragged_rows: " + why);
+    return TFRG_E_ARG;
+  };
+  if (!c) return bad("no context");
+  if (!c->have_result) return bad("no result (decode first)");
+  if (!specs || n_specs == 0 || n_specs > TFRG_RAGGED_MAX_SPECS)
+    return bad("n_specs must be 1.." + std::to_string(TFRG_RAGGED_MAX_SPECS));
+  static_assert(TFRG_RAGGED_MAX_SPECS == kRaggedMaxSpecs, "tfrg.h mirrors tfrg_ragged.h");
+  bool any_values = false;
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_ragged_spec& s = specs[i];
+    const std::string at = "spec " + std::to_string(i) + ": ";
+    if (s.slot >= c->n_slots) return bad(at + "slot " + std::to_string(s.slot) + " >= n_slots");
+    const uint32_t kind = c->slot_kind_h[s.slot] & 3u;
+    const bool fits = (kind == TFRG_KIND_INT64 && (s.dtype == TFRG_DENSE_I64 || s.dtype == TFRG_DENSE_I32)) ||
+                      (kind == TFRG_KIND_FLOAT && s.dtype == TFRG_DENSE_F32) ||
+                      (kind == TFRG_KIND_BYTES && s.dtype == TFRG_DENSE_U8);
+    if (!fits) return bad(at + "dtype " + std::to_string(s.dtype) + " does not fit the slot's kind " + std::to_string(kind));
+    if (!s.offsets) return bad(at + "offsets is NULL");
+    if (s.reserved) return bad(at + "reserved must be 0");
+    const uintptr_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
+    if (((uintptr_t)s.values & (isz - 1)) || ((uintptr_t)s.offsets & 7u))
+      return bad(at + "values and offsets must be aligned to their element size");
+    any_values |= s.values != nullptr && s.cap != 0;
+  }
+  if (d_rows && rows_dtype != TFRG_ROWS_I32 && rows_dtype != TFRG_ROWS_I64)
+    return bad("rows_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(rows_dtype));
+  if (m >= 0x80000000u) return bad("m must be below 2^31");
+  const uint32_t tile = c->ragged_tile;
+  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile;
+  // workgroups per tile that share its span: up to kRaggedMaxSplit while the launch is below 4 per CU
+  uint64_t split = 1;
+  if (any_values && tiles) {
+    const uint64_t want = (uint64_t)std::max(c->num_cus, 1) * 4u, have = tiles * n_specs;
+    split = std::min<uint64_t>(kRaggedMaxSplit, std::max<uint64_t>(1, (want + have - 1) / have));
+  }
+  if (tiles * n_specs * split > 0x7fffffffull) return bad("too many tiles for one launch: raise the ragged tile");
+  HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = confirm_pending(c)) return rc;
+  const bool run = m && c->n;
+  if (run) HIP_TRY(c->rg_tsum.ensure((size_t)(tiles * n_specs) * 8));
+  const hipStream_t st = c->last_stream;
+  const hipStream_t cs = consumer_stream ? static_cast<hipStream_t>(consumer_stream) : st;
+  if (cs != st) {
+    for (hipEvent_t& e : c->dense_ev)
+      if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->dense_ev[0], cs));
+    HIP_TRY(hipStreamWaitEvent(st, c->dense_ev[0], 0));
+  }
+  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
+  if (run) {
+    RaggedArgs a{};
+    a.rs = c->rs.as<uint32_t>();
+    a.slot_base = c->slot_base.as<uint64_t>();
+    // (a record without a value reads element 0 of a value array and drops it: an array that was never
+    // allocated is stood in for by the slot bases, which every result has)
+    auto col = [&](const DBuf& b) { return b.p ? b.p : c->slot_base.p; };
+    a.i64 = static_cast<const int64_t*>(col(c->i64));
+    a.f32 = static_cast<const uint32_t*>(col(c->f32));
+    a.b_off = static_cast<const uint32_t*>(col(c->b_off));
+    a.b_len = static_cast<const uint32_t*>(col(c->b_len));
+    // the bytes' source: the views' input buffer, readable to round_up(nbytes, 16), or the byte column
+    uint64_t bound;
+    if (c->materialized) {
+      a.b_off64 = static_cast<const uint64_t*>(col(c->boff64));
+      a.in = c->bdata.as<uint8_t>();
+      bound = c->bdata.p ? (uint64_t)c->bdata.cap & ~15ull : 0;
+    } else {
+      a.in = c->last.d_bytes;
+      bound = a.in ? (c->last.nbytes + 15ull) & ~15ull : 0;
+    }
+    a.in_bound = (uint32_t)std::min<uint64_t>(bound, 0xfffffff0ull);
+    a.info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
+    a.stats = d_stats;
+    a.totals = d_totals;
+    a.tsum = c->rg_tsum.as<uint64_t>();
+    a.rows = d_rows;
+    a.rows64 = rows_dtype == TFRG_ROWS_I64;
+    a.row0 = row0;
+    a.m = m;
+    a.n = c->n;
+    a.n_specs = n_specs;
+    a.tile = tile;
+    a.tiles = (uint32_t)tiles;
+    a.split = (uint32_t)split;
+    const bool const_len = (c->last_implicit & TFRG_IMPLICIT_BYTES_LEN) != 0;
+    for (uint32_t i = 0; i < n_specs; ++i) {
+      const tfrg_ragged_spec& s = specs[i];
+      RaggedSpec& d = a.sp[i];
+      d.values = s.values;
+      d.offsets = s.offsets;
+      d.cap = s.cap;
+      d.slot = s.slot;
+      d.dtype = s.dtype;
+      d.max_len = s.max_len;
+      d.const_len = kRaggedNoLen;  // (as implicit_len_runs: the column is not stored, the shapes' length holds)
+      if (const_len && s.dtype == TFRG_DENSE_U8) d.const_len = s.slot < c->const_len.size() ? c->const_len[s.slot] : 0u;
+    }
+    HIP_TRY(launch_ragged(a, st));
+  } else {
+    // no row, or no record (every row is skipped): all offsets and totals are 0
+    for (uint32_t i = 0; i < n_specs; ++i) {
+      HIP_TRY(hipMemsetAsync(specs[i].offsets, 0, ((size_t)m + 1) * 8, st));
+      if (d_stats && m)
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
+    }
+    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 8, st));
+  }
+  if (cs != st) {
+    HIP_TRY(hipEventRecord(c->dense_ev[1], st));
+    HIP_TRY(hipStreamWaitEvent(cs, c->dense_ev[1], 0));
+  }
+  return 0;
 }
 
 int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {

@@ -6,6 +6,7 @@ spreads the readers' files over several GPUs.
 """
 
 from tfr_reader.example import Feature, set_decoder_type
+from tfr_reader.ragged import Ragged, RaggedBatch
 from tfr_reader.reader import (
     TFRecordDatasetReader,
     TFRecordFileReader,
@@ -17,6 +18,8 @@ from tfr_reader.reader import (
 
 __all__ = [
     "Feature",
+    "Ragged",
+    "RaggedBatch",
     "TFRecordDatasetReader",
     "TFRecordFileReader",
     "inspect_dataset_example",

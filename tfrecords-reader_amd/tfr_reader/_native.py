@@ -117,6 +117,27 @@ DENSE_MAX_WIDTH = 4096
 ROWS_I32 = 0  # tfrg_result_dense_rows: the row list's element type (TFRG_ROWS_*)
 ROWS_I64 = 1
 
+
+class TfrgRaggedSpec(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("dtype", C.c_uint32),
+        ("max_len", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("cap", C.c_uint64),
+        ("values", C.c_void_p),
+        ("offsets", C.c_void_p),
+    ]
+
+
+RAGGED_MAX_SPECS = 64
+# tfrg_ctx_set_ragged_tile's range and default (csrc/tfrg_ragged.h), and the tile sums the scan
+# kernel takes per pass: with more tiles than that per spec it carries into a further pass
+RAGGED_TILE_MIN = 64
+RAGGED_TILE_MAX = 4096
+RAGGED_TILE_DEFAULT = 1024
+RAGGED_SCAN_THREADS = 1024
+
 # name -> (restype, argtypes); the exact list of exported symbols declared in include/tfrg.h
 SIGNATURES: dict[str, tuple] = {
     "tfrg_abi_version": (C.c_int, []),
@@ -194,6 +215,9 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_result_dense": (C.c_int, [C.c_void_p, C.POINTER(TfrgDenseSpec), C.c_uint32, C.c_void_p, C.c_void_p]),
     "tfrg_result_dense_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgDenseSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tfrg_result_ragged_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgRaggedSpec), C.c_uint32, C.c_void_p, C.c_uint32,
+                                          C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tfrg_ctx_set_ragged_tile": (C.c_int, [C.c_void_p, C.c_uint32]),
 }
 
 FLAG_PAYLOAD_ONLY = 1

@@ -500,6 +500,25 @@ class HipDecoder:
 
         return D.minibatches(self, specs, batch_size, seed=seed, drop_last=drop_last)
 
+    def set_ragged_tile(self, rows: int) -> None:
+        """Rows per workgroup tile of ``ragged`` (a power of two from 64 to 4096; 0: the default 1024)."""
+        N.check(self._lib.tfrg_ctx_set_ragged_tile(self._ctx, int(rows)), "tfrg_ctx_set_ragged_tile")
+
+    def ragged(self, specs, *, rows=None, capacity=None, out=None, stream: int | None = None):
+        """The last decode as packed ``(values, offsets)`` torch tensors on this decoder's device, one
+        pair per ``tfr_reader.ragged.Ragged`` spec, for every record or for the list ``rows``
+        (tfrg_result_ragged_rows); see ``tfr_reader.ragged.decoder_ragged``."""
+        from tfr_reader import ragged as R  # noqa: PLC0415
+
+        return R.decoder_ragged(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
+
+    def ragged_minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False, capacity=None):
+        """One epoch of shuffled ``batch_size``-row ``RaggedBatch``es over the last decode; see
+        ``tfr_reader.ragged.ragged_minibatches``."""
+        from tfr_reader import ragged as R  # noqa: PLC0415
+
+        return R.ragged_minibatches(self, specs, batch_size, seed=seed, drop_last=drop_last, capacity=capacity)
+
     def _fetch(self, buf, st, en, info: N.TfrgInfo, payload_only: bool, materialize: bool = False) -> BatchResult:
         n, ns = info.n_records, info.n_slots
         kt = info.kind_totals
@@ -768,6 +787,14 @@ class BatchResult:
         from tfr_reader import dense as D  # noqa: PLC0415
 
         return D.batch_dense(self, specs, strict, rows)
+
+    def ragged(self, specs, rows=None):
+        """Packed ``(values, offsets)`` numpy arrays of ``tfr_reader.ragged.Ragged`` specs from the
+        fetched columns (the host counterpart of ``HipDecoder.ragged``): a ``RaggedBatch`` with
+        ``.totals`` and ``.stats``. ``rows``: row k is record ``rows[k]`` (IndexError for one out of range)."""
+        from tfr_reader import ragged as R  # noqa: PLC0415
+
+        return R.batch_ragged(self, specs, rows)
 
 
 class _Layout:

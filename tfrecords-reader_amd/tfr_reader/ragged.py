@@ -1,0 +1,352 @@
+"""Ragged minibatches from decoded batches: the ``tf.io.parse_example`` ``VarLenFeature`` /
+``RaggedTensor`` side, next to the ``FixedLenFeature`` side of ``tfr_reader.dense``.
+
+``Ragged`` specs name variable-length outputs -- per key one packed ``values`` array with the rows
+back to back, and ``m + 1`` ``offsets`` (``cu_seqlens``: row k is ``values[offsets[k]:offsets[k + 1]]``)
+-- the form varlen attention, ``torch.nested`` / jagged tensors and ``EmbeddingBag`` take. No row is
+padded, and a row may be longer than ``dense``'s widest output.
+
+* ``HipDecoder.ragged`` gathers them on the device for every record in order or for a list of rows
+  (``rows=``: shuffled, sampled, filtered), in three launches over the columns where the decode left
+  them (``tfrg_result_ragged_rows``), and ``HipDecoder.ragged_minibatches`` draws an epoch from one
+  decode;
+* ``BatchResult.ragged`` / ``raggedify`` compute the same function with numpy from fetched columns
+  (the host path, and the reference the device path is tested against).
+
+Per output: ``totals[name]`` is ``offsets[m]``, ``stats[name]`` the four counters ``(truncated,
+empty, multi, skipped)``: rows longer than ``max_len``, rows without a value, (bytes) rows with more
+than one element -- only element 0 is taken, as ``dense`` does -- and rows whose entry in a device row
+list is out of range (they are empty rows here, and count in ``skipped`` alone).
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from collections.abc import Mapping, Sequence
+from dataclasses import dataclass
+
+import numpy as np
+
+from tfr_reader import _native as N
+from tfr_reader import dense as D
+
+STAT_NAMES = ("truncated", "empty", "multi", "skipped")
+
+
+@dataclass(frozen=True)
+class Ragged:
+    """One ragged output: ``key``'s values of ``dtype`` ("int64", "int32", "float32", "uint8"; the
+    dtype selects the slot kind as for ``Dense``). ``max_len``: a row contributes at most that many
+    elements (None: whole rows). ``name``: the output's name in the result (default: the key)."""
+
+    key: str
+    dtype: str
+    max_len: int | None = None
+    name: str | None = None
+
+    def __post_init__(self) -> None:
+        if self.dtype not in D.DTYPES:
+            raise ValueError(f"Ragged({self.key!r}): dtype must be one of {sorted(D.DTYPES)}, not {self.dtype!r}")
+        if self.max_len is not None and (not isinstance(self.max_len, (int, np.integer))
+                                         or not 1 <= int(self.max_len) < 1 << 32):
+            raise ValueError(f"Ragged({self.key!r}): max_len must be None or in 1..2^32 - 1, not {self.max_len!r}")
+        if not isinstance(self.key, str):
+            raise TypeError(f"Ragged key must be a str, not {type(self.key).__name__}")
+
+    @property
+    def out_name(self) -> str:
+        return self.name if self.name is not None else self.key
+
+    @property
+    def limit(self) -> int:
+        """``tfrg_ragged_spec.max_len`` (0: whole rows)."""
+        return int(self.max_len) if self.max_len is not None else 0
+
+
+def check_specs(specs: Sequence[Ragged]) -> list[Ragged]:
+    specs = list(specs)
+    if not 1 <= len(specs) <= N.RAGGED_MAX_SPECS:
+        raise ValueError(f"between 1 and {N.RAGGED_MAX_SPECS} Ragged specs per call, not {len(specs)}")
+    seen = set()
+    for s in specs:
+        if not isinstance(s, Ragged):
+            raise TypeError(f"specs must be Ragged objects, not {type(s).__name__}")
+        if s.out_name in seen:
+            raise ValueError(f"two Ragged specs are named {s.out_name!r}: give one of them name=")
+        seen.add(s.out_name)
+    return specs
+
+
+class RaggedBatch(dict):
+    """name -> ``(values, offsets)`` (torch tensors on the decoder's device, numpy arrays on the host
+    path). ``values`` holds ``capacity`` elements, of which the first ``offsets[-1]`` (at most) are
+    rows. ``totals[name]``: ``offsets[m]``; ``stats[name]``: the four counters ``STAT_NAMES`` as a
+    uint32 array; ``overflowed[name]``: the total is above the capacity (the stored prefix is still
+    right, the offsets complete). All three are read back from the device on first access."""
+
+    def __init__(self, outputs: Mapping, capacity: Mapping, totals, stats) -> None:
+        super().__init__(outputs)
+        self.capacity = dict(capacity)
+        self._totals = totals  # a dict, or a function returning it
+        self._stats = stats
+
+    @property
+    def totals(self) -> dict[str, int]:
+        if callable(self._totals):
+            self._totals = self._totals()
+        return self._totals
+
+    @property
+    def stats(self) -> dict[str, np.ndarray]:
+        if callable(self._stats):
+            self._stats = self._stats()
+        return self._stats
+
+    @property
+    def overflowed(self) -> dict[str, bool]:
+        return {k: t > self.capacity[k] for k, t in self.totals.items()}
+
+
+# ---------------------------------------------------------------------- host path (numpy)
+def raggedify(specs: Sequence[Ragged], *, n: int, slot_key: Sequence[str | None], slot_kind: Sequence[int],
+              row_splits: np.ndarray, slot_base: np.ndarray, i64: np.ndarray, f32: np.ndarray,
+              bytes_off: np.ndarray | None = None, bytes_len: np.ndarray | None = None, buf: np.ndarray | None = None,
+              bytes_data: np.ndarray | None = None, bytes_offsets: np.ndarray | None = None, rows=None) -> RaggedBatch:
+    """The ragged outputs of ``specs`` from plain result columns (as ``dense.densify`` takes them),
+    record by record. A key without a slot gives all-empty rows. ``rows``: output row k is record
+    ``rows[k]`` (any order, repeats allowed; IndexError for one outside [0, n))."""
+    specs = check_specs(specs)
+    picked = list(range(n)) if rows is None else D.host_rows(rows, n).tolist()
+    m = len(picked)
+    outputs, totals, stats = {}, {}, {}
+    for sp in specs:
+        _, kind, dt, udt = D.DTYPES[sp.dtype]
+        parts = []
+        offsets = np.zeros(m + 1, np.int64)
+        st = np.zeros(4, np.uint32)
+        s = D.find_slot(slot_key, slot_kind, sp.key, kind)
+        if s is None:
+            st[1] = m
+        else:
+            base = int(slot_base[s])
+            rs = np.asarray(row_splits[s]).astype(np.int64)
+            for k, g in enumerate(picked):
+                lo, c = base + int(rs[g]), int(rs[g + 1] - rs[g])
+                if kind == 1:
+                    row = np.zeros(0, np.uint8)
+                    if c:
+                        if bytes_data is not None:
+                            row = np.asarray(bytes_data[int(bytes_offsets[lo]) : int(bytes_offsets[lo + 1])], np.uint8)
+                        else:
+                            o, ln = int(bytes_off[lo]), int(bytes_len[lo])
+                            elem = np.asarray(buf[o : o + ln], np.uint8)
+                            row = np.zeros(ln, np.uint8)  # (a view past the input reads zeros)
+                            row[: elem.size] = elem
+                    st[2] += c > 1
+                else:
+                    src = f32 if kind == 2 else i64
+                    row = np.asarray(src[lo : lo + c]).view(np.uint32 if kind == 2 else np.uint64).astype(udt)
+                full = int(row.size)
+                if sp.max_len is not None and full > sp.max_len:
+                    row = row[: int(sp.max_len)]
+                    st[0] += 1
+                st[1] += c == 0
+                parts.append(row)
+                offsets[k + 1] = offsets[k] + row.size
+        values = np.concatenate(parts).astype(udt) if parts else np.zeros(0, udt)
+        outputs[sp.out_name] = (values.view(dt), offsets)
+        totals[sp.out_name] = int(offsets[m])
+        stats[sp.out_name] = st
+    return RaggedBatch(outputs, dict(totals), totals, stats)
+
+
+def batch_ragged(res, specs: Sequence[Ragged], rows=None) -> RaggedBatch:
+    """``BatchResult.ragged``: ``raggedify`` over a fetched result's columns."""
+    return raggedify(specs, n=len(res), slot_key=res.slot_key, slot_kind=res.slot_kind, row_splits=res.row_splits,
+                     slot_base=res.slot_base, i64=res.i64, f32=res.f32, bytes_off=res.bytes_off,
+                     bytes_len=res.bytes_len, buf=res.buf, bytes_data=res.bytes_data, bytes_offsets=res.bytes_offsets,
+                     rows=rows)
+
+
+# ---------------------------------------------------------------------- device path
+def _vp(p: int | None):
+    return C.c_void_p(p) if p else None
+
+
+def launch(dec, items: Sequence[tuple], rows: tuple | None, m: int, row0: int, totals_ptr: int | None,
+           stats_ptr: int | None, consumer: int | None) -> None:
+    """One ``tfrg_result_ragged_rows`` call: items are (slot, TFRG_DENSE_* id, max_len, cap, values
+    pointer or None, offsets pointer); ``rows``: (device pointer, TFRG_ROWS_* id) or None."""
+    arr = (N.TfrgRaggedSpec * len(items))()
+    for a, (slot, dt, max_len, cap, values, offsets) in zip(arr, items):
+        a.slot, a.dtype, a.max_len, a.reserved, a.cap, a.values, a.offsets = slot, dt, max_len, 0, cap, values, offsets
+    ptr, rdt = rows if rows is not None else (None, 0)
+    N.check(dec._lib.tfrg_result_ragged_rows(dec._ctx, arr, len(items), _vp(ptr), rdt, m, row0, _vp(totals_ptr),
+                                             _vp(stats_ptr), _vp(consumer)), "tfrg_result_ragged_rows")
+
+
+def decoder_ragged(dec, specs: Sequence[Ragged], *, rows=None, capacity=None, out: Mapping | None = None,
+                   stream: int | None = None) -> RaggedBatch:
+    """``HipDecoder.ragged``: the ragged outputs of the decoder's last decode, as torch tensors on
+    its device: name -> ``(values, offsets)``.
+
+    ``rows``: as ``dense(rows=)`` -- a 1-D contiguous int32 / int64 tensor on the device, used where
+    it is (an entry out of range is an empty row and counts in ``skipped``), or a host sequence,
+    range-checked here (IndexError) and uploaded; None: every record in order.
+
+    ``capacity``: elements per ``values`` tensor, an int or name -> int. With it the call enqueues
+    its work and returns without a host synchronisation; ``.overflowed`` tells (on first access)
+    whether a total was above it, in which case ``values`` holds the prefix that fits and the offsets
+    are still complete. Without it the call runs twice: offsets only, one device-to-host copy of the
+    totals (the step's single synchronisation), exact allocations, then the gather.
+
+    ``out``: name -> ``(values tensor, offsets tensor)`` to write into (``values`` 1-D of the spec's
+    dtype, its size the capacity; ``offsets`` int64 ``[m + 1]``). ``stream``: a HIP stream handle as
+    the consumer stream (default: the current torch stream)."""
+    import torch  # noqa: PLC0415
+
+    specs = check_specs(specs)
+    n = getattr(dec, "_last_n", None)
+    if n is None:
+        n = int(dec.info().n_records)
+    dev = torch.device("cuda", dec.device)
+    tdt = {"int64": torch.int64, "int32": torch.int32, "float32": torch.float32, "uint8": torch.uint8}
+    with torch.cuda.device(dev):
+        cur = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(cur):
+        d_rows, m = (None, n) if rows is None else D.device_rows(rows, n, dec.device)
+        # the consumer stream; the legacy default stream (handle 0, which NULL would not name) is stood
+        # in for by a side stream ordered after and before it
+        side = None
+        consumer = int(cur.cuda_stream)
+        if not consumer:
+            side = D._SIDE_STREAMS.get(dec.device)
+            if side is None:
+                side = D._SIDE_STREAMS[dec.device] = torch.cuda.Stream(dev)
+            consumer = int(side.cuda_stream)
+
+        def call(items, totals_t, stats_t) -> None:
+            if side is not None:
+                side.wait_stream(cur)
+            rw = None
+            if d_rows is not None:
+                rw = (d_rows.data_ptr(), N.ROWS_I64 if d_rows.dtype == torch.int64 else N.ROWS_I32)
+            launch(dec, items, rw, m, 0, totals_t.data_ptr(), stats_t.data_ptr() if stats_t is not None else None,
+                   consumer)
+            if side is not None:
+                cur.wait_stream(side)
+
+        caps: dict[str, int | None] = {}
+        values: dict = {}
+        offsets: dict = {}
+        present: list[tuple[Ragged, int]] = []  # the specs the library is called for, with their slots
+        absent: list[Ragged] = []  # key or kind not in the key table, or no record: all-empty rows, no launch
+        for sp in specs:
+            k = sp.out_name
+            given = (out or {}).get(k)
+            v = o = None
+            if given is not None:
+                v, o = given
+                if v.dim() != 1 or v.dtype != tdt[sp.dtype] or v.device != dev or not v.is_contiguous():
+                    raise ValueError(f"out[{k!r}] values must be a contiguous 1-D {tdt[sp.dtype]} tensor on {dev}")
+                if tuple(o.shape) != (m + 1,) or o.dtype != torch.int64 or o.device != dev or not o.is_contiguous():
+                    raise ValueError(f"out[{k!r}] offsets must be a contiguous int64 tensor of shape ({m + 1},) on {dev}")
+                caps[k] = int(v.numel())
+            else:
+                cap = capacity.get(k) if isinstance(capacity, Mapping) else capacity
+                if cap is not None and (not isinstance(cap, (int, np.integer)) or cap < 0):
+                    raise ValueError(f"capacity must be a non-negative integer, not {cap!r}")
+                caps[k] = None if cap is None else int(cap)
+            slot = D.resolve_slot(dec, sp) if n else None
+            if slot is None:
+                absent.append(sp)
+                caps[k] = caps[k] or 0
+                if v is None:
+                    v = torch.empty(caps[k], dtype=tdt[sp.dtype], device=dev)
+                if o is None:
+                    o = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+                else:
+                    o.zero_()
+            else:
+                present.append((sp, slot))
+                if o is None:
+                    o = torch.empty(m + 1, dtype=torch.int64, device=dev)
+            values[k], offsets[k] = v, o
+        # the skipped rows of a spec without a launch: every row of an empty decode, else the entries
+        # of a device row list outside [0, n) (a host list was checked)
+        absent_skipped = m if not n else 0
+        if absent and n and isinstance(rows, torch.Tensor):
+            absent_skipped = ((d_rows < 0) | (d_rows >= n)).sum()
+
+        kp = len(present)
+        host_totals = None
+        totals_t = stats_t = None
+        if kp:
+            totals_t = torch.empty(kp, dtype=torch.int64, device=dev)
+            stats_t = torch.empty((kp, 4), dtype=torch.int32, device=dev)
+
+            def items(with_values: bool) -> list:
+                got = []
+                for sp, slot in present:
+                    v = values[sp.out_name] if with_values else None
+                    got.append((slot, D.DTYPES[sp.dtype][0], sp.limit, int(v.numel()) if v is not None else 0,
+                                v.data_ptr() if v is not None and v.numel() else None, offsets[sp.out_name].data_ptr()))
+                return got
+
+            if any(caps[sp.out_name] is None for sp, _ in present):
+                call(items(False), totals_t, None)
+                host_totals = [int(t) for t in totals_t.cpu().tolist()]  # the step's one synchronisation
+                for (sp, _), t in zip(present, host_totals):
+                    if caps[sp.out_name] is None:
+                        caps[sp.out_name] = t
+            for sp, _ in present:
+                if values[sp.out_name] is None:
+                    values[sp.out_name] = torch.empty(caps[sp.out_name], dtype=tdt[sp.dtype], device=dev)
+            call(items(True), totals_t, stats_t)
+
+    names = [sp.out_name for sp, _ in present]
+
+    def totals() -> dict:
+        got = {sp.out_name: 0 for sp in absent}
+        if kp:
+            host = host_totals if host_totals is not None else totals_t.cpu().tolist()
+            got.update({k: int(t) for k, t in zip(names, host)})
+        return {sp.out_name: got[sp.out_name] for sp in specs}
+
+    def stats() -> dict:
+        got = {}
+        if absent:
+            bad = int(absent_skipped)
+            for sp in absent:
+                got[sp.out_name] = np.array([0, m - bad, 0, bad], np.uint32)
+        if kp:
+            host = stats_t.cpu().numpy().view(np.uint32)
+            got.update({k: host[i].copy() for i, k in enumerate(names)})
+        return {sp.out_name: got[sp.out_name] for sp in specs}
+
+    return RaggedBatch({sp.out_name: (values[sp.out_name], offsets[sp.out_name]) for sp in specs}, caps, totals, stats)
+
+
+def ragged_minibatches(dec, specs: Sequence[Ragged], batch_size: int, *, seed: int = 0, drop_last: bool = False,
+                       capacity=None):
+    """One epoch of shuffled ragged minibatches over the last decode of ``dec``: yields one
+    ``RaggedBatch`` of ``batch_size`` rows per step (the last one shorter, or left out with
+    ``drop_last``), in the order of a ``torch.randperm`` on the device seeded with ``seed``, as
+    ``dense.minibatches``. With ``capacity`` no step synchronises with the host."""
+    import torch  # noqa: PLC0415
+
+    if not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+        raise ValueError(f"batch_size must be a positive integer, not {batch_size!r}")
+    specs = check_specs(specs)
+    n = getattr(dec, "_last_n", None)
+    if n is None:
+        n = int(dec.info().n_records)
+    dev = torch.device("cuda", dec.device)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    perm = torch.randperm(n, generator=gen, device=dev)
+    for lo in range(0, n, int(batch_size)):
+        hi = min(lo + int(batch_size), n)
+        if drop_last and hi - lo < batch_size:
+            return
+        yield decoder_ragged(dec, specs, rows=perm[lo:hi], capacity=capacity)
