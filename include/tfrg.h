@@ -446,6 +446,83 @@ int tfrg_result_ragged_rows(tfrg_ctx* ctx, const tfrg_ragged_spec* specs, uint32
  * (1024). A tuning/testing knob: with small tiles small row lists exercise the multi-tile logic. */
 int tfrg_ctx_set_ragged_tile(tfrg_ctx* ctx, uint32_t rows);
 
+/* Filtered row lists: the WHERE clause over the last result, on the device. Predicates over the
+ * decoded columns in, the compacted list of the passing rows in device memory out -- usable as it is
+ * as d_rows of tfrg_result_dense_rows / tfrg_result_ragged_rows of the same context(s), with the same
+ * row0, and with no host synchronisation in between.
+ * Candidates: candidate k < m has entry(k) = d_rows[k] (TFRG_ROWS_I32 / TFRG_ROWS_I64), or k itself
+ * when d_rows is NULL (rows_dtype is then ignored), and names record g = entry(k) - row0. A candidate
+ * with g outside [0, n) -- INT64_MIN and INT64_MAX included, by tfrg_result_dense_rows's rule -- is
+ * skipped: nothing indexed by g is read, it is never selected, and it adds 1 to d_stats[1].
+ * A term is true or false for record g:
+ *   TFRG_SEL_VALUE: false if the record has <= index values, whatever the op (NE included); else
+ *     value[index] op operand;
+ *   TFRG_SEL_ANY: true iff some value of the record's list satisfies the op (false for an empty or
+ *     absent list);
+ *   TFRG_SEL_COUNT, TFRG_SEL_BYTES_LEN, TFRG_SEL_STATUS: always defined (0 for an absent list),
+ *     compared as signed int64.
+ * int64_list slots compare as signed 64-bit integers. float_list slots compare the float32 VALUES, not
+ * their bits: a NaN on either side is false under every op but NE, -0.0 == 0.0, and denormals are not
+ * flushed (the smallest positive denormal is > 0.0).
+ * Terms combine as an AND of OR-groups: record g passes iff every group that occurs among the terms
+ * holds at least one true term. `label IN (1, 3)` is two EQ terms of one group, `10 <= x < 20` two
+ * terms of two groups; n_terms == 0 selects every candidate that is not skipped.
+ * Output: the entries entry(k) (not g) of the passing candidates, in candidate order, go to d_out from
+ * position base on: base is 0, or with TFRG_SEL_APPEND the value of *d_count as the call's kernels find
+ * it on the device. Only positions < cap are stored and nothing else in d_out is written;
+ * *d_count = base + passing shows an overflow, as tfrg_result_ragged_rows's totals do. d_out NULL gives
+ * the count alone. out_dtype (TFRG_ROWS_I32 / TFRG_ROWS_I64) is independent of rows_dtype. d_stats
+ * (device, [2] u32, or NULL; zeroed by the call on the stream): candidates selected by this call,
+ * candidates skipped. The output is a function of the inputs alone: two equal calls write equal bytes.
+ * m == 0: no kernel; *d_count = 0, or unchanged with TFRG_SEL_APPEND. n == 0: every candidate is skipped.
+ * Three launches on the decode's stream (verdicts per tile of candidates, kept as one bit each; a scan
+ * of the tile sums; the write, which reads the bits and the entries alone); no device value is read
+ * back. Stream order, confirmation of an optimistic or hinted decode (the only host synchronisation,
+ * once per decode), the columns that are neither written nor read (identity row splits of placed
+ * slots, the implicit lengths and statuses), the full view afterwards and any number of calls per
+ * decode are as for tfrg_result_ragged_rows. Calls that share one consumer_stream are ordered with
+ * each other, whatever their contexts: several contexts holding consecutive runs of a row space append
+ * to one list, each with its own row0, the first without TFRG_SEL_APPEND.
+ * TFRG_E_ARG (text in tfrg_last_error, prefixed "tfrg_result_select_rows: "): no context, no result,
+ * n_terms > TFRG_SEL_MAX_TERMS, a slot >= n_slots, a subject that does not fit the slot's kind (VALUE /
+ * ANY on a bytes_list slot, BYTES_LEN on another kind, STATUS with slot != 0), an unknown subject or
+ * op, group >= 32, index != 0 outside VALUE, a nonzero reserved, a float operand with high bits set, an
+ * unknown rows_dtype with a non-NULL d_rows, an unknown out_dtype, m >= 2^31, a NULL d_count, d_out or
+ * d_count not aligned to their element size, a TFRG_ROWS_I32 output when [row0, row0 + n) does not fit
+ * int32, unknown flag bits. (d_out non-NULL with cap == 0 is allowed.) */
+#define TFRG_SEL_MAX_TERMS 32
+/* subject of a term */
+#define TFRG_SEL_VALUE 0      /* value `index` of the record's list (int64_list / float_list slot) */
+#define TFRG_SEL_ANY 1        /* any value of the record's list (int64_list / float_list slot) */
+#define TFRG_SEL_COUNT 2      /* the record's value count (any kind), compared as int64 */
+#define TFRG_SEL_BYTES_LEN 3  /* byte length of element 0 of a bytes_list slot, 0 if empty or absent
+                                 (tfrg_result_dense's lengths), compared as int64 */
+#define TFRG_SEL_STATUS 4     /* the record's status (tfrg_status.h) as int64; slot must be 0 */
+/* op */
+#define TFRG_SEL_EQ 0
+#define TFRG_SEL_NE 1
+#define TFRG_SEL_LT 2
+#define TFRG_SEL_LE 3
+#define TFRG_SEL_GT 4
+#define TFRG_SEL_GE 5
+typedef struct tfrg_select_term {
+  uint32_t slot;      /* column, as in tfrg_set_schema */
+  uint32_t subject;   /* TFRG_SEL_VALUE .. TFRG_SEL_STATUS */
+  uint32_t op;        /* TFRG_SEL_EQ .. TFRG_SEL_GE */
+  uint32_t group;     /* < 32: terms of one group are ORed, the groups ANDed */
+  uint32_t index;     /* TFRG_SEL_VALUE only, else 0 */
+  uint32_t reserved;  /* 0 */
+  uint64_t operand;   /* int64 raw bits; float_list VALUE / ANY: float bits in the low 32, high 32 zero */
+} tfrg_select_term;   /* 32 bytes */
+#define TFRG_SEL_APPEND 1u
+int tfrg_result_select_rows(tfrg_ctx* ctx, const tfrg_select_term* terms, uint32_t n_terms,
+                            const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
+                            void* d_out, uint32_t out_dtype, uint64_t cap, uint64_t* d_count,
+                            uint32_t* d_stats, uint32_t flags, void* consumer_stream);
+/* candidates per workgroup tile of tfrg_result_select_rows: a power of two from 64 to 4096, 0 = the
+ * default (1024). A tuning/testing knob, as tfrg_ctx_set_ragged_tile. */
+int tfrg_ctx_set_select_tile(tfrg_ctx* ctx, uint32_t rows);
+
 /* ---------------------------------------------------------------------------------------------
  * Double-buffered host -> HBM decode stream (replaces reader.py:212-247's per-record ThreadPool
  * read+decode for whole-dataset reads). Two slots, each with a pinned staging buffer of batch_bytes,

@@ -16,6 +16,7 @@
 #include "crc32c.h"
 #include "tfrg_dense.h"
 #include "tfrg_ragged.h"
+#include "tfrg_select.h"
 #include "tfrg_frame.h"
 #include "tfrg_internal.h"
 #include "tfrg_learn.h"
@@ -183,6 +184,10 @@ struct tfrg_ctx {
   // tfrg_result_ragged_rows: rows per tile (tfrg_ctx_set_ragged_tile), the per-tile sums
   uint32_t ragged_tile = kRaggedTileDefault;
   DBuf rg_tsum;
+  // tfrg_result_select_rows: candidates per tile (tfrg_ctx_set_select_tile), the ballot words of the
+  // candidates followed by the per-tile sums
+  uint32_t select_tile = kSelTileDefault;
+  DBuf sel_buf;
   void* fr_pin = nullptr;
   size_t fr_pin_cap = 0;
   // debug hook: records whose list locations are poisoned after the count passes (tests)
@@ -286,7 +291,7 @@ int tfrg_ctx_destroy(tfrg_ctx* c) {
                  &c->order, &c->count, &c->loc, &c->rs, &c->ident, &c->slot_base, &c->totals, &c->kind_totals, &c->i64,
                  &c->f32, &c->b_off, &c->b_len, &c->big_list, &c->slow_list, &c->miss, &c->info, &c->tsum,
                  &c->bdata, &c->boff64, &c->blb, &c->bbig, &c->crc_rec, &c->crc_base, &c->crc_part, &c->tpl, &c->spec,
-                 &c->dq, &c->dq_cnt, &c->lmask, &c->rlist, &c->fr_tab, &c->fr_dev, &c->rg_tsum};
+                 &c->dq, &c->dq_cnt, &c->lmask, &c->rlist, &c->fr_tab, &c->fr_dev, &c->rg_tsum, &c->sel_buf};
   for (DBuf* b : all) b->release();
   if (c->order_ev) (void)hipEventDestroy(c->order_ev);
   for (hipEvent_t e : c->dense_ev)
@@ -328,7 +333,7 @@ int tfrg_ctx_device_bytes(tfrg_ctx* c, uint64_t* bytes, uint64_t* reruns) {
                        &c->totals, &c->kind_totals, &c->i64, &c->f32, &c->b_off, &c->b_len, &c->big_list,
                        &c->slow_list, &c->miss, &c->info, &c->tsum, &c->bdata, &c->boff64, &c->blb, &c->bbig,
                        &c->crc_rec, &c->crc_base, &c->crc_part, &c->tpl, &c->spec, &c->dq, &c->dq_cnt, &c->lmask,
-                       &c->rlist, &c->fr_tab, &c->fr_dev, &c->rg_tsum};
+                       &c->rlist, &c->fr_tab, &c->fr_dev, &c->rg_tsum, &c->sel_buf};
   uint64_t t = 0;
   for (const DBuf* b : all) t += b->cap;
   if (bytes) *bytes = t;
@@ -359,6 +364,16 @@ int tfrg_ctx_set_ragged_tile(tfrg_ctx* c, uint32_t rows) {
     return TFRG_E_ARG;
   }
   c->ragged_tile = rows ? rows : kRaggedTileDefault;
+  return 0;
+}
+
+int tfrg_ctx_set_select_tile(tfrg_ctx* c, uint32_t rows) {
+  if (!c) return TFRG_E_ARG;
+  if (rows && (rows < kSelTileMin || rows > kSelTileMax || (rows & (rows - 1)))) {
+    set_error("select tile must be a power of two from 64 to 4096 (0: the default)");
+    return TFRG_E_ARG;
+  }
+  c->select_tile = rows ? rows : kSelTileDefault;
   return 0;
 }
 
@@ -1377,6 +1392,131 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
     }
     if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 8, st));
+  }
+  if (cs != st) {
+    HIP_TRY(hipEventRecord(c->dense_ev[1], st));
+    HIP_TRY(hipStreamWaitEvent(cs, c->dense_ev[1], 0));
+  }
+  return 0;
+}
+
+// The WHERE clause over the last result (tfrg_select.h: verdicts, tile scan, write). Every grid size
+// comes from m and the tile: nothing is read back from the device.
+int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t n_terms, const void* d_rows,
+                            uint32_t rows_dtype, uint32_t m, int64_t row0, void* d_out, uint32_t out_dtype,
+                            uint64_t cap, uint64_t* d_count, uint32_t* d_stats, uint32_t flags, void* consumer_stream) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_result_select_rows: " + why);
+    return TFRG_E_ARG;
+  };
+  if (!c) return bad("no context");
+  if (!c->have_result) return bad("no result (decode first)");
+  static_assert(TFRG_SEL_MAX_TERMS == kSelMaxTerms && TFRG_SEL_VALUE == kSelValue && TFRG_SEL_ANY == kSelAny &&
+                    TFRG_SEL_COUNT == kSelCount && TFRG_SEL_BYTES_LEN == kSelBytesLen &&
+                    TFRG_SEL_STATUS == kSelStatus && TFRG_SEL_EQ == kSelEq && TFRG_SEL_GE == kSelGe &&
+                    sizeof(tfrg_select_term) == 32,
+                "tfrg.h mirrors tfrg_select.h");
+  if (n_terms > TFRG_SEL_MAX_TERMS) return bad("n_terms must be at most " + std::to_string(TFRG_SEL_MAX_TERMS));
+  if (n_terms && !terms) return bad("terms is NULL");
+  for (uint32_t i = 0; i < n_terms; ++i) {
+    const tfrg_select_term& t = terms[i];
+    const std::string at = "term " + std::to_string(i) + ": ";
+    if (t.slot >= c->n_slots) return bad(at + "slot " + std::to_string(t.slot) + " >= n_slots");
+    if (t.subject > TFRG_SEL_STATUS) return bad(at + "unknown subject " + std::to_string(t.subject));
+    if (t.op > TFRG_SEL_GE) return bad(at + "unknown op " + std::to_string(t.op));
+    if (t.group >= 32) return bad(at + "group must be below 32");
+    const uint32_t kind = c->slot_kind_h[t.slot] & 3u;
+    const bool list = t.subject == TFRG_SEL_VALUE || t.subject == TFRG_SEL_ANY;
+    if ((list && kind != TFRG_KIND_INT64 && kind != TFRG_KIND_FLOAT) ||
+        (t.subject == TFRG_SEL_BYTES_LEN && kind != TFRG_KIND_BYTES) || (t.subject == TFRG_SEL_STATUS && t.slot != 0))
+      return bad(at + "subject " + std::to_string(t.subject) + " does not fit slot " + std::to_string(t.slot) +
+                 " of kind " + std::to_string(kind));
+    if (t.index && t.subject != TFRG_SEL_VALUE) return bad(at + "index must be 0 outside TFRG_SEL_VALUE");
+    if (t.reserved) return bad(at + "reserved must be 0");
+    if (list && kind == TFRG_KIND_FLOAT && (t.operand >> 32)) return bad(at + "a float operand has its high 32 bits set");
+  }
+  if (d_rows && rows_dtype != TFRG_ROWS_I32 && rows_dtype != TFRG_ROWS_I64)
+    return bad("rows_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(rows_dtype));
+  if (out_dtype != TFRG_ROWS_I32 && out_dtype != TFRG_ROWS_I64)
+    return bad("out_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(out_dtype));
+  if (m >= 0x80000000u) return bad("m must be below 2^31");
+  if (!d_count) return bad("d_count is NULL");
+  if (((uintptr_t)d_count & 7u) || ((uintptr_t)d_out & (out_dtype == TFRG_ROWS_I64 ? 7u : 3u)))
+    return bad("d_out and d_count must be aligned to their element size");
+  if (out_dtype == TFRG_ROWS_I32 && c->n &&
+      (row0 < (int64_t)INT32_MIN || row0 > (int64_t)INT32_MAX - ((int64_t)c->n - 1)))
+    return bad("rows [row0, row0 + n) do not fit an int32 output");
+  if (flags & ~TFRG_SEL_APPEND) return bad("unknown flag bits");
+  const bool append = (flags & TFRG_SEL_APPEND) != 0;
+  HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = confirm_pending(c)) return rc;
+  const uint32_t tile = c->select_tile;
+  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile, nwords = ((uint64_t)m + 63) / 64;
+  const bool run = m && c->n;
+  if (run) HIP_TRY(c->sel_buf.ensure((size_t)(nwords + tiles) * 8));
+  const hipStream_t st = c->last_stream;
+  const hipStream_t cs = consumer_stream ? static_cast<hipStream_t>(consumer_stream) : st;
+  if (cs != st) {
+    for (hipEvent_t& e : c->dense_ev)
+      if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->dense_ev[0], cs));
+    HIP_TRY(hipStreamWaitEvent(st, c->dense_ev[0], 0));
+  }
+  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, 8, st));
+  if (run) {
+    SelectArgs a{};
+    a.rs = c->rs.as<uint32_t>();
+    a.slot_base = c->slot_base.as<uint64_t>();
+    // (a record without the value reads element 0 of a value array and drops it: an array that was
+    // never allocated is stood in for by the slot bases, which every result has)
+    auto col = [&](const DBuf& b) { return b.p ? b.p : c->slot_base.p; };
+    a.i64 = static_cast<const int64_t*>(col(c->i64));
+    a.f32 = static_cast<const uint32_t*>(col(c->f32));
+    a.b_len = static_cast<const uint32_t*>(col(c->b_len));
+    if (c->materialized) a.b_off64 = static_cast<const uint64_t*>(col(c->boff64));
+    a.status = (c->last_implicit & TFRG_IMPLICIT_STATUS) ? nullptr : c->status.as<int32_t>();
+    a.info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
+    a.stats = d_stats;
+    a.count = d_count;
+    a.words = c->sel_buf.as<uint64_t>();
+    a.tsum = a.words + nwords;
+    a.rows = d_rows;
+    a.out = d_out;
+    a.cap = d_out ? cap : 0;
+    a.row0 = row0;
+    a.m = m;
+    a.rows64 = rows_dtype == TFRG_ROWS_I64;
+    a.out64 = out_dtype == TFRG_ROWS_I64;
+    a.n = c->n;
+    a.n_terms = n_terms;
+    a.tile = tile;
+    a.tiles = (uint32_t)tiles;
+    a.append = append;
+    const bool const_len = (c->last_implicit & TFRG_IMPLICIT_BYTES_LEN) != 0;
+    for (uint32_t i = 0; i < n_terms; ++i) {
+      const tfrg_select_term& t = terms[i];
+      SelTerm& d = a.term[i];
+      d.slot = t.slot;
+      d.subject = t.subject;
+      d.op = t.op;
+      d.group = t.group;
+      d.index = t.index;
+      d.rhs = (int64_t)t.operand;
+      const bool list = t.subject == TFRG_SEL_VALUE || t.subject == TFRG_SEL_ANY;
+      if (list && (c->slot_kind_h[t.slot] & 3u) == TFRG_KIND_FLOAT) {
+        d.is_float = 1;
+        d.rhs_nan = sel_float_nan((uint32_t)t.operand);
+        d.rhs = d.rhs_nan ? 0 : sel_float_key((uint32_t)t.operand);
+      }
+      d.const_len = kSelNoLen;  // (as implicit_len_runs: the column is not stored, the shapes' length holds)
+      if (const_len && t.subject == TFRG_SEL_BYTES_LEN) d.const_len = t.slot < c->const_len.size() ? c->const_len[t.slot] : 0u;
+      a.all_groups |= 1u << t.group;
+    }
+    HIP_TRY(launch_select(a, st));
+  } else {
+    // no candidate, or no record (every candidate is skipped): nothing is selected
+    if (!append) HIP_TRY(hipMemsetAsync(d_count, 0, 8, st));
+    if (d_stats && m) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 1), (int)m, 1, st));
   }
   if (cs != st) {
     HIP_TRY(hipEventRecord(c->dense_ev[1], st));

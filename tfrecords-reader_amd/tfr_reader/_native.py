@@ -138,6 +138,39 @@ RAGGED_TILE_MAX = 4096
 RAGGED_TILE_DEFAULT = 1024
 RAGGED_SCAN_THREADS = 1024
 
+
+class TfrgSelectTerm(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("subject", C.c_uint32),
+        ("op", C.c_uint32),
+        ("group", C.c_uint32),
+        ("index", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("operand", C.c_uint64),
+    ]
+
+
+SEL_MAX_TERMS = 32
+SEL_VALUE = 0  # tfrg_select_term.subject (TFRG_SEL_*)
+SEL_ANY = 1
+SEL_COUNT = 2
+SEL_BYTES_LEN = 3
+SEL_STATUS = 4
+SEL_EQ = 0  # tfrg_select_term.op
+SEL_NE = 1
+SEL_LT = 2
+SEL_LE = 3
+SEL_GT = 4
+SEL_GE = 5
+SEL_APPEND = 1  # tfrg_result_select_rows flags
+# tfrg_ctx_set_select_tile's range and default (csrc/tfrg_select.h), and the tile sums its scan kernel
+# takes per pass
+SEL_TILE_MIN = 64
+SEL_TILE_MAX = 4096
+SEL_TILE_DEFAULT = 1024
+SEL_SCAN_THREADS = 1024
+
 # name -> (restype, argtypes); the exact list of exported symbols declared in include/tfrg.h
 SIGNATURES: dict[str, tuple] = {
     "tfrg_abi_version": (C.c_int, []),
@@ -218,6 +251,10 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_result_ragged_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgRaggedSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_ctx_set_ragged_tile": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "tfrg_result_select_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgSelectTerm), C.c_uint32, C.c_void_p, C.c_uint32,
+                                          C.c_uint32, C.c_int64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                          C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tfrg_ctx_set_select_tile": (C.c_int, [C.c_void_p, C.c_uint32]),
 }
 
 FLAG_PAYLOAD_ONLY = 1

@@ -556,12 +556,14 @@ def shard_dense(sd, plan: np.ndarray, specs: Sequence[Dense], *, strict: bool = 
 
 
 def minibatches(dec, specs: Sequence[Dense], batch_size: int, *, plan: np.ndarray | None = None, seed: int = 0,
-                drop_last: bool = False):
+                drop_last: bool = False, where=None):
     """One epoch of shuffled minibatches over the last decode of ``dec`` (a ``HipDecoder``, or a
     ``ShardDecoder`` with its ``plan``): yields one ``DenseBatch`` of ``batch_size`` rows per step
     (the last one shorter, or left out with ``drop_last``). The order is a ``torch.randperm`` on the
     device from a generator seeded with ``seed``; every step is one launch per decoded batch over the
-    columns where the decode left them, with no host synchronisation after the first."""
+    columns where the decode left them, with no host synchronisation after the first. ``where``
+    (``tfr_reader.select`` terms): the epoch covers the records that pass, each once -- one select and
+    one read-back of its count, then the selected rows permuted with the seeded generator."""
     import torch  # noqa: PLC0415
 
     if not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
@@ -576,7 +578,13 @@ def minibatches(dec, specs: Sequence[Dense], batch_size: int, *, plan: np.ndarra
     dev = torch.device("cuda", dec.device)
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))
-    perm = torch.randperm(n, generator=gen, device=dev)
+    if where is None:
+        perm = torch.randperm(n, generator=gen, device=dev)
+    else:
+        from tfr_reader import select as SEL  # noqa: PLC0415
+
+        perm = SEL.selected_permutation(dec, where, plan, seed)
+        n = int(perm.numel())
     for lo in range(0, n, int(batch_size)):
         hi = min(lo + int(batch_size), n)
         if drop_last and hi - lo < batch_size:

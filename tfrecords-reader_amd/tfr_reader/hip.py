@@ -493,12 +493,12 @@ class HipDecoder:
 
         return D.decoder_dense(self, specs, strict=strict, out=out, stream=stream, rows=rows)
 
-    def minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False):
-        """One epoch of shuffled ``batch_size``-row ``DenseBatch``es over the last decode, one launch
-        per step; see ``tfr_reader.dense.minibatches``."""
+    def minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False, where=None):
+        """One epoch of shuffled ``batch_size``-row ``DenseBatch``es over the last decode (``where``:
+        over its records that pass), one launch per step; see ``tfr_reader.dense.minibatches``."""
         from tfr_reader import dense as D  # noqa: PLC0415
 
-        return D.minibatches(self, specs, batch_size, seed=seed, drop_last=drop_last)
+        return D.minibatches(self, specs, batch_size, seed=seed, drop_last=drop_last, where=where)
 
     def set_ragged_tile(self, rows: int) -> None:
         """Rows per workgroup tile of ``ragged`` (a power of two from 64 to 4096; 0: the default 1024)."""
@@ -512,12 +512,26 @@ class HipDecoder:
 
         return R.decoder_ragged(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
 
-    def ragged_minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False, capacity=None):
-        """One epoch of shuffled ``batch_size``-row ``RaggedBatch``es over the last decode; see
-        ``tfr_reader.ragged.ragged_minibatches``."""
+    def ragged_minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False, capacity=None,
+                           where=None):
+        """One epoch of shuffled ``batch_size``-row ``RaggedBatch``es over the last decode (``where``:
+        over its records that pass); see ``tfr_reader.ragged.ragged_minibatches``."""
         from tfr_reader import ragged as R  # noqa: PLC0415
 
-        return R.ragged_minibatches(self, specs, batch_size, seed=seed, drop_last=drop_last, capacity=capacity)
+        return R.ragged_minibatches(self, specs, batch_size, seed=seed, drop_last=drop_last, capacity=capacity,
+                                    where=where)
+
+    def set_select_tile(self, rows: int) -> None:
+        """Candidates per workgroup tile of ``select`` (a power of two from 64 to 4096; 0: the default 1024)."""
+        N.check(self._lib.tfrg_ctx_set_select_tile(self._ctx, int(rows)), "tfrg_ctx_set_select_tile")
+
+    def select(self, where, *, rows=None, capacity=None, dtype: str = "int64", out=None, stream: int | None = None):
+        """The rows of the last decode that pass ``where`` (``tfr_reader.select.Term``s), as a row
+        list on this decoder's device that ``dense`` / ``ragged`` take as ``rows=``
+        (tfrg_result_select_rows); see ``tfr_reader.select.decoder_select``."""
+        from tfr_reader import select as S  # noqa: PLC0415
+
+        return S.decoder_select(self, where, rows=rows, capacity=capacity, dtype=dtype, out=out, stream=stream)
 
     def _fetch(self, buf, st, en, info: N.TfrgInfo, payload_only: bool, materialize: bool = False) -> BatchResult:
         n, ns = info.n_records, info.n_slots
@@ -795,6 +809,15 @@ class BatchResult:
         from tfr_reader import ragged as R  # noqa: PLC0415
 
         return R.batch_ragged(self, specs, rows)
+
+    def select(self, where, rows=None, row0: int = 0):
+        """The candidates that pass ``where`` (``tfr_reader.select.Term``s), from the fetched columns
+        (the host counterpart of ``HipDecoder.select``): (their entries in candidate order as int64,
+        (selected, skipped)). ``rows``: candidate k is record ``rows[k] - row0``, skipped where that is
+        out of range; None: every record in order."""
+        from tfr_reader import select as S  # noqa: PLC0415
+
+        return S.batch_select(self, where, rows, row0)
 
 
 class _Layout:

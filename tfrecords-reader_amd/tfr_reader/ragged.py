@@ -328,11 +328,13 @@ def decoder_ragged(dec, specs: Sequence[Ragged], *, rows=None, capacity=None, ou
 
 
 def ragged_minibatches(dec, specs: Sequence[Ragged], batch_size: int, *, seed: int = 0, drop_last: bool = False,
-                       capacity=None):
+                       capacity=None, where=None):
     """One epoch of shuffled ragged minibatches over the last decode of ``dec``: yields one
     ``RaggedBatch`` of ``batch_size`` rows per step (the last one shorter, or left out with
     ``drop_last``), in the order of a ``torch.randperm`` on the device seeded with ``seed``, as
-    ``dense.minibatches``. With ``capacity`` no step synchronises with the host."""
+    ``dense.minibatches``. With ``capacity`` no step synchronises with the host. ``where``
+    (``tfr_reader.select`` terms): the epoch covers the records that pass, each once (one select and
+    one read-back of its count before the first step)."""
     import torch  # noqa: PLC0415
 
     if not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
@@ -344,7 +346,13 @@ def ragged_minibatches(dec, specs: Sequence[Ragged], batch_size: int, *, seed: i
     dev = torch.device("cuda", dec.device)
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))
-    perm = torch.randperm(n, generator=gen, device=dev)
+    if where is None:
+        perm = torch.randperm(n, generator=gen, device=dev)
+    else:
+        from tfr_reader import select as SEL  # noqa: PLC0415
+
+        perm = SEL.selected_permutation(dec, where, None, seed)
+        n = int(perm.numel())
     for lo in range(0, n, int(batch_size)):
         hi = min(lo + int(batch_size), n)
         if drop_last and hi - lo < batch_size:

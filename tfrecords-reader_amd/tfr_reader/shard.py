@@ -385,12 +385,22 @@ class ShardDecoder:
 
         return D.shard_dense(self, plan, specs, strict=strict, out=out, stream=stream, rows=rows)
 
-    def minibatches(self, plan: np.ndarray, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False):
-        """One epoch of shuffled ``batch_size``-row ``DenseBatch``es over the plan's last decode; see
-        ``tfr_reader.dense.minibatches``."""
+    def minibatches(self, plan: np.ndarray, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False,
+                    where=None):
+        """One epoch of shuffled ``batch_size``-row ``DenseBatch``es over the plan's last decode
+        (``where``: over its rows that pass); see ``tfr_reader.dense.minibatches``."""
         from tfr_reader import dense as D  # noqa: PLC0415
 
-        return D.minibatches(self, specs, batch_size, plan=plan, seed=seed, drop_last=drop_last)
+        return D.minibatches(self, specs, batch_size, plan=plan, seed=seed, drop_last=drop_last, where=where)
+
+    def select(self, plan: np.ndarray, where, *, rows=None, capacity=None, dtype: str = "int64", out=None,
+               stream: int | None = None):
+        """The rows of the plan's last decode that pass ``where`` (``tfr_reader.select.Term``s), as one
+        device row list numbering the plan's rows: every batch context appends what it holds, in plan
+        order (tfrg_result_select_rows with TFRG_SEL_APPEND); see ``tfr_reader.select.shard_select``."""
+        from tfr_reader import select as S  # noqa: PLC0415
+
+        return S.shard_select(self, plan, where, rows=rows, capacity=capacity, dtype=dtype, out=out, stream=stream)
 
     def device_bytes(self) -> tuple[int, int]:
         """(device memory of every batch context, decodes re-run so far: a value hint too small or
