@@ -213,3 +213,24 @@ def test_result_select_rows_without_a_context_is_an_argument_error():
     assert lib.tfrg_ctx_set_select_tile(None, 64) == -1
     assert (N.SEL_VALUE, N.SEL_ANY, N.SEL_COUNT, N.SEL_BYTES_LEN, N.SEL_STATUS) == (0, 1, 2, 3, 4)
     assert (N.SEL_EQ, N.SEL_NE, N.SEL_LT, N.SEL_LE, N.SEL_GT, N.SEL_GE) == (0, 1, 2, 3, 4, 5)
+
+
+def test_no_context_is_reported_first_and_in_the_same_words_by_every_result_entry_point():
+    """The exact text, and that a missing context is reported before any other defect of the call
+    (a count of 0, a NULL spec table); tests/test_result_args_gpu.py pins the checks that need a
+    context."""
+    lib = N.lib()
+    dense = N.TfrgDenseSpec(slot=0, dtype=N.DENSE_I64, width=1, reserved=0, fill=0, out=16, lengths=None)
+    ragged = N.TfrgRaggedSpec(slot=0, dtype=N.DENSE_I64, max_len=0, reserved=0, cap=0, values=None, offsets=16)
+    term = N.TfrgSelectTerm(slot=0, subject=N.SEL_VALUE, op=N.SEL_EQ, group=0, index=0, reserved=0, operand=1)
+    for n, d, r, t in ((1, C.byref(dense), C.byref(ragged), C.byref(term)), (0, None, None, None)):
+        assert lib.tfrg_result_dense(None, d, n, None, None) == -1
+        assert lib.tfrg_last_error() == b"tfrg_result_dense: no context"
+        assert lib.tfrg_result_dense_rows(None, d, n, C.c_void_p(16), 7, 1 << 31, 0, None, None, None) == -1
+        assert lib.tfrg_last_error() == b"tfrg_result_dense_rows: no context"
+        assert lib.tfrg_result_ragged_rows(None, r, n, C.c_void_p(16), 7, 1 << 31, 0, None, None, None) == -1
+        assert lib.tfrg_last_error() == b"tfrg_result_ragged_rows: no context"
+        rc = lib.tfrg_result_select_rows(None, t, 33 if n == 0 else 1, C.c_void_p(16), 7, 1 << 31, 0, None, 7, 1, None,
+                                         None, 2, None)
+        assert rc == -1
+        assert lib.tfrg_last_error() == b"tfrg_result_select_rows: no context"

@@ -117,7 +117,7 @@ struct tfrg_ctx {
   uint32_t n = 0;
   uint64_t cap_hint = 0;  // tfrg_decode_host: total bytes of the given ranges (>= nbytes when they overlap)
   hipEvent_t order_ev = nullptr;  // orders a decode on a new stream after the previous one
-  hipEvent_t dense_ev[2] = {nullptr, nullptr};  // tfrg_result_dense: consumer stream -> decode stream -> consumer
+  hipEvent_t consumer_ev[2] = {nullptr, nullptr};  // fence_open / fence_close: consumer stream -> decode stream -> consumer
   int dense_nt = 0;  // k_dense's output stores nontemporal (env TFRG_DENSE_NT=1, for A/B measurements)
   uint64_t nbytes = 0;
   uint64_t cap_i64 = 0, cap_f32 = 0, cap_b = 0;
@@ -294,7 +294,7 @@ int tfrg_ctx_destroy(tfrg_ctx* c) {
                  &c->dq, &c->dq_cnt, &c->lmask, &c->rlist, &c->fr_tab, &c->fr_dev, &c->rg_tsum, &c->sel_buf};
   for (DBuf* b : all) b->release();
   if (c->order_ev) (void)hipEventDestroy(c->order_ev);
-  for (hipEvent_t e : c->dense_ev)
+  for (hipEvent_t e : c->consumer_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->have_events)
     for (auto& e : c->ev) (void)hipEventDestroy(e);
@@ -1137,6 +1137,105 @@ int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
   return 0;
 }
 
+// ---- Host-side setup shared by the entry points over the last result (tfrg_result_dense / _dense_rows,
+// _ragged_rows, _select_rows). `bad` is the entry point's own: it prefixes the function's name.
+extern "C++" {
+template <class Bad>
+static int check_result(const tfrg_ctx* c, const Bad& bad) {
+  if (!c) return bad("no context");
+  if (!c->have_result) return bad("no result (decode first)");
+  return 0;
+}
+template <class Bad>
+static int check_specs(const tfrg_ctx* c, const void* specs, uint32_t n_specs, uint32_t max_specs, const Bad& bad) {
+  if (const int rc = check_result(c, bad)) return rc;
+  if (!specs || n_specs == 0 || n_specs > max_specs) return bad("n_specs must be 1.." + std::to_string(max_specs));
+  return 0;
+}
+// (the spec's slot exists and its TFRG_DENSE_* dtype fits the slot's kind)
+template <class Bad>
+static int check_slot_dtype(const tfrg_ctx* c, const std::string& at, uint32_t slot, uint32_t dtype, const Bad& bad) {
+  if (slot >= c->n_slots) return bad(at + "slot " + std::to_string(slot) + " >= n_slots");
+  const uint32_t kind = c->slot_kind_h[slot] & 3u;
+  const bool fits = (kind == TFRG_KIND_INT64 && (dtype == TFRG_DENSE_I64 || dtype == TFRG_DENSE_I32)) ||
+                    (kind == TFRG_KIND_FLOAT && dtype == TFRG_DENSE_F32) ||
+                    (kind == TFRG_KIND_BYTES && dtype == TFRG_DENSE_U8);
+  if (!fits) return bad(at + "dtype " + std::to_string(dtype) + " does not fit the slot's kind " + std::to_string(kind));
+  return 0;
+}
+// The row list. tfrg_result_dense_rows always has one (`required`): its rows_dtype is checked whatever
+// d_rows is, and m > 0 rows need a d_rows. Ragged and select take a NULL d_rows as the identity list and
+// read rows_dtype only beside a list. (Two functions: select checks its out_dtype between them.)
+template <class Bad>
+static int check_rows_dtype(const void* d_rows, uint32_t rows_dtype, bool required, const Bad& bad) {
+  if ((required || d_rows) && rows_dtype != TFRG_ROWS_I32 && rows_dtype != TFRG_ROWS_I64)
+    return bad("rows_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(rows_dtype));
+  return 0;
+}
+template <class Bad>
+static int check_rows_m(const void* d_rows, uint32_t m, bool required, const Bad& bad) {
+  if (m >= 0x80000000u) return bad("m must be below 2^31");
+  if (required && m && !d_rows) return bad("d_rows is NULL");
+  return 0;
+}
+
+// (a record without a value reads element 0 of a value array and drops it: an array that was never
+// allocated is stood in for by the slot bases, which every result has)
+template <class T>
+static const T* view_col(const tfrg_ctx* c, const DBuf& b) {
+  return static_cast<const T*>(b.p ? b.p : c->slot_base.p);
+}
+// The column view of the last result: what DenseArgs, RaggedArgs and SelectArgs have in common
+template <class Args>
+static void fill_columns(const tfrg_ctx* c, Args& a) {
+  a.rs = c->rs.as<uint32_t>();
+  a.slot_base = c->slot_base.as<uint64_t>();
+  a.i64 = view_col<int64_t>(c, c->i64);
+  a.f32 = view_col<uint32_t>(c, c->f32);
+  a.b_len = view_col<uint32_t>(c, c->b_len);
+  if (c->materialized) a.b_off64 = view_col<uint64_t>(c, c->boff64);
+  a.info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
+  a.n = c->n;
+}
+// The bytes' source: the views' input buffer, readable to round_up(nbytes, 16), or the byte column
+template <class Args>
+static void fill_bytes_source(const tfrg_ctx* c, Args& a) {
+  a.b_off = view_col<uint32_t>(c, c->b_off);
+  a.in = c->materialized ? c->bdata.as<uint8_t>() : c->last.d_bytes;
+  const uint64_t bound = c->materialized ? (uint64_t)c->bdata.cap & ~15ull : (c->last.nbytes + 15ull) & ~15ull;
+  a.in_bound = a.in ? (uint32_t)std::min<uint64_t>(bound, 0xfffffff0ull) : 0;
+}
+}  // extern "C++"
+
+// A bytes slot's constant element length where the last decode did not store the bytes_len column (as
+// implicit_len_runs: the shapes' length holds); else, or for a spec / term that reads no length, the
+// kernels' "the column is stored" sentinel.
+static_assert(kDenseNoLen == kRaggedNoLen && kRaggedNoLen == kSelNoLen, "one const_len lookup serves all three");
+static uint32_t const_len_of(const tfrg_ctx* c, uint32_t slot, bool reads_len) {
+  if (!reads_len || !(c->last_implicit & TFRG_IMPLICIT_BYTES_LEN)) return kDenseNoLen;
+  return slot < c->const_len.size() ? c->const_len[slot] : 0u;
+}
+
+// The consumer-stream fence: the work an entry point puts on the decode's stream *st starts after what
+// the consumer stream *cs holds so far (fence_open), and the consumer waits for it (fence_close). A
+// NULL consumer_stream is the decode's own stream: no fence.
+static int fence_open(tfrg_ctx* c, void* consumer_stream, hipStream_t* st, hipStream_t* cs) {
+  *st = c->last_stream;
+  *cs = consumer_stream ? static_cast<hipStream_t>(consumer_stream) : *st;
+  if (*cs == *st) return 0;
+  for (hipEvent_t& e : c->consumer_ev)
+    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(c->consumer_ev[0], *cs));
+  HIP_TRY(hipStreamWaitEvent(*st, c->consumer_ev[0], 0));
+  return 0;
+}
+static int fence_close(tfrg_ctx* c, hipStream_t st, hipStream_t cs) {
+  if (cs == st) return 0;
+  HIP_TRY(hipEventRecord(c->consumer_ev[1], st));
+  HIP_TRY(hipStreamWaitEvent(cs, c->consumer_ev[1], 0));
+  return 0;
+}
+
 // The row list of tfrg_result_dense_rows (d_rows null: tfrg_result_dense, every record in order)
 struct DenseRows {
   const void* d_rows = nullptr;
@@ -1151,10 +1250,7 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
     set_error(std::string(fn) + ": " + why);
     return TFRG_E_ARG;
   };
-  if (!c) return bad("no context");
-  if (!c->have_result) return bad("no result (decode first)");
-  if (!specs || n_specs == 0 || n_specs > TFRG_DENSE_MAX_SPECS)
-    return bad("n_specs must be 1.." + std::to_string(TFRG_DENSE_MAX_SPECS));
+  if (const int rc = check_specs(c, specs, n_specs, TFRG_DENSE_MAX_SPECS, bad)) return rc;
   static_assert(TFRG_DENSE_MAX_SPECS == kDenseMaxSpecs && TFRG_DENSE_MAX_WIDTH == kDenseMaxWidth &&
                     TFRG_DENSE_I64 == kDenseI64 && TFRG_DENSE_I32 == kDenseI32 && TFRG_DENSE_F32 == kDenseF32 &&
                     TFRG_DENSE_U8 == kDenseU8,
@@ -1162,22 +1258,15 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
   for (uint32_t i = 0; i < n_specs; ++i) {
     const tfrg_dense_spec& s = specs[i];
     const std::string at = "spec " + std::to_string(i) + ": ";
-    if (s.slot >= c->n_slots) return bad(at + "slot " + std::to_string(s.slot) + " >= n_slots");
-    const uint32_t kind = c->slot_kind_h[s.slot] & 3u;
-    const bool fits = (kind == TFRG_KIND_INT64 && (s.dtype == TFRG_DENSE_I64 || s.dtype == TFRG_DENSE_I32)) ||
-                      (kind == TFRG_KIND_FLOAT && s.dtype == TFRG_DENSE_F32) ||
-                      (kind == TFRG_KIND_BYTES && s.dtype == TFRG_DENSE_U8);
-    if (!fits) return bad(at + "dtype " + std::to_string(s.dtype) + " does not fit the slot's kind " + std::to_string(kind));
+    if (const int rc = check_slot_dtype(c, at, s.slot, s.dtype, bad)) return rc;
     if (s.width == 0 || s.width > TFRG_DENSE_MAX_WIDTH)
       return bad(at + "width must be 1.." + std::to_string(TFRG_DENSE_MAX_WIDTH));
     if (!s.out) return bad(at + "out is NULL");
     if (s.reserved) return bad(at + "reserved must be 0");
   }
   if (by_rows) {
-    if (rows.dtype != TFRG_ROWS_I32 && rows.dtype != TFRG_ROWS_I64)
-      return bad("rows_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(rows.dtype));
-    if (rows.m >= 0x80000000u) return bad("m must be below 2^31");
-    if (rows.m && !rows.d_rows) return bad("d_rows is NULL");
+    if (const int rc = check_rows_dtype(rows.d_rows, rows.dtype, true, bad)) return rc;
+    if (const int rc = check_rows_m(rows.d_rows, rows.m, true, bad)) return rc;
   }
   if (!by_rows && c->n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
@@ -1192,32 +1281,11 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
     a.row0 = rows.row0;
     a.skipped = rows.d_skipped;
   }
-  a.rs = c->rs.as<uint32_t>();
-  a.slot_base = c->slot_base.as<uint64_t>();
-  // (k_dense reads element 0 of a value array for a record without a value, and drops it: an array
-  // that was never allocated is stood in for by the slot bases, which every result has)
-  auto col = [&](const DBuf& b) { return b.p ? b.p : c->slot_base.p; };
-  a.i64 = static_cast<const int64_t*>(col(c->i64));
-  a.f32 = static_cast<const uint32_t*>(col(c->f32));
-  a.b_off = static_cast<const uint32_t*>(col(c->b_off));
-  a.b_len = static_cast<const uint32_t*>(col(c->b_len));
-  // the bytes' source: the views' input buffer, readable to round_up(nbytes, 16), or the byte column
-  uint64_t bound;
-  if (c->materialized) {
-    a.b_off64 = static_cast<const uint64_t*>(col(c->boff64));
-    a.in = c->bdata.as<uint8_t>();
-    bound = c->bdata.p ? (uint64_t)c->bdata.cap & ~15ull : 0;
-  } else {
-    a.in = c->last.d_bytes;
-    bound = a.in ? (c->last.nbytes + 15ull) & ~15ull : 0;
-  }
-  a.in_bound = (uint32_t)std::min<uint64_t>(bound, 0xfffffff0ull);
-  a.info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
+  fill_columns(c, a);
+  fill_bytes_source(c, a);
   a.stats = d_stats;
-  a.n = c->n;
   a.n_specs = n_specs;
   a.nt = (uint32_t)c->dense_nt;
-  const bool const_len = (c->last_implicit & TFRG_IMPLICIT_BYTES_LEN) != 0;
   // workgroups per spec: one per chunk of its output, within an even share of 16 per CU
   const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 16u / n_specs);
   uint32_t blocks = 0;
@@ -1230,8 +1298,7 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
     d.slot = s.slot;
     d.dtype = s.dtype;
     d.width = s.width;
-    d.const_len = kDenseNoLen;  // (as implicit_len_runs: the column is not stored, the shapes' length holds)
-    if (const_len && s.dtype == TFRG_DENSE_U8) d.const_len = s.slot < c->const_len.size() ? c->const_len[s.slot] : 0u;
+    d.const_len = const_len_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
     const uint64_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
     const uint64_t total = (uint64_t)out_rows * s.width * isz;
     // 16-byte units, or single elements where the output's base is not 16-byte aligned
@@ -1240,14 +1307,8 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
     d.nblk = (uint32_t)std::min<uint64_t>(cap, (work + kDenseChunk - 1) / kDenseChunk);
     blocks += d.nblk;
   }
-  const hipStream_t st = c->last_stream;
-  const hipStream_t cs = consumer_stream ? static_cast<hipStream_t>(consumer_stream) : st;
-  if (cs != st) {
-    for (hipEvent_t& e : c->dense_ev)
-      if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->dense_ev[0], cs));
-    HIP_TRY(hipStreamWaitEvent(st, c->dense_ev[0], 0));
-  }
+  hipStream_t st, cs;
+  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
   // (counters that lie back to back, stats first, are zeroed by one memset: one launch less per step)
   const bool one_memset = by_rows && c->n && d_stats && rows.d_skipped == d_stats + 4 * (size_t)n_specs;
   if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * (one_memset ? 20 : 16), st));
@@ -1255,11 +1316,7 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
   if (by_rows && rows.d_skipped && !one_memset)
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rows.d_skipped), c->n ? 0 : (int)rows.m, n_specs, st));
   if (out_rows && c->n) HIP_TRY(launch_dense(a, blocks, st));
-  if (cs != st) {
-    HIP_TRY(hipEventRecord(c->dense_ev[1], st));
-    HIP_TRY(hipStreamWaitEvent(cs, c->dense_ev[1], 0));
-  }
-  return 0;
+  return fence_close(c, st, cs);
 }
 
 int tfrg_result_dense(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_specs, uint32_t* d_stats,
@@ -1288,21 +1345,13 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
     set_error("tfrg_result_ragged_rows: " + why);
     return TFRG_E_ARG;
   };
-  if (!c) return bad("no context");
-  if (!c->have_result) return bad("no result (decode first)");
-  if (!specs || n_specs == 0 || n_specs > TFRG_RAGGED_MAX_SPECS)
-    return bad("n_specs must be 1.." + std::to_string(TFRG_RAGGED_MAX_SPECS));
+  if (const int rc = check_specs(c, specs, n_specs, TFRG_RAGGED_MAX_SPECS, bad)) return rc;
   static_assert(TFRG_RAGGED_MAX_SPECS == kRaggedMaxSpecs, "tfrg.h mirrors tfrg_ragged.h");
   bool any_values = false;
   for (uint32_t i = 0; i < n_specs; ++i) {
     const tfrg_ragged_spec& s = specs[i];
     const std::string at = "spec " + std::to_string(i) + ": ";
-    if (s.slot >= c->n_slots) return bad(at + "slot " + std::to_string(s.slot) + " >= n_slots");
-    const uint32_t kind = c->slot_kind_h[s.slot] & 3u;
-    const bool fits = (kind == TFRG_KIND_INT64 && (s.dtype == TFRG_DENSE_I64 || s.dtype == TFRG_DENSE_I32)) ||
-                      (kind == TFRG_KIND_FLOAT && s.dtype == TFRG_DENSE_F32) ||
-                      (kind == TFRG_KIND_BYTES && s.dtype == TFRG_DENSE_U8);
-    if (!fits) return bad(at + "dtype " + std::to_string(s.dtype) + " does not fit the slot's kind " + std::to_string(kind));
+    if (const int rc = check_slot_dtype(c, at, s.slot, s.dtype, bad)) return rc;
     if (!s.offsets) return bad(at + "offsets is NULL");
     if (s.reserved) return bad(at + "reserved must be 0");
     const uintptr_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
@@ -1310,9 +1359,8 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
       return bad(at + "values and offsets must be aligned to their element size");
     any_values |= s.values != nullptr && s.cap != 0;
   }
-  if (d_rows && rows_dtype != TFRG_ROWS_I32 && rows_dtype != TFRG_ROWS_I64)
-    return bad("rows_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(rows_dtype));
-  if (m >= 0x80000000u) return bad("m must be below 2^31");
+  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
+  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
   const uint32_t tile = c->ragged_tile;
   const uint64_t tiles = ((uint64_t)m + tile - 1) / tile;
   // workgroups per tile that share its span: up to kRaggedMaxSplit while the launch is below 4 per CU
@@ -1326,38 +1374,13 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
   if (const int rc = confirm_pending(c)) return rc;
   const bool run = m && c->n;
   if (run) HIP_TRY(c->rg_tsum.ensure((size_t)(tiles * n_specs) * 8));
-  const hipStream_t st = c->last_stream;
-  const hipStream_t cs = consumer_stream ? static_cast<hipStream_t>(consumer_stream) : st;
-  if (cs != st) {
-    for (hipEvent_t& e : c->dense_ev)
-      if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->dense_ev[0], cs));
-    HIP_TRY(hipStreamWaitEvent(st, c->dense_ev[0], 0));
-  }
+  hipStream_t st, cs;
+  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
   if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
   if (run) {
     RaggedArgs a{};
-    a.rs = c->rs.as<uint32_t>();
-    a.slot_base = c->slot_base.as<uint64_t>();
-    // (a record without a value reads element 0 of a value array and drops it: an array that was never
-    // allocated is stood in for by the slot bases, which every result has)
-    auto col = [&](const DBuf& b) { return b.p ? b.p : c->slot_base.p; };
-    a.i64 = static_cast<const int64_t*>(col(c->i64));
-    a.f32 = static_cast<const uint32_t*>(col(c->f32));
-    a.b_off = static_cast<const uint32_t*>(col(c->b_off));
-    a.b_len = static_cast<const uint32_t*>(col(c->b_len));
-    // the bytes' source: the views' input buffer, readable to round_up(nbytes, 16), or the byte column
-    uint64_t bound;
-    if (c->materialized) {
-      a.b_off64 = static_cast<const uint64_t*>(col(c->boff64));
-      a.in = c->bdata.as<uint8_t>();
-      bound = c->bdata.p ? (uint64_t)c->bdata.cap & ~15ull : 0;
-    } else {
-      a.in = c->last.d_bytes;
-      bound = a.in ? (c->last.nbytes + 15ull) & ~15ull : 0;
-    }
-    a.in_bound = (uint32_t)std::min<uint64_t>(bound, 0xfffffff0ull);
-    a.info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
+    fill_columns(c, a);
+    fill_bytes_source(c, a);
     a.stats = d_stats;
     a.totals = d_totals;
     a.tsum = c->rg_tsum.as<uint64_t>();
@@ -1365,12 +1388,10 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
     a.rows64 = rows_dtype == TFRG_ROWS_I64;
     a.row0 = row0;
     a.m = m;
-    a.n = c->n;
     a.n_specs = n_specs;
     a.tile = tile;
     a.tiles = (uint32_t)tiles;
     a.split = (uint32_t)split;
-    const bool const_len = (c->last_implicit & TFRG_IMPLICIT_BYTES_LEN) != 0;
     for (uint32_t i = 0; i < n_specs; ++i) {
       const tfrg_ragged_spec& s = specs[i];
       RaggedSpec& d = a.sp[i];
@@ -1380,8 +1401,7 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
       d.slot = s.slot;
       d.dtype = s.dtype;
       d.max_len = s.max_len;
-      d.const_len = kRaggedNoLen;  // (as implicit_len_runs: the column is not stored, the shapes' length holds)
-      if (const_len && s.dtype == TFRG_DENSE_U8) d.const_len = s.slot < c->const_len.size() ? c->const_len[s.slot] : 0u;
+      d.const_len = const_len_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
     }
     HIP_TRY(launch_ragged(a, st));
   } else {
@@ -1393,11 +1413,7 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
     }
     if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 8, st));
   }
-  if (cs != st) {
-    HIP_TRY(hipEventRecord(c->dense_ev[1], st));
-    HIP_TRY(hipStreamWaitEvent(cs, c->dense_ev[1], 0));
-  }
-  return 0;
+  return fence_close(c, st, cs);
 }
 
 // The WHERE clause over the last result (tfrg_select.h: verdicts, tile scan, write). Every grid size
@@ -1409,8 +1425,7 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
     set_error("tfrg_result_select_rows: " + why);
     return TFRG_E_ARG;
   };
-  if (!c) return bad("no context");
-  if (!c->have_result) return bad("no result (decode first)");
+  if (const int rc = check_result(c, bad)) return rc;
   static_assert(TFRG_SEL_MAX_TERMS == kSelMaxTerms && TFRG_SEL_VALUE == kSelValue && TFRG_SEL_ANY == kSelAny &&
                     TFRG_SEL_COUNT == kSelCount && TFRG_SEL_BYTES_LEN == kSelBytesLen &&
                     TFRG_SEL_STATUS == kSelStatus && TFRG_SEL_EQ == kSelEq && TFRG_SEL_GE == kSelGe &&
@@ -1435,11 +1450,10 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
     if (t.reserved) return bad(at + "reserved must be 0");
     if (list && kind == TFRG_KIND_FLOAT && (t.operand >> 32)) return bad(at + "a float operand has its high 32 bits set");
   }
-  if (d_rows && rows_dtype != TFRG_ROWS_I32 && rows_dtype != TFRG_ROWS_I64)
-    return bad("rows_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(rows_dtype));
+  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
   if (out_dtype != TFRG_ROWS_I32 && out_dtype != TFRG_ROWS_I64)
     return bad("out_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(out_dtype));
-  if (m >= 0x80000000u) return bad("m must be below 2^31");
+  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
   if (!d_count) return bad("d_count is NULL");
   if (((uintptr_t)d_count & 7u) || ((uintptr_t)d_out & (out_dtype == TFRG_ROWS_I64 ? 7u : 3u)))
     return bad("d_out and d_count must be aligned to their element size");
@@ -1454,28 +1468,13 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
   const uint64_t tiles = ((uint64_t)m + tile - 1) / tile, nwords = ((uint64_t)m + 63) / 64;
   const bool run = m && c->n;
   if (run) HIP_TRY(c->sel_buf.ensure((size_t)(nwords + tiles) * 8));
-  const hipStream_t st = c->last_stream;
-  const hipStream_t cs = consumer_stream ? static_cast<hipStream_t>(consumer_stream) : st;
-  if (cs != st) {
-    for (hipEvent_t& e : c->dense_ev)
-      if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->dense_ev[0], cs));
-    HIP_TRY(hipStreamWaitEvent(st, c->dense_ev[0], 0));
-  }
+  hipStream_t st, cs;
+  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
   if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, 8, st));
   if (run) {
     SelectArgs a{};
-    a.rs = c->rs.as<uint32_t>();
-    a.slot_base = c->slot_base.as<uint64_t>();
-    // (a record without the value reads element 0 of a value array and drops it: an array that was
-    // never allocated is stood in for by the slot bases, which every result has)
-    auto col = [&](const DBuf& b) { return b.p ? b.p : c->slot_base.p; };
-    a.i64 = static_cast<const int64_t*>(col(c->i64));
-    a.f32 = static_cast<const uint32_t*>(col(c->f32));
-    a.b_len = static_cast<const uint32_t*>(col(c->b_len));
-    if (c->materialized) a.b_off64 = static_cast<const uint64_t*>(col(c->boff64));
+    fill_columns(c, a);
     a.status = (c->last_implicit & TFRG_IMPLICIT_STATUS) ? nullptr : c->status.as<int32_t>();
-    a.info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
     a.stats = d_stats;
     a.count = d_count;
     a.words = c->sel_buf.as<uint64_t>();
@@ -1487,12 +1486,10 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
     a.m = m;
     a.rows64 = rows_dtype == TFRG_ROWS_I64;
     a.out64 = out_dtype == TFRG_ROWS_I64;
-    a.n = c->n;
     a.n_terms = n_terms;
     a.tile = tile;
     a.tiles = (uint32_t)tiles;
     a.append = append;
-    const bool const_len = (c->last_implicit & TFRG_IMPLICIT_BYTES_LEN) != 0;
     for (uint32_t i = 0; i < n_terms; ++i) {
       const tfrg_select_term& t = terms[i];
       SelTerm& d = a.term[i];
@@ -1508,8 +1505,7 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
         d.rhs_nan = sel_float_nan((uint32_t)t.operand);
         d.rhs = d.rhs_nan ? 0 : sel_float_key((uint32_t)t.operand);
       }
-      d.const_len = kSelNoLen;  // (as implicit_len_runs: the column is not stored, the shapes' length holds)
-      if (const_len && t.subject == TFRG_SEL_BYTES_LEN) d.const_len = t.slot < c->const_len.size() ? c->const_len[t.slot] : 0u;
+      d.const_len = const_len_of(c, t.slot, t.subject == TFRG_SEL_BYTES_LEN);
       a.all_groups |= 1u << t.group;
     }
     HIP_TRY(launch_select(a, st));
@@ -1518,11 +1514,7 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
     if (!append) HIP_TRY(hipMemsetAsync(d_count, 0, 8, st));
     if (d_stats && m) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 1), (int)m, 1, st));
   }
-  if (cs != st) {
-    HIP_TRY(hipEventRecord(c->dense_ev[1], st));
-    HIP_TRY(hipStreamWaitEvent(cs, c->dense_ev[1], 0));
-  }
-  return 0;
+  return fence_close(c, st, cs);
 }
 
 int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 from collections.abc import Mapping, Sequence
 from dataclasses import dataclass
 
@@ -248,7 +249,7 @@ def resolve_slot(dec, sp: Dense) -> int | None:
     return s
 
 
-def _vp(p: int | None):
+def vp(p: int | None):
     return C.c_void_p(p) if p else None
 
 
@@ -261,11 +262,11 @@ def launch(dec, items: Sequence[tuple], stats_ptr: int | None, consumer: int | N
     for a, (slot, dt, width, fill, out, lens) in zip(arr, items):
         a.slot, a.dtype, a.width, a.reserved, a.fill, a.out, a.lengths = slot, dt, width, 0, fill, out, lens
     if rows is None:
-        N.check(dec._lib.tfrg_result_dense(dec._ctx, arr, len(items), _vp(stats_ptr), _vp(consumer)), "tfrg_result_dense")
+        N.check(dec._lib.tfrg_result_dense(dec._ctx, arr, len(items), vp(stats_ptr), vp(consumer)), "tfrg_result_dense")
         return
     ptr, m, rdt = rows
-    N.check(dec._lib.tfrg_result_dense_rows(dec._ctx, arr, len(items), _vp(ptr), rdt, m, row0, _vp(stats_ptr),
-                                            _vp(skipped_ptr), _vp(consumer)), "tfrg_result_dense_rows")
+    N.check(dec._lib.tfrg_result_dense_rows(dec._ctx, arr, len(items), vp(ptr), rdt, m, row0, vp(stats_ptr),
+                                            vp(skipped_ptr), vp(consumer)), "tfrg_result_dense_rows")
 
 
 ROW_DTYPES = {"int32": N.ROWS_I32, "int64": N.ROWS_I64}
@@ -295,7 +296,63 @@ def device_rows(rows, n: int, device: int):
         return torch.from_numpy(a).to(dev, non_blocking=True), int(a.size)
 
 
-_SIDE_STREAMS: dict = {}
+def rows_arg(rows) -> tuple[int, int]:
+    """(device pointer, TFRG_ROWS_* id) of a row tensor that ``device_rows`` returned."""
+    return rows.data_ptr(), N.ROWS_I64 if rows.element_size() == 8 else N.ROWS_I32
+
+
+@functools.cache
+def torch_dtypes() -> dict:
+    """dtype name (``DTYPES``) -> torch dtype (one table, made on first use)."""
+    import torch  # noqa: PLC0415
+
+    return {"int64": torch.int64, "int32": torch.int32, "float32": torch.float32, "uint8": torch.uint8}
+
+
+def last_n(dec) -> int:
+    """The records of ``dec``'s last decode (from ``dec.info()`` where the decoder did not note them)."""
+    n = getattr(dec, "_last_n", None)
+    return int(dec.info().n_records) if n is None else n
+
+
+class ConsumerStream:
+    """The consumer stream of library calls made for the torch stream ``cur``; the calls are given
+    ``handle``. The legacy default stream (handle 0, which NULL would not name) is stood in for by one
+    side stream per device: ``begin`` orders it after ``cur``, ``end`` orders ``cur`` after it, and
+    the caller chooses how many calls lie between the two. ``handle=``: a raw HIP stream handle to
+    use instead of ``cur``'s: dense's ``stream=``, whose tensors are allocated on the current torch
+    stream. Ragged and select make their ``stream=`` the current torch stream (``wrapping``), so
+    their allocations run on it too. The two differ observably and stay as they are."""
+
+    __slots__ = ("cur", "side", "handle")
+    _side: dict = {}
+
+    def __init__(self, cur, handle: int | None = None) -> None:
+        self.cur, self.side = cur, None
+        self.handle = int(cur.cuda_stream) if handle is None else handle
+        if not self.handle:
+            import torch  # noqa: PLC0415
+
+            self.side = self._side.get(cur.device.index)
+            if self.side is None:
+                self.side = self._side[cur.device.index] = torch.cuda.Stream(cur.device)
+            self.handle = int(self.side.cuda_stream)
+
+    @classmethod
+    def wrapping(cls, stream: int | None, dev) -> ConsumerStream:
+        """For ``stream`` (a HIP stream handle) as a torch stream, or the current one of ``dev``."""
+        import torch  # noqa: PLC0415
+
+        with torch.cuda.device(dev):
+            return cls(torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.current_stream(dev))
+
+    def begin(self) -> None:
+        if self.side is not None:
+            self.side.wait_stream(self.cur)
+
+    def end(self) -> None:
+        if self.side is not None:
+            self.cur.wait_stream(self.side)
 
 
 class _Collator:
@@ -319,7 +376,7 @@ class _Collator:
         if rows is not None:
             self.rows, n = device_rows(rows, n, device)
         self.n = n
-        tdt = {"int64": torch.int64, "int32": torch.int32, "float32": torch.float32, "uint8": torch.uint8}
+        tdt = torch_dtypes()
         self.values, self.lengths = {}, {}
         with torch.cuda.device(self.dev):
             self.cur = torch.cuda.current_stream(self.dev)
@@ -350,16 +407,8 @@ class _Collator:
             self.masks: list = []  # (spec index, how many rows of the list an absent slot's batch holds)
             self.absent = np.zeros((self.k, 4), np.int64)  # counters of the (batch, spec) pairs without a slot
             self.calls: list = []  # (batch, spec indices of the call's counters)
-            # the consumer stream; the legacy default stream (handle 0, which NULL would not name) is
-            # stood in for by a side stream ordered after and before it
-            self.side = None
-            self.consumer = stream if stream is not None else int(self.cur.cuda_stream)
-            if not self.consumer:
-                self.side = _SIDE_STREAMS.get(device)
-                if self.side is None:
-                    self.side = _SIDE_STREAMS[device] = torch.cuda.Stream(self.dev)
-                self.side.wait_stream(self.cur)
-                self.consumer = int(self.side.cuda_stream)
+            self.consumer = ConsumerStream(self.cur, stream)  # (once per collator: finish() ends it)
+            self.consumer.begin()
 
     def _check(self, t, shape, dtype, what: str) -> None:
         if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self.dev or not t.is_contiguous():
@@ -393,7 +442,8 @@ class _Collator:
             if slot is None:
                 if strict and r1 > r0:
                     raise KeyError(sp.key)
-                with self.torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext():
+                side = self.consumer.side
+                with self.torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
                     if by_rows:
                         # the rows of the list that are this batch's (none of an empty batch)
                         mine = (self.rows >= r0) & (self.rows < r1)
@@ -417,16 +467,15 @@ class _Collator:
         if items:
             # (the library's counters are per spec of the call: its rows map back on the host)
             if by_rows:
-                rdt = N.ROWS_I64 if self.rows.dtype == self.torch.int64 else N.ROWS_I32
-                launch(dec, items, self.stats[k].data_ptr(), self.consumer, (self.rows.data_ptr(), self.n, rdt), r0,
+                ptr, rdt = rows_arg(self.rows)
+                launch(dec, items, self.stats[k].data_ptr(), self.consumer.handle, (ptr, self.n, rdt), r0,
                        self.skips[k].data_ptr())
             else:
-                launch(dec, items, self.stats[k].data_ptr(), self.consumer)
+                launch(dec, items, self.stats[k].data_ptr(), self.consumer.handle)
             self.calls.append((k, rows))
 
     def finish(self, strict: bool = False) -> DenseBatch:
-        if self.side is not None:
-            self.cur.wait_stream(self.side)
+        self.consumer.end()
         specs, stats_t, absent, calls = self.specs, self.stats, self.absent, self.calls
         skips_t, masks, m, ran = self.skips, self.masks, self.n, self.ran
 
@@ -500,11 +549,8 @@ def decoder_dense(dec, specs: Sequence[Dense], *, strict: bool = False, out: Map
     IndexError), or a host sequence, range-checked here (IndexError) and uploaded. With raw pointers
     as ``out=`` it is ``(device pointer, m, "int32" | "int64")``."""
     specs = check_specs(specs)
-    n = getattr(dec, "_last_n", None)
-    info = None
-    if n is None or strict:
-        info = dec.info()
-        n = int(info.n_records)
+    info = dec.info() if strict else None
+    n = int(info.n_records) if strict else last_n(dec)
     if strict and info.n_errors:
         _raise_first_error(dec, info)
     raw = bool(out) and all(isinstance(v, (int, np.integer)) or (isinstance(v, tuple) and isinstance(v[0], (int, np.integer)))
@@ -572,9 +618,7 @@ def minibatches(dec, specs: Sequence[Dense], batch_size: int, *, plan: np.ndarra
     if plan is not None:
         n = int(plan[-1, 1]) if len(plan) else 0
     else:
-        n = getattr(dec, "_last_n", None)
-        if n is None:
-            n = int(dec.info().n_records)
+        n = last_n(dec)
     dev = torch.device("cuda", dec.device)
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))

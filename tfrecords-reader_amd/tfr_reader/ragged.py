@@ -21,7 +21,6 @@ list is out of range (they are empty rows here, and count in ``skipped`` alone).
 
 from __future__ import annotations
 
-import ctypes as C
 from collections.abc import Mapping, Sequence
 from dataclasses import dataclass
 
@@ -169,10 +168,6 @@ def batch_ragged(res, specs: Sequence[Ragged], rows=None) -> RaggedBatch:
 
 
 # ---------------------------------------------------------------------- device path
-def _vp(p: int | None):
-    return C.c_void_p(p) if p else None
-
-
 def launch(dec, items: Sequence[tuple], rows: tuple | None, m: int, row0: int, totals_ptr: int | None,
            stats_ptr: int | None, consumer: int | None) -> None:
     """One ``tfrg_result_ragged_rows`` call: items are (slot, TFRG_DENSE_* id, max_len, cap, values
@@ -181,8 +176,8 @@ def launch(dec, items: Sequence[tuple], rows: tuple | None, m: int, row0: int, t
     for a, (slot, dt, max_len, cap, values, offsets) in zip(arr, items):
         a.slot, a.dtype, a.max_len, a.reserved, a.cap, a.values, a.offsets = slot, dt, max_len, 0, cap, values, offsets
     ptr, rdt = rows if rows is not None else (None, 0)
-    N.check(dec._lib.tfrg_result_ragged_rows(dec._ctx, arr, len(items), _vp(ptr), rdt, m, row0, _vp(totals_ptr),
-                                             _vp(stats_ptr), _vp(consumer)), "tfrg_result_ragged_rows")
+    N.check(dec._lib.tfrg_result_ragged_rows(dec._ctx, arr, len(items), D.vp(ptr), rdt, m, row0, D.vp(totals_ptr),
+                                             D.vp(stats_ptr), D.vp(consumer)), "tfrg_result_ragged_rows")
 
 
 def decoder_ragged(dec, specs: Sequence[Ragged], *, rows=None, capacity=None, out: Mapping | None = None,
@@ -206,35 +201,19 @@ def decoder_ragged(dec, specs: Sequence[Ragged], *, rows=None, capacity=None, ou
     import torch  # noqa: PLC0415
 
     specs = check_specs(specs)
-    n = getattr(dec, "_last_n", None)
-    if n is None:
-        n = int(dec.info().n_records)
+    n = D.last_n(dec)
     dev = torch.device("cuda", dec.device)
-    tdt = {"int64": torch.int64, "int32": torch.int32, "float32": torch.float32, "uint8": torch.uint8}
-    with torch.cuda.device(dev):
-        cur = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev), torch.cuda.stream(cur):
+    tdt = D.torch_dtypes()
+    consumer = D.ConsumerStream.wrapping(stream, dev)
+    with torch.cuda.device(dev), torch.cuda.stream(consumer.cur):
         d_rows, m = (None, n) if rows is None else D.device_rows(rows, n, dec.device)
-        # the consumer stream; the legacy default stream (handle 0, which NULL would not name) is stood
-        # in for by a side stream ordered after and before it
-        side = None
-        consumer = int(cur.cuda_stream)
-        if not consumer:
-            side = D._SIDE_STREAMS.get(dec.device)
-            if side is None:
-                side = D._SIDE_STREAMS[dec.device] = torch.cuda.Stream(dev)
-            consumer = int(side.cuda_stream)
+        rw = D.rows_arg(d_rows) if d_rows is not None else None
 
-        def call(items, totals_t, stats_t) -> None:
-            if side is not None:
-                side.wait_stream(cur)
-            rw = None
-            if d_rows is not None:
-                rw = (d_rows.data_ptr(), N.ROWS_I64 if d_rows.dtype == torch.int64 else N.ROWS_I32)
+        def call(items, totals_t, stats_t) -> None:  # (the consumer is ordered around each call)
+            consumer.begin()
             launch(dec, items, rw, m, 0, totals_t.data_ptr(), stats_t.data_ptr() if stats_t is not None else None,
-                   consumer)
-            if side is not None:
-                cur.wait_stream(side)
+                   consumer.handle)
+            consumer.end()
 
         caps: dict[str, int | None] = {}
         values: dict = {}
@@ -340,9 +319,7 @@ def ragged_minibatches(dec, specs: Sequence[Ragged], batch_size: int, *, seed: i
     if not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
         raise ValueError(f"batch_size must be a positive integer, not {batch_size!r}")
     specs = check_specs(specs)
-    n = getattr(dec, "_last_n", None)
-    if n is None:
-        n = int(dec.info().n_records)
+    n = D.last_n(dec)
     dev = torch.device("cuda", dec.device)
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))

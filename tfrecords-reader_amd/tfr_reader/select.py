@@ -24,7 +24,6 @@ Integers compare as signed 64-bit, float32 values by value (NaN is false under e
 
 from __future__ import annotations
 
-import ctypes as C
 import operator
 from collections.abc import Sequence
 from dataclasses import dataclass
@@ -234,10 +233,6 @@ def batch_select(res, where, rows=None, row0: int = 0) -> tuple[np.ndarray, tupl
 
 
 # ---------------------------------------------------------------------- device path
-def _vp(p: int | None):
-    return C.c_void_p(p) if p else None
-
-
 def launch(dec, terms: Sequence[tuple], rows: tuple | None, m: int, row0: int, out: tuple | None, cap: int,
            count_ptr: int, stats_ptr: int | None, flags: int, consumer: int | None) -> None:
     """One ``tfrg_result_select_rows`` call: terms are (slot, subject, op, group, index, operand bits);
@@ -247,8 +242,8 @@ def launch(dec, terms: Sequence[tuple], rows: tuple | None, m: int, row0: int, o
         a.slot, a.subject, a.op, a.group, a.index, a.reserved, a.operand = slot, subject, op, group, index, 0, operand
     ptr, rdt = rows if rows is not None else (None, 0)
     optr, odt = out if out is not None else (None, N.ROWS_I64)
-    N.check(dec._lib.tfrg_result_select_rows(dec._ctx, arr, len(terms), _vp(ptr), rdt, m, row0, _vp(optr), odt, cap,
-                                             _vp(count_ptr), _vp(stats_ptr), flags, _vp(consumer)),
+    N.check(dec._lib.tfrg_result_select_rows(dec._ctx, arr, len(terms), D.vp(ptr), rdt, m, row0, D.vp(optr), odt, cap,
+                                             D.vp(count_ptr), D.vp(stats_ptr), flags, D.vp(consumer)),
             "tfrg_result_select_rows")
 
 
@@ -321,10 +316,9 @@ def _select(decs: Sequence, spans: Sequence[tuple[int, int]], n: int, device: in
                                  or capacity < 0):
         raise ValueError(f"capacity must be a non-negative integer, not {capacity!r}")
     dev = torch.device("cuda", device)
-    tdt = {"int32": torch.int32, "int64": torch.int64}
-    with torch.cuda.device(dev):
-        cur = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev), torch.cuda.stream(cur):
+    tdt = D.torch_dtypes()
+    consumer = D.ConsumerStream.wrapping(stream, dev)
+    with torch.cuda.device(dev), torch.cuda.stream(consumer.cur):
         d_rows, m = (None, n) if rows is None else D.device_rows(rows, n, device)
         exact = capacity is None and out is None
         if out is not None:
@@ -340,19 +334,8 @@ def _select(decs: Sequence, spans: Sequence[tuple[int, int]], n: int, device: in
         odt = N.ROWS_I64 if out.dtype == torch.int64 else N.ROWS_I32
         count_t = torch.zeros(1, dtype=torch.int64, device=dev)
         stats_t = torch.zeros((max(len(decs), 1), 2), dtype=torch.int32, device=dev)
-        # the consumer stream; the legacy default stream (handle 0, which NULL would not name) is stood
-        # in for by a side stream ordered after and before it
-        side = None
-        consumer = int(cur.cuda_stream)
-        if not consumer:
-            side = D._SIDE_STREAMS.get(device)
-            if side is None:
-                side = D._SIDE_STREAMS[device] = torch.cuda.Stream(dev)
-            consumer = int(side.cuda_stream)
-            side.wait_stream(cur)
-        rw = None
-        if d_rows is not None:
-            rw = (d_rows.data_ptr(), N.ROWS_I64 if d_rows.dtype == torch.int64 else N.ROWS_I32)
+        consumer.begin()  # (once around the loop over the contexts)
+        rw = D.rows_arg(d_rows) if d_rows is not None else None
         ran = 0
         unlaunched = []  # per context without a launch: how many candidates it skips
         for k, (dec, (r0, r1)) in enumerate(zip(decs, spans)):
@@ -368,10 +351,9 @@ def _select(decs: Sequence, spans: Sequence[tuple[int, int]], n: int, device: in
                     unlaunched.append(m - int(((a >= r0) & (a < r1)).sum()))
                 continue
             launch(dec, terms, rw, m, r0, (out.data_ptr() if cap else None, odt), cap, count_t.data_ptr(),
-                   stats_t[k].data_ptr(), N.SEL_APPEND if ran else 0, consumer)
+                   stats_t[k].data_ptr(), N.SEL_APPEND if ran else 0, consumer.handle)
             ran += 1
-        if side is not None:
-            cur.wait_stream(side)
+        consumer.end()
         n_ctx = len(decs)
 
         def stats() -> tuple[int, int]:
@@ -406,9 +388,7 @@ def decoder_select(dec, where, *, rows=None, capacity=None, dtype: str = "int64"
     ``out``: a 1-D int32 / int64 tensor to write into instead (its length is the capacity; nothing
     past the stored rows is written). ``stream``: a HIP stream handle as the consumer stream
     (default: the current torch stream)."""
-    n = getattr(dec, "_last_n", None)
-    if n is None:
-        n = int(dec.info().n_records)
+    n = D.last_n(dec)
     return _select([dec], [(0, n)], n, dec.device, where, rows=rows, capacity=capacity, dtype=dtype, out=out,
                    stream=stream)
 
