@@ -297,7 +297,27 @@ typedef struct tfrg_info {
    * tfrg_result_fetch writes them into the caller's buffer, and tfrg_result_device into the device
    * columns (one small kernel on the decode's stream, before it returns the view). */
   uint64_t placed_slots;
+  /* bit k: the last decode did not store slot k's bytes_off words. Slot k is a bytes_list slot that
+   * holds one element per record at the same distance from the record's end in every record shape,
+   * so element r of the slot's column is d_end32[r] + delta, with d_end32 the u32 ends the caller
+   * passed to tfrg_decode_device32 and delta = tfrg_ctx_rel_off(ctx, k) (negative). Set only by an
+   * optimistic decode (tfrg_result_info) with u32 offsets and without TFRG_FLAG_MATERIALIZE_BYTES;
+   * a u64 or host decode, a re-run decode and env TFRG_IMPLICIT_OFF=0 at context creation store
+   * every word (mask 0). tfrg_result_device writes the words into the device column (one small
+   * kernel per masked slot on the decode's stream, once per decode) and tfrg_result_fetch copies
+   * them from there; tfrg_result_dense / _dense_rows / _ragged_rows read d_end32 instead of the
+   * column and write nothing.
+   * Lifetime: while a result with a nonzero mask is read (tfrg_result_fetch, tfrg_result_device,
+   * dense / dense_rows / ragged over a bytes slot), the d_end32 array of its decode must stay in
+   * place and unchanged, until the next decode on the context -- exactly as d_bytes must stay for
+   * the bytes views and for the confirmation of the decode. */
+  uint64_t implicit_off_slots;
 } tfrg_info;
+
+/* The end-relative element offset of bytes slot `slot` in the context's learned record shapes
+ * (tfrg_info.implicit_off_slots): *delta such that the slot's element of a record ending at e lies at
+ * e + *delta. TFRG_E_ARG if the slot is not at one end-relative position in every learned shape. */
+int tfrg_ctx_rel_off(const tfrg_ctx* ctx, uint32_t slot, int32_t* delta);
 
 /* Waits for the last decode and returns its summary. Optimistic decodes: when the context's record
  * shapes took their whole learning sample, every slot is a single value and no record can exceed

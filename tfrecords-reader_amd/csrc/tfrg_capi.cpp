@@ -164,6 +164,12 @@ struct tfrg_ctx {
   bool ord_const = false;     // (Learned::ord_const) of the learned shapes
   bool len_const = false;     // (Learned::len_const)
   std::vector<uint32_t> const_len;  // per slot: the bytes element length of every learned shape
+  bool implicit_off_on = true;  // (env TFRG_IMPLICIT_OFF=0: every bytes_off word stored, A/B and tests)
+  uint64_t off_rel = 0;       // (Learned::off_rel) bytes slots at one end-relative offset in every shape
+  std::vector<int32_t> rel_off;  // (Learned::rel_off) per slot: that offset
+  uint64_t last_off_mask = 0; // slots whose bytes_off words the last decode did not store (implicit_off_slots)
+  std::vector<int32_t> last_rel_off;  // rel_off as that decode ran with it (a later re-learn does not change its result)
+  bool off_complete = false;  // fill_implicit_off wrote them into the device column
   uint32_t last_implicit = 0; // TFRG_IMPLICIT_* columns the last decode did not store
   bool last_aux_zero = false; // the last decode ran optimistically with stored statuses: aux is all 0
   uint32_t* info_pin = nullptr;  // pinned host copy of the info words + kind totals (confirmation)
@@ -215,6 +221,7 @@ int tfrg_ctx_create(int device, tfrg_ctx** out) {
     if (v == 2 || v == 4 || v == 8) c->tpl_gpw = (uint32_t)v;
   }
   if (const char* e = getenv("TFRG_OPTIMISTIC")) c->optimistic_on = atoi(e) != 0;
+  if (const char* e = getenv("TFRG_IMPLICIT_OFF")) c->implicit_off_on = atoi(e) != 0;
   if (const char* e = getenv("TFRG_WALK_BESIDE")) c->walk_beside = atoi(e) != 0;
   if (const char* e = getenv("TFRG_WALK_BLOCKS")) c->walk_blocks = (uint32_t)atoi(e);
   if (const char* e = getenv("TFRG_DENSE_NT")) c->dense_nt = atoi(e) != 0;
@@ -561,6 +568,8 @@ int tfrg_set_schema(tfrg_ctx* c, uint32_t n_keys, const uint8_t* key_blob, const
   c->key_slot_h = ks;
   c->slot_kind_h.assign(slot_kind, slot_kind + n_slots);
   c->n_tpl = 0;  // slots may have moved: learn again from the next host batch
+  c->off_rel = 0;
+  c->rel_off.clear();
   c->tpl_learned = false;
   c->have_spec = false;
   return 0;
@@ -601,6 +610,8 @@ extern "C" int tfrg_learn_templates(tfrg_ctx* c, const uint8_t* h_bytes, uint64_
   c->n_tpl = 0;
   c->tpl_frames = 0;
   c->have_spec = false;
+  c->off_rel = 0;  // (no shape, no end-relative slot: tfrg_ctx_rel_off answers from the kept shapes only)
+  c->rel_off.clear();
   if (!c->n_keys) return 0;
   const TplSchema sch{c->key_id, c->key_slot_h, c->slot_kind_h};
   Learned L;
@@ -633,6 +644,8 @@ extern "C" int tfrg_learn_templates(tfrg_ctx* c, const uint8_t* h_bytes, uint64_
     c->ord_const = L.ord_const;
     c->len_const = L.len_const;
     c->const_len = L.const_len;
+    c->off_rel = L.off_rel;
+    c->rel_off = L.rel_off;
   }
   if (L.have_spec) HIP_TRY(hipMemcpy(c->spec.p, L.spec.data(), spec_bytes, hipMemcpyHostToDevice));
   c->spec_h = L.spec;
@@ -880,6 +893,8 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   cfg.ord_const = c->ord_const;
   cfg.len_const = c->len_const && !mat;  // (the byte gather reads the lengths)
   cfg.implicit = 0;
+  cfg.off_rel = c->implicit_off_on ? c->off_rel : 0ull;  // (launch_decode: u32 offsets, no byte gather)
+  cfg.implicit_off = 0;
   const uint64_t bound = c->call_bound ? c->call_bound : c->record_bound;
   c->call_bound = 0;
   c->last = tfrg_ctx::LastCall{d_bytes, nbytes, cap_in, bound, n, flags, st};
@@ -944,6 +959,9 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   if (n != 0 && cfg.ran_quiet_big) c->tsum_dirty = true;
   c->mat_pending = c->opt_pending && mat && S;
   c->last_implicit = n != 0 ? cfg.implicit : 0u;
+  c->last_off_mask = n != 0 ? cfg.implicit_off : 0ull;
+  if (c->last_off_mask) c->last_rel_off = c->rel_off;
+  c->off_complete = false;
   // (k_tpl_lane stored status and verdict per record and no aux: every record of a confirmed decode is OK)
   c->last_aux_zero = n != 0 && cfg.ran_optimistic && !cfg.ran_quiet_big && !(cfg.implicit & TFRG_IMPLICIT_STATUS);
   c->cols_complete = false;
@@ -1073,7 +1091,14 @@ int tfrg_result_info(tfrg_ctx* c, tfrg_info* info) {
   info->tpl_groups_missed = h[kInfoResid];
   info->placed_slots = ((uint64_t)h[kInfoPlacedHi] << 32) | h[kInfoPlacedLo];
   info->implicit_cols = c->last_implicit;
+  info->implicit_off_slots = c->last_off_mask;
   return overflow_status(h);
+}
+
+int tfrg_ctx_rel_off(const tfrg_ctx* c, uint32_t slot, int32_t* delta) {
+  if (!c || !delta || slot >= 64u || !((c->off_rel >> slot) & 1ull) || slot >= c->rel_off.size()) return TFRG_E_ARG;
+  *delta = c->rel_off[slot];
+  return 0;
 }
 
 // (TFRG_IMPLICIT_BYTES_LEN) per bytes slot of an optimistic decode: its first row in the bytes
@@ -1088,6 +1113,35 @@ static std::vector<std::pair<uint64_t, uint32_t>> implicit_len_runs(const tfrg_c
     base += c->n;
   }
   return out;
+}
+
+// (tfrg_info.implicit_off_slots) the same rule for the bytes_off words: per masked slot its first row
+// in the bytes columns and its end-relative offset (element r is end32[r] + that)
+static std::vector<std::pair<uint64_t, uint32_t>> implicit_off_runs(const tfrg_ctx* c) {
+  std::vector<std::pair<uint64_t, uint32_t>> out;
+  uint64_t base = 0;
+  for (uint32_t k = 0; k < c->n_slots; ++k) {
+    if ((c->slot_kind_h[k] & 3u) != TFRG_KIND_BYTES) continue;
+    if (k < 64u && ((c->last_off_mask >> k) & 1ull)) out.push_back({base, (uint32_t)c->last_rel_off[k]});
+    base += c->n;
+  }
+  return out;
+}
+
+// The implicit bytes_off words written into the device column, once per decode, on the decode's
+// stream, from the decode's u32 ends (the caller keeps them in place while the result is read:
+// tfrg.h). The one place that formula is evaluated outside the consumers' kernels: tfrg_result_device
+// hands out the column, tfrg_result_fetch copies it. Only after the decode is confirmed.
+static int fill_implicit_off(tfrg_ctx* c) {
+  if (!c->last_off_mask || c->off_complete || !c->n) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  for (const auto& [base, delta] : implicit_off_runs(c)) {
+    if (base >= c->cap_b) continue;  // (an overflowed result is an error: tfrg_result_info)
+    const uint32_t rows = (uint32_t)std::min<uint64_t>(c->n, c->cap_b - base);
+    HIP_TRY(launch_fill_rel_off(c->b_off.as<uint32_t>() + base, c->last_off.e32, delta, rows, c->last_stream));
+  }
+  c->off_complete = true;
+  return 0;
 }
 
 int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
@@ -1121,6 +1175,7 @@ int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
                                   c->last_stream));
   }
   c->cols_complete = true;
+  if (const int rc = fill_implicit_off(c)) return rc;
   d->status = c->status.as<int32_t>();
   d->aux = c->aux.as<int64_t>();
   d->verdict = c->verdict.as<uint8_t>();
@@ -1204,8 +1259,19 @@ static void fill_bytes_source(const tfrg_ctx* c, Args& a) {
   a.in = c->materialized ? c->bdata.as<uint8_t>() : c->last.d_bytes;
   const uint64_t bound = c->materialized ? (uint64_t)c->bdata.cap & ~15ull : (c->last.nbytes + 15ull) & ~15ull;
   a.in_bound = a.in ? (uint32_t)std::min<uint64_t>(bound, 0xfffffff0ull) : 0;
+  // (the decode's u32 ends, for the specs with a const_off: read for such a spec only)
+  a.end32 = c->last_off_mask ? c->last_off.e32 : nullptr;
 }
 }  // extern "C++"
+
+// A bytes slot's end-relative element offset where the last decode did not store its bytes_off words
+// (tfrg_info.implicit_off_slots: the element of record g is end32[g] + that); else the kernels' "the
+// column is stored" sentinel.
+static_assert(kDenseOffStored == kRaggedOffStored, "one const_off lookup serves both");
+static int32_t const_off_of(const tfrg_ctx* c, uint32_t slot, bool reads_off) {
+  if (!reads_off || slot >= 64u || !((c->last_off_mask >> slot) & 1ull)) return kDenseOffStored;
+  return c->last_rel_off[slot];
+}
 
 // A bytes slot's constant element length where the last decode did not store the bytes_len column (as
 // implicit_len_runs: the shapes' length holds); else, or for a spec / term that reads no length, the
@@ -1299,6 +1365,7 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
     d.dtype = s.dtype;
     d.width = s.width;
     d.const_len = const_len_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
+    d.const_off = const_off_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
     const uint64_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
     const uint64_t total = (uint64_t)out_rows * s.width * isz;
     // 16-byte units, or single elements where the output's base is not 16-byte aligned
@@ -1402,6 +1469,7 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
       d.dtype = s.dtype;
       d.max_len = s.max_len;
       d.const_len = const_len_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
+      d.const_off = const_off_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
     }
     HIP_TRY(launch_ragged(a, st));
   } else {
@@ -1569,6 +1637,9 @@ int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {
   auto cl = [](uint64_t v, uint64_t cap) { return v < cap ? v : cap; };
   HIP_TRY(cp(h->i64, c->i64.p, cl(info.kind_totals[TFRG_KIND_INT64], c->cap_i64) * 8));
   HIP_TRY(cp(h->f32, c->f32.p, cl(info.kind_totals[TFRG_KIND_FLOAT], c->cap_f32) * 4));
+  // (implicit offset words: written into the device column first, by the device view's fill)
+  if (h->bytes_off)
+    if (const int rc2 = fill_implicit_off(c)) return rc2;
   HIP_TRY(cp(h->bytes_off, c->b_off.p, cl(info.kind_totals[TFRG_KIND_BYTES], c->cap_b) * 4));
   if ((info.implicit_cols & TFRG_IMPLICIT_BYTES_LEN) && h->bytes_len) {
     for (const auto& [base, len] : implicit_len_runs(c)) std::fill_n(h->bytes_len + base, n, len);

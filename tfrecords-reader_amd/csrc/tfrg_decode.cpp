@@ -68,6 +68,7 @@ static LeanArgs lean_args(const DevBatch& b, const DevSchema& sc, const DevOut& 
     else if (kind == TFRG_KIND_FLOAT) t.v1 = o.f32 + base;
     else t.v1 = o.b_off + base;
     t.v2 = o.b_len + base;
+    t.no_off = kind == TFRG_KIND_BYTES && k < 64u && ((cfg.implicit_off >> k) & 1ull) ? 1u : 0u;
   }
   return a;
 }
@@ -128,6 +129,10 @@ hipError_t launch_decode(const DevBatch& b, const DevSchema& sc, const DevOut& o
                                                   (cfg.ord_const ? TFRG_IMPLICIT_ORDER : 0u) |
                                                   (cfg.len_const ? TFRG_IMPLICIT_BYTES_LEN : 0u)
                                             : 0u;
+  // (and the bytes_off words of a slot at one end-relative offset in every shape, when the caller's
+  // u32 ends are on the device to recompute them from: tfrg_info.implicit_off_slots. Every slot of
+  // such a decode is placed, so the slot's column rows are n * its rank among the bytes slots)
+  cfg.implicit_off = lean && quiet_tpl && b.omode != kOffU64 && !(b.flags & kFlagMaterializeBytes) ? cfg.off_rel : 0ull;
   DevOut ox = o;
   if (!lean) {
     ox.lmask = nullptr;

@@ -11,6 +11,8 @@ constexpr uint32_t kDenseMaxSpecs = 64;    // (tfrg.h TFRG_DENSE_MAX_SPECS)
 constexpr uint32_t kDenseMaxWidth = 4096;  // (tfrg.h TFRG_DENSE_MAX_WIDTH)
 enum DenseType : uint32_t { kDenseI64 = 0, kDenseI32 = 1, kDenseF32 = 2, kDenseU8 = 3 };  // (TFRG_DENSE_*)
 constexpr uint32_t kDenseNoLen = 0xffffffffu;  // DenseSpec::const_len: the bytes_len column is stored
+constexpr int32_t kDenseOffStored = 0x7fffffff;  // DenseSpec::const_off: the bytes_off column is stored (a real
+                                                 // offset is negative: the element lies before the record's end)
 
 // A workgroup covers 16-byte units [chunk * kDenseChunk, + kDenseChunk) of one output, 4 per lane
 constexpr uint32_t kDenseChunk = 1024;
@@ -27,6 +29,8 @@ struct DenseSpec {
   uint32_t const_len;  // bytes slot under TFRG_IMPLICIT_BYTES_LEN: every element's length; else kDenseNoLen
   uint32_t blk0;
   uint32_t nblk;
+  int32_t const_off;   // bytes slot under tfrg_info.implicit_off_slots: the element of record g lies at
+                       // end32[g] + const_off; else kDenseOffStored
 };
 
 // Kernel argument (read with scalar loads: every field a workgroup uses is uniform over it)
@@ -37,6 +41,7 @@ struct DenseArgs {
   const uint32_t* f32;
   const uint32_t* b_off;       // bytes views into `in` (null: materialized)
   const uint32_t* b_len;
+  const uint32_t* end32;       // [n] the decode's u32 record ends (read for specs with a const_off only)
   const uint64_t* b_off64;     // materialized: element e is in[b_off64[e], b_off64[e + 1])
   const uint8_t* in;           // the batch (views) or the materialized byte column
   const uint32_t* info;        // the decode's info words (kInfoPlacedLo / Hi read on the device)

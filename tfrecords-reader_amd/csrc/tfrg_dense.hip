@@ -14,8 +14,9 @@
 // dwords), so that they are in flight together; lengths and counters come last.
 //
 // Not read: the row splits of a placed slot (info words kInfoPlacedLo / Hi: row r holds record r's
-// single value), the bytes_len column of a slot whose length is constant (DenseSpec::const_len),
-// status / aux / verdict / order. The input of the bytes views is read through a buffer resource
+// single value), the bytes_len column of a slot whose length is constant (DenseSpec::const_len), the
+// bytes_off words of a slot the decode left implicit (DenseSpec::const_off: the decode's u32 record
+// ends are read in their place, DenseArgs::end32), status / aux / verdict / order. The input of the bytes views is read through a buffer resource
 // bounded to the batch: a view that runs past it reads zeros.
 //
 // k_dense_rows (tfrg_result_dense_rows) is the same kernel behind one level of indirection:
@@ -212,7 +213,9 @@ __device__ __forceinline__ BRow brow_of(const Sp& x, const Rec& q) {
     b.off = o0 < 0xffffffffull ? (uint32_t)o0 : 0xffffffffu;
     b.len = l < 0xffffffffull ? (uint32_t)l : 0xffffffffu;
   } else {
-    b.off = x.a->b_off[es];
+    // (uniform; const_off: an optimistic decode left the words implicit, the slot is placed and
+    // record g's element lies at its end plus a constant -- a skipped row's g is 0)
+    b.off = x.s->const_off != kDenseOffStored ? x.a->end32[q.g] + (uint32_t)x.s->const_off : x.a->b_off[es];
     b.len = x.s->const_len != kDenseNoLen ? x.s->const_len : x.a->b_len[es];
   }
   if (!c) b.len = 0u;

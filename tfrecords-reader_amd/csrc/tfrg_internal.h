@@ -49,7 +49,9 @@ struct LeanTgt {
   uint32_t* v2;    // speculative placement of bytes: the length column at n * (rank - 1)
   uint32_t lim;    // speculative placement: records r < lim are stored (capacity)
   uint32_t kind;   // speculative placement kind (0: the slot is not placed speculatively)
-  uint32_t pad[2];
+  uint32_t no_off; // bytes slot whose offset words this decode leaves implicit (LaunchCfg::implicit_off):
+                   // v1 is not stored
+  uint32_t pad;
 };
 struct LeanArgs {
   uint32_t n_tpl;
@@ -290,6 +292,10 @@ struct LaunchCfg {
                            // (k_tail_count's first workgroups) instead of before it (k_lane_count)
   uint32_t walk_blocks;    // cap on those workgroups (0: automatic)
   uint32_t implicit;       // (out) TFRG_IMPLICIT_* columns the decode did not store
+  uint64_t off_rel;        // bytes slots at one end-relative offset in every learned shape (Learned::off_rel;
+                           // 0: TFRG_IMPLICIT_OFF=0, or a decode whose byte gather reads the column)
+  uint64_t implicit_off;   // (out) the slots of off_rel whose bytes_off words the decode did not store: a
+                           // lean optimistic decode with u32 offsets (element r is end32[r] + rel_off)
 };
 
 // Kernel stages, in launch order (profiling events bracket each one).
@@ -319,6 +325,8 @@ void launch_down_gather(const DevBatch& b, const DevSchema& sc, const DevOut& o,
 void launch_tail_gather(const DevBatch& b, const DevSchema& sc, const DevOut& o, const LaunchCfg& cfg, int max_blocks,
                         hipStream_t st);
 hipError_t launch_fill_placed_rows(uint32_t* rs, const uint32_t* info, uint32_t n_slots, uint32_t n, hipStream_t st);
+// off[r] = end32[r] + delta for r < n: an implicit bytes_off run written out (tfrg_info.implicit_off_slots)
+hipError_t launch_fill_rel_off(uint32_t* off, const uint32_t* end32, uint32_t delta, uint32_t n, hipStream_t st);
 hipError_t launch_stream_read(const void* d, uint64_t nbytes, uint32_t* sink, hipStream_t st, int variant);
 // tfrg_frame.hip: every phase of the chunked framing index (tfrg_frame.h) enqueued on st
 struct FrTab;

@@ -391,6 +391,21 @@ uint32_t learn_shapes(const TplSchema* c, uint32_t S, const uint8_t* h_bytes, ui
     }
     out.const_len[s2] = (z0 >> 8) & 0xffu;
   }
+  // a bytes slot that is one inline element at one end-relative position in every kept shape
+  out.off_rel = 0;
+  out.rel_off.assign(S, 0);
+  for (uint32_t s2 = 0; s2 < S && s2 < kLeanMaxSlots && s2 < 64u; ++s2) {
+    if ((c->slot_kind[s2] & 3u) != TFRG_KIND_BYTES) continue;
+    const uint32_t z0 = w[kLtSlot + 3 * s2], p0 = w[kLtSlot + 3 * s2 + 1];
+    bool rel = (z0 & 0xffu) == 3u && (z0 >> 16) != 0;
+    for (uint32_t k = 1; rel && k < nt; ++k) {
+      const uint32_t* zk = &w[(size_t)k * kLtWords + kLtSlot + 3 * s2];
+      rel = (zk[0] & 0xffu) == 3u && (zk[0] >> 16) != 0 && zk[1] == p0;
+    }
+    if (!rel) continue;
+    out.off_rel |= 1ull << s2;
+    out.rel_off[s2] = (int32_t)p0;
+  }
   out.w = std::move(w);
   out.spec = std::move(spec);
   out.img = std::move(img);

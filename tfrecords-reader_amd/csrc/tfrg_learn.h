@@ -32,6 +32,12 @@ struct Learned {
   // leaves the bytes_len column implicit (TFRG_IMPLICIT_BYTES_LEN); const_len[k] that length
   bool len_const = false;
   std::vector<uint32_t> const_len;
+  // bit k: bytes slot k (< 64) is one inline element (mode 3, present) at the same offset from the
+  // record's end in every kept template; rel_off[k] that offset (the template's pos word, negative:
+  // the element's batch offset is end + rel_off[k]). Per slot, whatever len_const says. An optimistic
+  // decode with u32 offsets leaves such a slot's bytes_off words implicit (tfrg_info.implicit_off_slots)
+  uint64_t off_rel = 0;
+  std::vector<int32_t> rel_off;
 };
 
 // Returns the template count (0: none).

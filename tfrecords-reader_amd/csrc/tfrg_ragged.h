@@ -17,6 +17,7 @@ constexpr uint32_t kRaggedScanThreads = 1024;
 constexpr uint32_t kRaggedChunk = 1024;
 constexpr uint32_t kRaggedMaxSplit = 256;
 constexpr uint32_t kRaggedNoLen = 0xffffffffu;  // RaggedSpec::const_len: the bytes_len column is stored
+constexpr int32_t kRaggedOffStored = 0x7fffffff;  // RaggedSpec::const_off: the bytes_off column is stored
 
 // One requested output
 struct RaggedSpec {
@@ -27,6 +28,8 @@ struct RaggedSpec {
   uint32_t dtype;      // DenseType
   uint32_t max_len;    // 0: whole rows
   uint32_t const_len;  // bytes slot under TFRG_IMPLICIT_BYTES_LEN: every element's length; else kRaggedNoLen
+  int32_t const_off;   // bytes slot under tfrg_info.implicit_off_slots: the element of record g lies at
+                       // end32[g] + const_off; else kRaggedOffStored
 };
 
 // Kernel argument of all three kernels (read with scalar loads: every field a workgroup uses is
@@ -38,6 +41,7 @@ struct RaggedArgs {
   const uint32_t* f32;
   const uint32_t* b_off;      // bytes views into `in` (null: materialized)
   const uint32_t* b_len;
+  const uint32_t* end32;      // [n] the decode's u32 record ends (read for specs with a const_off only)
   const uint64_t* b_off64;    // materialized: element e is in[b_off64[e], b_off64[e + 1])
   const uint8_t* in;          // the batch (views) or the materialized byte column
   const uint32_t* info;       // the decode's info words (kInfoPlacedLo / Hi read on the device)

@@ -19,7 +19,8 @@
 //
 // Not read (as k_dense): the row splits of a placed slot (info words kInfoPlacedLo / Hi: the row has
 // one value, at index g), the bytes_len column of a slot whose length is constant
-// (RaggedSpec::const_len), status / aux / verdict / order. The input of the bytes views is read through
+// (RaggedSpec::const_len), the bytes_off words of a slot the decode left implicit (RaggedSpec::const_off:
+// the decode's u32 record ends are read in their place), status / aux / verdict / order. The input of the bytes views is read through
 // a buffer resource bounded to the batch: a view that runs past it reads zeros.
 //
 // A row whose g is not in [0, n) is an empty row: nothing indexed by g is loaded for it (it reads
@@ -135,7 +136,9 @@ __device__ __forceinline__ Row row_of(const Sp& x, uint32_t k) {
       off = o0 < 0xffffffffull ? (uint32_t)o0 : 0xffffffffu;
       len = l < 0xffffffffull ? (uint32_t)l : 0xffffffffu;
     } else {
-      off = x.a->b_off[es];
+      // (uniform; const_off: an optimistic decode left the words implicit, the slot is placed and
+      // record g's element lies at its end plus a constant -- a skipped row's g is 0)
+      off = x.s->const_off != kRaggedOffStored ? x.a->end32[q.g] + (uint32_t)x.s->const_off : x.a->b_off[es];
       len = x.s->const_len != kRaggedNoLen ? x.s->const_len : x.a->b_len[es];
     }
     r.src = off;

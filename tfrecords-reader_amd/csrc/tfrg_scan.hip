@@ -406,4 +406,19 @@ hipError_t launch_fill_placed_rows(uint32_t* rs, const uint32_t* info, uint32_t 
   return hipGetLastError();
 }
 
+// The bytes_off words of a slot an optimistic decode left implicit (tfrg_info.implicit_off_slots)
+// written into the device column, for tfrg_result_device's view and tfrg_result_fetch: record r's
+// element lies at its u32 end plus the slot's end-relative offset.
+__global__ __launch_bounds__(256) void k_fill_rel_off(uint32_t* __restrict__ off, const uint32_t* __restrict__ end32,
+                                                      uint32_t delta, uint32_t n) {
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) off[i] = end32[i] + delta;
+}
+
+hipError_t launch_fill_rel_off(uint32_t* off, const uint32_t* end32, uint32_t delta, uint32_t n, hipStream_t st) {
+  if (!n) return hipSuccess;
+  const uint32_t blocks = (n + 255u) / 256u;
+  hipLaunchKernelGGL(k_fill_rel_off, dim3(blocks < 4096u ? blocks : 4096u), dim3(256), 0, st, off, end32, delta, n);
+  return hipGetLastError();
+}
+
 }  // namespace tfrg

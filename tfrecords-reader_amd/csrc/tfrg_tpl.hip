@@ -416,7 +416,9 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
               if (T.kind == TFRG_KIND_INT64) {
                 st_nt<kNt>(reinterpret_cast<uint64_t*>(T.v1) + r, (uint64_t)lx);
               } else {
-                st_nt<kNt>(reinterpret_cast<uint32_t*>(T.v1) + r, lx);
+                // (uniform; no_off: the element's offset en + pos is the caller's u32 end plus a constant
+                // of the shapes, left implicit -- tfrg_info.implicit_off_slots)
+                if (!T.no_off) st_nt<kNt>(reinterpret_cast<uint32_t*>(T.v1) + r, lx);
                 if (T.kind == TFRG_KIND_BYTES && !(A.implicit & TFRG_IMPLICIT_BYTES_LEN)) st_nt<kNt>(T.v2 + r, ly);
               }
             }

@@ -42,6 +42,7 @@ class TfrgInfo(C.Structure):
         ("tpl_groups_missed", C.c_uint32),
         ("implicit_cols", C.c_uint32),
         ("placed_slots", C.c_uint64),
+        ("implicit_off_slots", C.c_uint64),
     ]
 
 
@@ -243,6 +244,7 @@ SIGNATURES: dict[str, tuple] = {
                                     C.c_void_p, C.c_uint64, u64p, C.c_void_p, C.POINTER(TfrgIndexInfo)]),
     "tfrg_stream_set_device_index": (C.c_int, [C.c_void_p, C.c_int]),
     "tfrg_result_info": (C.c_int, [C.c_void_p, C.POINTER(TfrgInfo)]),
+    "tfrg_ctx_rel_off": (C.c_int, [C.c_void_p, C.c_uint32, i32p]),
     "tfrg_result_device": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),
     "tfrg_result_fetch": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),
     "tfrg_result_dense": (C.c_int, [C.c_void_p, C.POINTER(TfrgDenseSpec), C.c_uint32, C.c_void_p, C.c_void_p]),

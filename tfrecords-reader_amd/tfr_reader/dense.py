@@ -14,7 +14,10 @@ with ``fill`` or truncated, in the dtype the model wants -- and
 Row lists: every entry point takes ``rows=``, and then output row k is record ``rows[k]`` of the
 decode -- a shuffled, sampled or filtered minibatch. On the device that is one launch per decoded
 batch over columns that stay where the decode left them (``tfrg_result_dense_rows``), so a shard is
-decoded once and ``minibatches`` draws an epoch of batches from it.
+decoded once and ``minibatches`` draws an epoch of batches from it. The columns an optimistic decode
+left implicit are not written for it: a bytes output whose ``bytes_off`` words are implicit
+(``info().implicit_off_slots``) is gathered from the decode's u32 record ends, which therefore stay in
+place, like the input bytes, while the decode is read.
 
 Per output: ``lengths[r]`` is the record's untruncated value count (bytes: the byte length of the
 list's first element, 0 if the list is empty or absent) and ``stats`` the four counters

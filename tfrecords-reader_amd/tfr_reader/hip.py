@@ -116,6 +116,7 @@ class HipDecoder:
         self.keys = keys or KeyTable()
         self._pushed = -1
         self._lock = threading.Lock()
+        self._last_image = None  # decode_image: the image and index tensors its result still reads
         h = C.c_void_p()
         N.check(self._lib.tfrg_ctx_create(device, C.byref(h)), "tfrg_ctx_create")
         self._ctx = h
@@ -131,6 +132,7 @@ class HipDecoder:
         d.keys = keys
         d._pushed = -1
         d._lock = threading.Lock()
+        d._last_image = None
         d._ctx = C.c_void_p(ctx)
         d._owned = False
         return d
@@ -139,6 +141,7 @@ class HipDecoder:
         if self._ctx and getattr(self, "_owned", True):
             self._lib.tfrg_ctx_destroy(self._ctx)
         self._ctx = None
+        self._last_image = None
 
     def __del__(self):  # noqa: D105
         try:
@@ -256,8 +259,9 @@ class HipDecoder:
 
     def device_columns(self) -> N.TfrgColumns:
         """Device pointers of the last result (tfrg_result_device): valid until the next decode on
-        this decoder; the placed slots' identity row splits are written into them on the decode's
-        stream first."""
+        this decoder; the placed slots' identity row splits, the constant columns and the
+        end-relative ``bytes_off`` words an optimistic decode left implicit (``info().implicit_cols``,
+        ``info().implicit_off_slots``) are written into them on the decode's stream first."""
         cols = N.TfrgColumns()
         N.check(self._lib.tfrg_result_device(self._ctx, C.byref(cols)), "tfrg_result_device")
         return cols
@@ -363,7 +367,13 @@ class HipDecoder:
                         n: int, *, payload_only: bool = False, crc: bool = True, stream: int | None = None,
                         strict_crc: bool = False, materialize_bytes: bool = False) -> None:
         """``decode_device`` with u32 offsets; ``d_start32`` None: back-to-back records, record 0 at
-        ``first_start`` and record i > 0 where record i - 1 ends (only the u32 ends are read)."""
+        ``first_start`` and record i > 0 where record i - 1 ends (only the u32 ends are read).
+
+        ``d_end32`` stays in place and unchanged, like ``d_bytes``, until the next decode on this
+        decoder: an optimistic decode does not store the ``bytes_off`` words of a bytes slot that
+        lies at one distance from the record's end in every learned shape
+        (``info().implicit_off_slots``); ``device_columns``, the fetch, ``dense`` and ``ragged``
+        compute them from the ends."""
         self.push_schema()
         N.check(
             self._lib.tfrg_decode_device32(
@@ -465,6 +475,8 @@ class HipDecoder:
             self._seed_keys(host, st, en, flags)
             torch.cuda.current_stream(dev).synchronize()  # the uploads above, before the context's stream reads
             self.last_image_mode = "u32_ends" if tiled else "u64"
+            # (the image and its u32 ends stay in place while the result is read: tfrg_info.implicit_off_slots)
+            self._last_image = (d_all, ix)
             while True:
                 self.push_schema()
                 if tiled:

@@ -9,7 +9,9 @@ padded, and a row may be longer than ``dense``'s widest output.
 * ``HipDecoder.ragged`` gathers them on the device for every record in order or for a list of rows
   (``rows=``: shuffled, sampled, filtered), in three launches over the columns where the decode left
   them (``tfrg_result_ragged_rows``), and ``HipDecoder.ragged_minibatches`` draws an epoch from one
-  decode;
+  decode; implicit columns are not written for it, and a bytes output whose ``bytes_off`` words are
+  implicit (``info().implicit_off_slots``) is gathered from the decode's u32 record ends, which stay
+  in place like the input bytes while the decode is read;
 * ``BatchResult.ragged`` / ``raggedify`` compute the same function with numpy from fetched columns
   (the host path, and the reference the device path is tested against).
 
