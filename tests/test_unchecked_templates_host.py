@@ -47,16 +47,16 @@ def _mask_crc(c: int) -> int:
     return ((((c >> 15) | (c << 17)) & 0xFFFFFFFF) + 0xA282EAD8) & 0xFFFFFFFF
 
 
-def _learn(buf, st, en):
-    blob = b"".join(KEYS)
-    offs = np.zeros(len(KEYS) + 1, np.uint64)
-    offs[1:] = np.cumsum([len(k) for k in KEYS])
-    sk = np.array([s[0] for s in SLOTS], np.uint32)
-    sd = np.array([s[1] for s in SLOTS], np.uint8)
+def _learn(buf, st, en, keys=KEYS, slots=SLOTS):
+    blob = b"".join(keys)
+    offs = np.zeros(len(keys) + 1, np.uint64)
+    offs[1:] = np.cumsum([len(k) for k in keys])
+    sk = np.array([s[0] for s in slots], np.uint32)
+    sd = np.array([s[1] for s in slots], np.uint8)
     out = np.zeros(32 * K_WORDS, np.uint32)
     W = np.zeros(1, np.uint32)
     b = np.frombuffer(blob, np.uint8)
-    nt = N.lib().tfrg_learn_templates_host(len(KEYS), N.ptr(b), N.ptr(offs), None, len(SLOTS), N.ptr(sk), N.ptr(sd),
+    nt = N.lib().tfrg_learn_templates_host(len(keys), N.ptr(b), N.ptr(offs), None, len(slots), N.ptr(sk), N.ptr(sd),
                                            N.ptr(buf), buf.size, N.ptr(st), N.ptr(en), st.size, 0, N.ptr(out),
                                            out.size, N.ptr(W))
     assert nt >= 1
