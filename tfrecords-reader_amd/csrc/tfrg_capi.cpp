@@ -78,55 +78,115 @@ struct Offsets {
   uint32_t mode = kOffU64;
 };
 
-struct tfrg_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t last_stream = nullptr;
-  uint32_t lane_max = 2048;
-  uint32_t wave_stage = 0xffffffffu;  // clamped to the kernel's stage size
-  uint64_t record_bound = 0;  // tfrg_ctx_set_record_bound: no record above this (0 = unknown)
-  uint64_t call_bound = 0;    // tfrg_decode_host: the bound of its own ranges (one call)
-  int num_cus = 256;
-  uint32_t cu_lds = 65536;     // LDS bytes of a CU
-  int tpl_stage = 1;           // k_tpl_lane's staged windows: TFRG_TPL_STAGE=0 off (A/B measurements), 1 on
-                               // large batches, 2 on batches of any size (tests)
-  uint32_t tpl_gpw = 0;        // TFRG_TPL_GPW=2, 4 or 8: k_tpl_lane's groups per wave whatever the batch size
-                               // (tests, measurements); 0: launch_tpl_lane's choice
-  // constants
-  DBuf crc_tab, consts;
-  // schema
-  DBuf ht, key_hash, key_off, key_blob, key_slot, slot_kind, key_w, krec;
-  uint32_t n_keys = 0, n_slots = 0, ht_mask = 0;
-  // host staging for tfrg_decode_host
-  DBuf in_bytes, in_start, in_end;
-  // arena
+// One decode as decode_device_any runs it: the three public entry points build one, finish_decode
+// re-runs a copy of the stored one with `full` / `worst_case` set.
+struct DecodeReq {
+  const uint8_t* d_bytes = nullptr;
+  uint64_t nbytes = 0;
+  Offsets off;
+  uint32_t n = 0, flags = 0;
+  hipStream_t stream = nullptr;  // NULL: the context's own
+  uint64_t cap_in = 0;      // total bytes of the ranges (tfrg_decode_host: > nbytes when they overlap); 0: nbytes
+  uint64_t bound = 0;       // no record above this; 0: the context's record_bound
+  bool full = false;        // no optimistic pass
+  bool worst_case = false;  // the value-capacity hints ignored
+};
+
+// Everything known about the last decode. Replaced as a whole: decode_device_any and tfrg_set_schema
+// clear it (`valid` false: no result), and a decode assigns it once it is enqueued.
+struct Result {
+  bool valid = false;
+  DecodeReq req;  // as it ran: stream, capacity and bound resolved (the consumers' d_bytes, nbytes and e32)
+  uint64_t cap_i64 = 0, cap_f32 = 0, cap_b = 0;
+  bool materialized = false;
+  bool hinted = false;        // ran with a value-capacity hint below its worst case
+  bool opt_pending = false;   // ran optimistically and is not confirmed yet
+  bool mat_pending = false;   // its byte materialization waits for that confirmation
+  bool rs_complete = false;   // the placed slots' identity rows are written into the device columns
+  bool cols_complete = false; // tfrg_result_device wrote the constant columns (constant_fills)
+  bool off_complete = false;  // fill_implicit_off wrote the implicit bytes_off words
+  uint32_t implicit = 0;      // TFRG_IMPLICIT_* columns the decode did not store
+  uint64_t off_mask = 0;      // slots whose bytes_off words it did not store (implicit_off_slots)
+  bool aux_zero = false;      // ran optimistically with stored statuses: aux is all 0
+  // the learned constants behind those columns as the decode ran with them (a later re-learn does not
+  // change its result), each copied only where its bit is set. Only k_tpl_lane leaves a column implicit
+  // (launch_decode), so such a decode has at most kLeanMaxSlots slots: no allocation per decode.
+  struct SlotConst {
+    int32_t rel_off;      // off_mask: the end-relative element offset
+    uint32_t elem_len;    // TFRG_IMPLICIT_BYTES_LEN: the bytes element length
+    uint16_t order_word;  // TFRG_IMPLICIT_ORDER
+  } slot[kLeanMaxSlots] = {};
+};
+
+// Every device buffer of a context. `each` is the one list of them, checked against the members.
+struct Arena {
+  DBuf crc_tab, consts;  // constants
+  DBuf ht, key_hash, key_off, key_blob, key_slot, slot_kind, key_w, krec;  // schema
+  DBuf in_bytes, in_start, in_end;  // host staging for tfrg_decode_host
+  // columns and work space of a decode
   DBuf status, aux, verdict, order, count, loc, rs, slot_base, totals, kind_totals;
-  DBuf ident;            // 0, 1, 2, ... (ident_n words): the fetched row splits of placed slots
-  size_t ident_n = 0;
+  DBuf ident;  // 0, 1, 2, ... (ident_n words): the fetched row splits of placed slots
   DBuf i64, f32, b_off, b_len, big_list, slow_list, miss, info, tsum, crc_rec, crc_base, crc_part;
   DBuf dq, dq_cnt;  // deferred packed-int64 bodies (k_body_count)
   DBuf lmask, rlist;  // k_tpl_lane's per-group miss masks and listed groups
   DBuf bdata, boff64, blb, bbig;  // TFRG_FLAG_MATERIALIZE_BYTES
-  bool materialized = false;
+  DBuf tpl, spec;  // record-shape templates, speculative placement (tfrg_learn_templates)
+  DBuf fr_tab, fr_dev;  // tfrg_index_device: chunk table, piece rows + summary
+  DBuf rg_tsum;  // tfrg_result_ragged_rows: the per-tile sums
+  DBuf sel_buf;  // tfrg_result_select_rows: the candidates' ballot words, then the per-tile sums
+  template <class F>
+  void each(F f) {
+    DBuf* const all[] = {&crc_tab, &consts, &ht, &key_hash, &key_off, &key_blob, &key_slot, &slot_kind, &key_w, &krec,
+                         &in_bytes, &in_start, &in_end, &status, &aux, &verdict, &order, &count, &loc, &rs, &slot_base,
+                         &totals, &kind_totals, &ident, &i64, &f32, &b_off, &b_len, &big_list, &slow_list, &miss, &info,
+                         &tsum, &crc_rec, &crc_base, &crc_part, &dq, &dq_cnt, &lmask, &rlist, &bdata, &boff64, &blb,
+                         &bbig, &tpl, &spec, &fr_tab, &fr_dev, &rg_tsum, &sel_buf};
+    static_assert(sizeof(all) / sizeof(*all) * sizeof(DBuf) == sizeof(Arena), "a buffer is missing from the list");
+    for (DBuf* b : all) f(*b);
+  }
+};
+
+// Switches read from the environment in tfrg_ctx_create (A/B measurements and tests)
+struct Switches {
+  bool tpl_on = true;        // TFRG_TEMPLATES (also tfrg_ctx_set_templates)
+  bool spec_on = true;       // TFRG_SPEC: speculative single-value placement
+  int tpl_stage = 1;         // TFRG_TPL_STAGE: k_tpl_lane's staged windows 0 off, 1 on large batches, 2 on any
+  uint32_t tpl_gpw = 0;      // TFRG_TPL_GPW=2, 4 or 8: its groups per wave; 0: launch_tpl_lane's choice
+  bool optimistic = true;    // TFRG_OPTIMISTIC=0: no optimistic decodes
+  bool implicit_off = true;  // TFRG_IMPLICIT_OFF=0: every bytes_off word stored
+  bool walk_beside = true;   // TFRG_WALK_BESIDE=0: large records walked before the CRC
+  uint32_t walk_blocks = 0;  // TFRG_WALK_BLOCKS: cap on its walking workgroups; 0 = automatic
+  int dense_nt = 0;          // TFRG_DENSE_NT=1: k_dense's output stores nontemporal
+  // TFRG_DEBUG_POISON_LOC="r0,r1,..." (at most 4): records whose list locations are poisoned after the count passes
+  uint32_t poison[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+};
+
+// Per context: the device, its streams and events, the arena, the schema, the learned shapes and the
+// settings. What belongs to one decode is in `res`.
+struct tfrg_ctx : Arena {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t last_stream = nullptr;  // of the last decode enqueued: arena buffers may be in use on it
+  Switches sw;
+  uint32_t lane_max = 2048;
+  uint32_t wave_stage = 0xffffffffu;  // clamped to the kernel's stage size
+  uint64_t record_bound = 0;  // tfrg_ctx_set_record_bound: no record above this (0 = unknown)
+  int num_cus = 256;
+  uint32_t cu_lds = 65536;     // LDS bytes of a CU
+  uint32_t n_keys = 0, n_slots = 0, ht_mask = 0;
+  size_t ident_n = 0;
   bool tsum_dirty = true;  // the scan words must be cleared before the next decode
   // info words: two slots, decode k using slot k % 2; k_lane_count zeroes the other one for the
   // next decode (no per-call memset). info_clean: the next slot is known to be zero.
   uint32_t info_slot = 0;
   bool info_clean = false;
-  // last batch
-  uint32_t n = 0;
-  uint64_t cap_hint = 0;  // tfrg_decode_host: total bytes of the given ranges (>= nbytes when they overlap)
+  uint32_t* info_pin = nullptr;  // pinned host copy of the info words + kind totals (confirmation)
   hipEvent_t order_ev = nullptr;  // orders a decode on a new stream after the previous one
   hipEvent_t consumer_ev[2] = {nullptr, nullptr};  // fence_open / fence_close: consumer stream -> decode stream -> consumer
-  int dense_nt = 0;  // k_dense's output stores nontemporal (env TFRG_DENSE_NT=1, for A/B measurements)
-  uint64_t nbytes = 0;
-  uint64_t cap_i64 = 0, cap_f32 = 0, cap_b = 0;
-  bool have_result = false;
-  bool rs_complete = false;  // the placed slots' identity rows are written into the device columns
+  Result res;  // the last decode
   // record-shape templates (tfrg_learn_templates): host key table, device templates
   std::unordered_map<std::string, uint32_t> key_id;
   std::vector<int32_t> key_slot_h;  // [4 * key]: flags, slot per kind
-  DBuf tpl;
   uint32_t n_tpl = 0;
   uint32_t tpl_w = 0;  // window words of the templates (16 / 32 / 64)
   size_t tpl_img_off = 0;  // the lane image follows the window-form templates in tpl
@@ -136,68 +196,30 @@ struct tfrg_ctx {
   bool tpl_learned = false;
   bool tpl_full = false;  // the templates took every record of their learning sample
   uint32_t tpl_frames = 0;  // frame classes of the kept templates: bit 0 spec, bit 1 unchecked
-  bool tpl_on = true;
   // speculative single-value placement (DevSchema::spec), derived from the templates
   std::vector<uint8_t> slot_kind_h;
-  DBuf spec;
   std::vector<uint32_t> spec_h;  // host copy (k_tpl_lane's placement targets)
   bool have_spec = false;
-  bool spec_on = true;
+  // what the learned shapes have in common (Learned): an optimistic decode (launch_decode: a batch of
+  // C1-shaped records whose templates took the learning sample runs as k_tpl_lane alone) leaves such
+  // columns implicit and snapshots the constant into its Result
+  bool ord_const = false;     // every shape has the same order words
+  bool len_const = false;     // ... and the same bytes element lengths
+  std::vector<uint32_t> const_len;  // per slot: that length
+  uint64_t off_rel = 0;       // bytes slots at one end-relative offset in every shape
+  std::vector<int32_t> rel_off;  // per slot: that offset
   // optional per-stage HIP events (tfrg_ctx_set_profiling)
   bool profiling = false;
   bool have_events = false;
   hipEvent_t ev[kNumStages + 1] = {};
-  // value-capacity hints (tfrg_ctx_set_value_caps; 0: the worst case) and the last decode's
-  // arguments, for the transparent worst-case re-run when a hint proved too small
+  // value-capacity hints (tfrg_ctx_set_value_caps; 0: the worst case)
   uint64_t hint_i64 = 0, hint_f32 = 0, hint_b = 0;
-  bool hinted = false;  // the last decode ran with a hint below its worst case
-  bool no_hints = false;  // (the re-run: the worst case)
   uint64_t hint_reruns = 0;  // decodes re-run: a hint was too small, or an optimistic decode incomplete
-  // optimistic decodes (launch_decode): a batch of C1-shaped records whose templates took the learning
-  // sample is launched as k_tpl_lane alone (its last workgroup finishes it); the decode is complete once tfrg_result_info
-  // (or tfrg_result_device) has read that no record was left, else it is re-run with every pass
-  bool optimistic_on = true;  // (env TFRG_OPTIMISTIC=0: off, for A/B measurements)
-  bool walk_beside = true;    // (env TFRG_WALK_BESIDE=0: large records walked before the CRC, A/B)
-  uint32_t walk_blocks = 0;   // (env TFRG_WALK_BLOCKS: cap on its walking workgroups; 0 = automatic)
-  bool no_quiet = false;      // (the re-run)
-  bool opt_pending = false;   // the last decode ran optimistically and is not confirmed yet
-  bool ord_const = false;     // (Learned::ord_const) of the learned shapes
-  bool len_const = false;     // (Learned::len_const)
-  std::vector<uint32_t> const_len;  // per slot: the bytes element length of every learned shape
-  bool implicit_off_on = true;  // (env TFRG_IMPLICIT_OFF=0: every bytes_off word stored, A/B and tests)
-  uint64_t off_rel = 0;       // (Learned::off_rel) bytes slots at one end-relative offset in every shape
-  std::vector<int32_t> rel_off;  // (Learned::rel_off) per slot: that offset
-  uint64_t last_off_mask = 0; // slots whose bytes_off words the last decode did not store (implicit_off_slots)
-  std::vector<int32_t> last_rel_off;  // rel_off as that decode ran with it (a later re-learn does not change its result)
-  bool off_complete = false;  // fill_implicit_off wrote them into the device column
-  uint32_t last_implicit = 0; // TFRG_IMPLICIT_* columns the last decode did not store
-  bool last_aux_zero = false; // the last decode ran optimistically with stored statuses: aux is all 0
-  uint32_t* info_pin = nullptr;  // pinned host copy of the info words + kind totals (confirmation)
-  bool cols_complete = false; // tfrg_result_device filled them into the device columns
-  bool mat_pending = false;   // an optimistic decode's byte materialization waits for its confirmation
-  struct LastCall {
-    const uint8_t* d_bytes;
-    uint64_t nbytes;
-    uint64_t cap_in;
-    uint64_t bound;
-    uint32_t n, flags;
-    hipStream_t st;
-  } last{};
-  Offsets last_off{};
-  // tfrg_index_device: chunk table, piece rows + summary (device), their pinned host staging
   uint32_t index_chunk = kIndexChunkDefault;  // tfrg_ctx_set_index_chunk
-  DBuf fr_tab, fr_dev;
-  // tfrg_result_ragged_rows: rows per tile (tfrg_ctx_set_ragged_tile), the per-tile sums
-  uint32_t ragged_tile = kRaggedTileDefault;
-  DBuf rg_tsum;
-  // tfrg_result_select_rows: candidates per tile (tfrg_ctx_set_select_tile), the ballot words of the
-  // candidates followed by the per-tile sums
-  uint32_t select_tile = kSelTileDefault;
-  DBuf sel_buf;
-  void* fr_pin = nullptr;
+  uint32_t ragged_tile = kRaggedTileDefault;  // tfrg_ctx_set_ragged_tile: rows per tile
+  uint32_t select_tile = kSelTileDefault;     // tfrg_ctx_set_select_tile: candidates per tile
+  void* fr_pin = nullptr;  // tfrg_index_device: pinned host staging
   size_t fr_pin_cap = 0;
-  // debug hook: records whose list locations are poisoned after the count passes (tests)
-  uint32_t poison[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
 };
 
 extern "C" {
@@ -213,22 +235,22 @@ int tfrg_ctx_create(int device, tfrg_ctx** out) {
   HIP_TRY(hipSetDevice(device));
   tfrg_ctx* c = new tfrg_ctx();
   c->device = device;
-  if (const char* e = getenv("TFRG_TEMPLATES")) c->tpl_on = atoi(e) != 0;  // (A/B measurements)
-  if (const char* e = getenv("TFRG_SPEC")) c->spec_on = atoi(e) != 0;
-  if (const char* e = getenv("TFRG_TPL_STAGE")) c->tpl_stage = atoi(e);
-  if (const char* e = getenv("TFRG_TPL_GPW")) {
-    const int v = atoi(e);
-    if (v == 2 || v == 4 || v == 8) c->tpl_gpw = (uint32_t)v;
-  }
-  if (const char* e = getenv("TFRG_OPTIMISTIC")) c->optimistic_on = atoi(e) != 0;
-  if (const char* e = getenv("TFRG_IMPLICIT_OFF")) c->implicit_off_on = atoi(e) != 0;
-  if (const char* e = getenv("TFRG_WALK_BESIDE")) c->walk_beside = atoi(e) != 0;
-  if (const char* e = getenv("TFRG_WALK_BLOCKS")) c->walk_blocks = (uint32_t)atoi(e);
-  if (const char* e = getenv("TFRG_DENSE_NT")) c->dense_nt = atoi(e) != 0;
-  if (const char* e = getenv("TFRG_DEBUG_POISON_LOC")) {  // "r0,r1,..." (at most 4)
+  auto num = [](const char* name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
+  Switches& s = c->sw;
+  s.tpl_on = num("TFRG_TEMPLATES", 1) != 0;
+  s.spec_on = num("TFRG_SPEC", 1) != 0;
+  s.optimistic = num("TFRG_OPTIMISTIC", 1) != 0;
+  s.implicit_off = num("TFRG_IMPLICIT_OFF", 1) != 0;
+  s.walk_beside = num("TFRG_WALK_BESIDE", 1) != 0;
+  s.tpl_stage = num("TFRG_TPL_STAGE", 1);
+  const int gpw = num("TFRG_TPL_GPW", 0);
+  if (gpw == 2 || gpw == 4 || gpw == 8) s.tpl_gpw = (uint32_t)gpw;
+  s.walk_blocks = (uint32_t)num("TFRG_WALK_BLOCKS", 0);
+  s.dense_nt = num("TFRG_DENSE_NT", 0) != 0;
+  if (const char* e = getenv("TFRG_DEBUG_POISON_LOC")) {
     char* q = const_cast<char*>(e);
     for (int i = 0; i < 4 && *q; ++i) {
-      c->poison[i] = (uint32_t)strtoul(q, &q, 10);
+      s.poison[i] = (uint32_t)strtoul(q, &q, 10);
       while (*q == ',' || *q == ' ') ++q;
     }
   }
@@ -293,13 +315,7 @@ int tfrg_ctx_destroy(tfrg_ctx* c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
   if (c->last_stream) (void)hipStreamSynchronize(c->last_stream);
-  DBuf* all[] = {&c->crc_tab, &c->consts, &c->ht, &c->key_hash, &c->key_off, &c->key_blob, &c->key_slot,
-                 &c->slot_kind, &c->key_w, &c->krec, &c->in_bytes, &c->in_start, &c->in_end, &c->status, &c->aux, &c->verdict,
-                 &c->order, &c->count, &c->loc, &c->rs, &c->ident, &c->slot_base, &c->totals, &c->kind_totals, &c->i64,
-                 &c->f32, &c->b_off, &c->b_len, &c->big_list, &c->slow_list, &c->miss, &c->info, &c->tsum,
-                 &c->bdata, &c->boff64, &c->blb, &c->bbig, &c->crc_rec, &c->crc_base, &c->crc_part, &c->tpl, &c->spec,
-                 &c->dq, &c->dq_cnt, &c->lmask, &c->rlist, &c->fr_tab, &c->fr_dev, &c->rg_tsum, &c->sel_buf};
-  for (DBuf* b : all) b->release();
+  c->each([](DBuf& b) { b.release(); });
   if (c->order_ev) (void)hipEventDestroy(c->order_ev);
   for (hipEvent_t e : c->consumer_ev)
     if (e) (void)hipEventDestroy(e);
@@ -334,15 +350,8 @@ int tfrg_ctx_set_value_caps(tfrg_ctx* c, uint64_t int64_values, uint64_t float_v
 
 int tfrg_ctx_device_bytes(tfrg_ctx* c, uint64_t* bytes, uint64_t* reruns) {
   if (!c) return TFRG_E_ARG;
-  const DBuf* all[] = {&c->crc_tab, &c->consts, &c->ht, &c->key_hash, &c->key_off, &c->key_blob, &c->key_slot,
-                       &c->slot_kind, &c->key_w, &c->krec, &c->in_bytes, &c->in_start, &c->in_end, &c->status,
-                       &c->aux, &c->verdict, &c->order, &c->count, &c->loc, &c->rs, &c->ident, &c->slot_base,
-                       &c->totals, &c->kind_totals, &c->i64, &c->f32, &c->b_off, &c->b_len, &c->big_list,
-                       &c->slow_list, &c->miss, &c->info, &c->tsum, &c->bdata, &c->boff64, &c->blb, &c->bbig,
-                       &c->crc_rec, &c->crc_base, &c->crc_part, &c->tpl, &c->spec, &c->dq, &c->dq_cnt, &c->lmask,
-                       &c->rlist, &c->fr_tab, &c->fr_dev, &c->rg_tsum, &c->sel_buf};
   uint64_t t = 0;
-  for (const DBuf* b : all) t += b->cap;
+  c->each([&t](const DBuf& b) { t += b.cap; });
   if (bytes) *bytes = t;
   if (reruns) *reruns = c->hint_reruns;
   return 0;
@@ -474,7 +483,7 @@ int tfrg_ctx_set_profiling(tfrg_ctx* c, int on) {
 }
 
 int tfrg_profile_last(tfrg_ctx* c, float* ms, const char** names, int cap) {
-  if (!c || !c->have_events || !c->have_result) return TFRG_E_ARG;
+  if (!c || !c->have_events || !c->res.valid) return TFRG_E_ARG;
   HIP_TRY(hipEventSynchronize(c->ev[kNumStages]));
   const int k = cap < kNumStages ? cap : (int)kNumStages;
   for (int i = 0; i < k; ++i) {
@@ -501,7 +510,7 @@ int tfrg_set_schema(tfrg_ctx* c, uint32_t n_keys, const uint8_t* key_blob, const
   HIP_TRY(hipSetDevice(c->device));
   if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
   // a failure below may leave buffers reallocated: no schema and no result until this succeeds
-  c->have_result = false;
+  c->res = {};
   c->n_keys = c->n_slots = 0;
   c->ht_mask = 0;
   uint32_t hsz = 16;
@@ -592,13 +601,13 @@ static DevSchema schema_view(const tfrg_ctx* c) {
   s.tpl_img = s.tpl + c->tpl_img_off;
   s.tpl_img_words = c->tpl_img_words;
   s.tpl_tab_words = c->tpl_tab_words;
-  s.n_tpl = c->tpl_on ? c->n_tpl : 0u;
+  s.n_tpl = c->sw.tpl_on ? c->n_tpl : 0u;
   s.tpl_w = c->tpl_w;
   // speculative placement is a property of the learned shapes' schema (a slot that is one inline
   // value in every shape), not of the template match: it stays on with the templates off, where
   // k_lane_count places those values itself
   // (and without any shape: learn_single_slots)
-  s.spec = c->spec_on && c->have_spec ? c->spec.as<uint32_t>() : nullptr;
+  s.spec = c->sw.spec_on && c->have_spec ? c->spec.as<uint32_t>() : nullptr;
   return s;
 }
 
@@ -667,60 +676,71 @@ extern "C" int tfrg_template_words(tfrg_ctx* c, uint32_t* out, uint64_t cap, uin
 
 extern "C" int tfrg_ctx_set_templates(tfrg_ctx* c, int on) {
   if (!c) return TFRG_E_ARG;
-  c->tpl_on = on != 0;
+  c->sw.tpl_on = on != 0;
   return 0;
 }
 
-static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const Offsets& off, uint32_t n,
-                             uint32_t flags, void* stream);
+static int decode_device_any(tfrg_ctx* c, const DecodeReq& req);
 
 int tfrg_decode_device(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_start,
                        const uint64_t* d_end, uint32_t n, uint32_t flags, void* stream) {
-  Offsets off;
-  off.s64 = d_start;
-  off.e64 = d_end;
-  return decode_device_any(c, d_bytes, nbytes, off, n, flags, stream);
+  DecodeReq q{d_bytes, nbytes, {}, n, flags, static_cast<hipStream_t>(stream)};
+  q.off.s64 = d_start;
+  q.off.e64 = d_end;
+  return decode_device_any(c, q);
 }
 
 int tfrg_decode_device32(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const uint32_t* d_start32,
                          const uint32_t* d_end32, uint32_t first_start, uint32_t n, uint32_t flags, void* stream) {
   if (n && !d_end32) return TFRG_E_ARG;
-  Offsets off;
-  off.s32 = d_start32;
-  off.e32 = d_end32;
-  off.first = first_start;
-  off.mode = d_start32 ? kOffU32 : kOffEnds;
-  return decode_device_any(c, d_bytes, nbytes, off, n, flags, stream);
+  DecodeReq q{d_bytes, nbytes, {}, n, flags, static_cast<hipStream_t>(stream)};
+  q.off.s32 = d_start32;
+  q.off.e32 = d_end32;
+  q.off.first = first_start;
+  q.off.mode = d_start32 ? kOffU32 : kOffEnds;
+  return decode_device_any(c, q);
 }
 
 // TFRG_FLAG_MATERIALIZE_BYTES: the bytes views of the decode just enqueued on `st` gathered into one
 // contiguous column. Reads the decode's kind totals and b_off / b_len, so it runs only once they are
 // final: after a full decode at once, after an optimistic one once finish_decode has confirmed it.
-static hipError_t launch_materialize_last(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, uint64_t cap_in,
-                                          uint64_t cap_b, hipStream_t st) {
+static hipError_t launch_materialize_last(tfrg_ctx* c, const DecodeReq& q, uint64_t cap_b) {
   uint32_t* const info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
   DevBytes d;
-  d.in = d_bytes;
-  d.in_readable = (nbytes + 15) & ~15ull;
+  d.in = q.d_bytes;
+  d.in_readable = (q.nbytes + 15) & ~15ull;
   d.b_off = c->b_off.as<uint32_t>();
   d.b_len = c->b_len.as<uint32_t>();
   d.kind_totals = c->kind_totals.as<uint64_t>();
   d.offsets = c->boff64.as<uint64_t>();
   d.offsets_cap = cap_b;
   d.data = c->bdata.as<uint8_t>();
-  d.data_cap = cap_in + 16;
+  d.data_cap = q.cap_in + 16;
   d.lb = c->blb.as<uint64_t>();
   d.ticket = info + kInfoBytesTicket;
   d.big_count = info + kInfoBytesBig;
   d.big_list = c->bbig.as<uint32_t>();
   d.overflow = info + kInfoOverflow;
-  return launch_materialize(d, c->num_cus, st);
+  return launch_materialize(d, c->num_cus, q.stream);
 }
 
-static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const Offsets& off, uint32_t n,
-                             uint32_t flags, void* stream) {
+// The buffers of one group at the sizes a decode needs. Growing one frees the old allocation, so the
+// previous stream's work, which may still read it, is waited for first.
+static int ensure_group(tfrg_ctx* c, const char* group, std::initializer_list<std::pair<DBuf*, size_t>> needs) {
+  bool grow = false;
+  for (const auto& [buf, bytes] : needs) grow |= buf->cap < bytes;
+  if (grow && c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
+  for (const auto& [buf, bytes] : needs)
+    if (buf->ensure(bytes) != hipSuccess) {
+      set_error(std::string("device allocation failed") + group);
+      return TFRG_E_NOMEM;
+    }
+  return 0;
+}
+
+static int decode_device_any(tfrg_ctx* c, const DecodeReq& req) {
   if (!c) return TFRG_E_ARG;
-  if (nbytes >= (1ull << 32)) {
+  if (req.nbytes >= (1ull << 32)) {
     set_error("batch larger than 4 GiB: split it");
     return TFRG_E_LIMIT;
   }
@@ -730,15 +750,27 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
     if (st) return st;
   }
   HIP_TRY(hipSetDevice(c->device));
-  c->have_result = false;  // set again once this decode is enqueued
-  hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
-  if (flags & TFRG_FLAG_STRICT_CRC) flags &= ~TFRG_FLAG_NO_CRC;  // strict mode needs the verdicts
+  c->res = {};  // no result until this decode is enqueued (the checks above leave the previous one)
+  // the request as it runs (and as the result keeps it): stream, flags, capacity and bound resolved
+  DecodeReq q = req;
+  if (!q.stream) q.stream = c->own_stream;
+  if (q.flags & TFRG_FLAG_STRICT_CRC) q.flags &= ~TFRG_FLAG_NO_CRC;  // strict mode needs the verdicts
+  // value capacities: bounds for disjoint ranges (one int64 per byte, one float per 4, one bytes
+  // element per 2); tfrg_decode_host passes the total of its ranges, which covers overlaps. A batch
+  // of overlapping device ranges that exceeds them is reported by tfrg_result_info (TFRG_E_LIMIT).
+  q.cap_in = std::max(q.cap_in, q.nbytes);
+  if (!q.bound) q.bound = c->record_bound;
+  const hipStream_t st = q.stream;
+  const uint32_t n = q.n, flags = q.flags;
+  const uint64_t nbytes = q.nbytes, cap_in = q.cap_in;
   // a decode on another stream than the previous one must not overtake it (shared arena)
   if (c->last_stream && c->last_stream != st) {
     if (!c->order_ev) HIP_TRY(hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(c->order_ev, c->last_stream));
     HIP_TRY(hipStreamWaitEvent(st, c->order_ev, 0));
   }
+  Result r;
+  uint64_t &cap_i64 = r.cap_i64, &cap_f32 = r.cap_f32, &cap_b = r.cap_b;
   const uint32_t S = c->n_slots;
   const uint64_t nn = n ? n : 1;
   const uint64_t ngroups = (nn + 63) / 64;  // k_tpl_lane's 64-record groups
@@ -747,47 +779,28 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   const uint32_t n_chunks = (n_tiles + (1u << kSpineChunkShift) - 1u) >> kSpineChunkShift;
   // tile sums + look-back words + per-slot irregular-record counts (DevOut::irr)
   const uint64_t tsum_words = (uint64_t)S * tile_stride + 2ull * S * n_chunks + S;
-  // value capacities: bounds for disjoint ranges (one int64 per byte, one float per 4, one bytes
-  // element per 2); tfrg_decode_host passes the total of its ranges, which covers overlaps. A batch
-  // of overlapping device ranges that exceeds them is reported by tfrg_result_info (TFRG_E_LIMIT).
-  const uint64_t cap_in = c->cap_hint > nbytes ? c->cap_hint : nbytes;
-  c->cap_hint = 0;
-  uint64_t cap_i64 = cap_in + 16, cap_f32 = cap_in / 4 + 16, cap_b = cap_in / 2 + 16;
+  cap_i64 = cap_in + 16, cap_f32 = cap_in / 4 + 16, cap_b = cap_in / 2 + 16;
   // value-capacity hints (tfrg_ctx_set_value_caps) below the worst case: a decode that overflows one
-  // is re-run with the worst case by tfrg_result_info (decode_rerun), before any result is read
-  c->hinted = false;
+  // is re-run with the worst case by tfrg_result_info (finish_decode), before any result is read
   auto hint = [&](uint64_t h, uint64_t& cap) {
-    if (h && h + 16 < cap) {
+    if (!q.worst_case && h && h + 16 < cap) {
       cap = h + 16;
-      c->hinted = true;
+      r.hinted = true;
     }
   };
-  if (!c->no_hints) {
-    hint(c->hint_i64, cap_i64);
-    hint(c->hint_f32, cap_f32);
-    hint(c->hint_b, cap_b);
-  }
-  // growing an arena buffer frees the old one: wait for work that may still read it
-  bool grow = c->status.cap < nn * 4 || c->aux.cap < nn * 8 || c->verdict.cap < nn ||
-              c->order.cap < S * nn * 2 || c->count.cap < S * nn * 4 || c->loc.cap < S * nn * 8 ||
-              c->rs.cap < S * (nn + 1) * 4 || c->i64.cap < cap_i64 * 8 || c->f32.cap < cap_f32 * 4 ||
-              c->b_off.cap < cap_b * 4 || c->b_len.cap < cap_b * 4 || c->big_list.cap < nn * 4 ||
-              c->slow_list.cap < nn * 4 || c->tsum.cap < tsum_words * 4 + 16 || c->crc_rec.cap < nn * 4 ||
-              c->crc_base.cap < nn * 8 || c->crc_part.cap < nn * 8 || c->lmask.cap < ngroups * 8 ||
-              c->rlist.cap < ngroups * 4;
-  if (grow && c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
+  hint(c->hint_i64, cap_i64);
+  hint(c->hint_f32, cap_f32);
+  hint(c->hint_b, cap_b);
   const size_t tsum_cap0 = c->tsum.cap;
-  if (c->status.ensure(nn * 4) || c->aux.ensure(nn * 8) || c->verdict.ensure(nn) || c->order.ensure(S * nn * 2) ||
-      c->count.ensure(S * nn * 4) || c->loc.ensure(S * nn * 8) || c->rs.ensure(S * (nn + 1) * 4) ||
-      c->slot_base.ensure((S + 1) * 8) || c->totals.ensure((S + 1) * 4) || c->kind_totals.ensure(32) ||
-      c->i64.ensure(cap_i64 * 8) || c->f32.ensure(cap_f32 * 4) || c->b_off.ensure(cap_b * 4) ||
-      c->b_len.ensure(cap_b * 4) || c->big_list.ensure(nn * 4) || c->slow_list.ensure(nn * 4) ||
-      c->miss.ensure(kMissCap * 16ull) || c->info.ensure(2 * kInfoCount * 4) ||
-      c->tsum.ensure(tsum_words * 4 + 16) || c->crc_rec.ensure(nn * 4) || c->crc_base.ensure(nn * 8) ||
-      c->crc_part.ensure(nn * 8) || c->lmask.ensure(ngroups * 8) || c->rlist.ensure(ngroups * 4)) {
-    set_error("device allocation failed");
-    return TFRG_E_NOMEM;
-  }
+  if (const int rc = ensure_group(
+          c, "",
+          {{&c->status, nn * 4}, {&c->aux, nn * 8}, {&c->verdict, nn}, {&c->order, S * nn * 2}, {&c->count, S * nn * 4},
+           {&c->loc, S * nn * 8}, {&c->rs, S * (nn + 1) * 4}, {&c->slot_base, (S + 1) * 8}, {&c->totals, (S + 1) * 4},
+           {&c->kind_totals, 32}, {&c->i64, cap_i64 * 8}, {&c->f32, cap_f32 * 4}, {&c->b_off, cap_b * 4},
+           {&c->b_len, cap_b * 4}, {&c->big_list, nn * 4}, {&c->slow_list, nn * 4}, {&c->miss, kMissCap * 16ull},
+           {&c->info, 2 * kInfoCount * 4}, {&c->tsum, tsum_words * 4 + 16}, {&c->crc_rec, nn * 4}, {&c->crc_base, nn * 8},
+           {&c->crc_part, nn * 8}, {&c->lmask, ngroups * 8}, {&c->rlist, ngroups * 4}}))
+    return rc;
   // per-call counters (Guideline 16: every polled word zero per call): this decode's info slot was
   // zeroed by the previous decode's k_lane_count, else (a fresh context, an empty batch or a failed
   // launch before) here
@@ -808,28 +821,23 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   const bool mat = (flags & TFRG_FLAG_MATERIALIZE_BYTES) != 0;
   const uint64_t lb_words = materialize_lb_words(cap_b);
   if (mat) {
-    const bool g2 = c->bdata.cap < cap_in + 16 || c->boff64.cap < (cap_b + 1) * 8 || c->blb.cap < lb_words * 8 ||
-                    c->bbig.cap < cap_b * 4;
-    if (g2 && c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
-    if (c->bdata.ensure(cap_in + 16) || c->boff64.ensure((cap_b + 1) * 8) || c->blb.ensure(lb_words * 8) ||
-        c->bbig.ensure(cap_b * 4)) {
-      set_error("device allocation failed (materialized bytes)");
-      return TFRG_E_NOMEM;
-    }
+    if (const int rc = ensure_group(c, " (materialized bytes)", {{&c->bdata, cap_in + 16}, {&c->boff64, (cap_b + 1) * 8},
+                                                                {&c->blb, lb_words * 8}, {&c->bbig, cap_b * 4}}))
+      return rc;
     HIP_TRY(hipMemsetAsync(c->blb.p, 0, lb_words * 8, st));
     if (!n) HIP_TRY(hipMemsetAsync(c->boff64.p, 0, 8, st));
   }
   if (!S || !n) HIP_TRY(hipMemsetAsync(c->kind_totals.p, 0, 32, st));
 
   DevBatch b;
-  b.bytes = d_bytes;
+  b.bytes = q.d_bytes;
   b.nbytes = nbytes;
-  b.start = off.s64;
-  b.end = off.e64;
-  b.start32 = off.s32;
-  b.end32 = off.e32;
-  b.first = off.first;
-  b.omode = off.mode;
+  b.start = q.off.s64;
+  b.end = q.off.e64;
+  b.start32 = q.off.s32;
+  b.end32 = q.off.e32;
+  b.first = q.off.first;
+  b.omode = q.off.mode;
   b.n = n;
   b.flags = flags;
   DevOut o;
@@ -868,10 +876,10 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   o.rlist = c->rlist.as<uint32_t>();
   LaunchCfg cfg;
   cfg.num_cus = c->num_cus;
-  cfg.tpl_cu_lds = c->tpl_stage ? c->cu_lds : 0u;
-  cfg.tpl_stage_any = c->tpl_stage == 2;
-  cfg.tpl_gpw = c->tpl_gpw;
-  cfg.lean = c->tpl_on && c->n_tpl;
+  cfg.tpl_cu_lds = c->sw.tpl_stage ? c->cu_lds : 0u;
+  cfg.tpl_stage_any = c->sw.tpl_stage == 2;
+  cfg.tpl_gpw = c->sw.tpl_gpw;
+  cfg.lean = c->sw.tpl_on && c->n_tpl;
   cfg.tpl_full = cfg.lean && c->tpl_full;
   cfg.tpl_unchecked = cfg.lean && (c->tpl_frames & 2u) != 0;
   cfg.spec_h = c->spec_h.empty() ? nullptr : c->spec_h.data();
@@ -883,37 +891,29 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
   cfg.wave_grid = (int)(wave_blocks < 1 ? 1 : (wave_blocks < wave_cap ? wave_blocks : wave_cap));
   cfg.lane_max = c->lane_max;
   cfg.wave_stage = c->wave_stage;
-  memcpy(cfg.poison, c->poison, sizeof(cfg.poison));
+  memcpy(cfg.poison, c->sw.poison, sizeof(cfg.poison));
   // (the poison hook needs the gathers it tests)
-  cfg.optimistic = c->optimistic_on && !c->no_quiet && c->poison[0] == 0xffffffffu;
-  cfg.walk_beside = c->walk_beside;
-  cfg.walk_blocks = c->walk_blocks;
+  cfg.optimistic = c->sw.optimistic && !q.full && c->sw.poison[0] == 0xffffffffu;
+  cfg.walk_beside = c->sw.walk_beside;
+  cfg.walk_blocks = c->sw.walk_blocks;
   cfg.ran_optimistic = false;
   cfg.ran_quiet_big = false;
   cfg.ord_const = c->ord_const;
   cfg.len_const = c->len_const && !mat;  // (the byte gather reads the lengths)
   cfg.implicit = 0;
-  cfg.off_rel = c->implicit_off_on ? c->off_rel : 0ull;  // (launch_decode: u32 offsets, no byte gather)
+  cfg.off_rel = c->sw.implicit_off ? c->off_rel : 0ull;  // (launch_decode: u32 offsets, no byte gather)
   cfg.implicit_off = 0;
-  const uint64_t bound = c->call_bound ? c->call_bound : c->record_bound;
-  c->call_bound = 0;
-  c->last = tfrg_ctx::LastCall{d_bytes, nbytes, cap_in, bound, n, flags, st};
-  c->last_off = off;
   // deferred packed bodies when records above lane_max may be walked from HBM: one 64-row block
   // (2,048 entries of 16 bytes) per 256 KiB of input, at least 16
   o.dq = nullptr;
   o.dq_cnt = nullptr;
   o.dq_blocks = 0;
   cfg.body_count = false;
-  if (n && (bound == 0 || bound > c->lane_max)) {
+  if (n && (q.bound == 0 || q.bound > c->lane_max)) {
     uint64_t blocks = nbytes >> 18;
     blocks = blocks < 16 ? 16 : (blocks > (1u << 16) ? (1u << 16) : blocks);
     const size_t qb = (size_t)blocks * 64u * kDeferK * 16u, cb = (size_t)blocks * 64u;
-    if ((c->dq.cap < qb || c->dq_cnt.cap < cb) && c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
-    if (c->dq.ensure(qb) || c->dq_cnt.ensure(cb)) {
-      set_error("device allocation failed (deferred bodies)");
-      return TFRG_E_NOMEM;
-    }
+    if (const int rc = ensure_group(c, " (deferred bodies)", {{&c->dq, qb}, {&c->dq_cnt, cb}})) return rc;
     o.dq = c->dq.as<uint4>();
     o.dq_cnt = c->dq_cnt.as<uint8_t>();
     o.dq_blocks = (uint32_t)blocks;
@@ -932,7 +932,7 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
     // (an optimistic decode that leaves records writes no kind totals and is re-run in full: its
     // byte views are gathered only once finish_decode has confirmed it)
     if (e == hipSuccess && mat && S && !cfg.ran_optimistic) {
-      e = launch_materialize_last(c, d_bytes, nbytes, cap_in, cap_b, st);
+      e = launch_materialize_last(c, q, cap_b);
     } else if (e == hipSuccess && mat && !S) {
       e = hipMemsetAsync(c->boff64.p, 0, 8, st);  // no slots: no elements
     }
@@ -944,27 +944,26 @@ static int decode_device_any(tfrg_ctx* c, const uint8_t* d_bytes, uint64_t nbyte
     }
   }
   c->info_clean = n != 0;  // (k_lane_count ran: the other slot is zero)
-  c->n = n;
-  c->nbytes = nbytes;
-  c->cap_i64 = cap_i64;
-  c->cap_f32 = cap_f32;
-  c->cap_b = cap_b;
   c->last_stream = st;
-  c->materialized = mat;
-  c->have_result = true;
-  c->rs_complete = false;
-  c->opt_pending = n != 0 && cfg.ran_optimistic;
   // (an optimistic decode without shapes leaves the lane kernel's tile sums in the scan words: the
   // next decode clears them; one with shapes writes none)
   if (n != 0 && cfg.ran_quiet_big) c->tsum_dirty = true;
-  c->mat_pending = c->opt_pending && mat && S;
-  c->last_implicit = n != 0 ? cfg.implicit : 0u;
-  c->last_off_mask = n != 0 ? cfg.implicit_off : 0ull;
-  if (c->last_off_mask) c->last_rel_off = c->rel_off;
-  c->off_complete = false;
+  r.valid = true;
+  r.materialized = mat;
+  r.opt_pending = n != 0 && cfg.ran_optimistic;
+  r.mat_pending = r.opt_pending && mat && S;
+  r.implicit = n != 0 ? cfg.implicit : 0u;
+  r.off_mask = n != 0 ? cfg.implicit_off : 0ull;
   // (k_tpl_lane stored status and verdict per record and no aux: every record of a confirmed decode is OK)
-  c->last_aux_zero = n != 0 && cfg.ran_optimistic && !cfg.ran_quiet_big && !(cfg.implicit & TFRG_IMPLICIT_STATUS);
-  c->cols_complete = false;
+  r.aux_zero = r.opt_pending && !cfg.ran_quiet_big && !(cfg.implicit & TFRG_IMPLICIT_STATUS);
+  for (uint32_t k = 0; (r.implicit || r.off_mask) && k < S && k < kLeanMaxSlots; ++k) {
+    Result::SlotConst& sc = r.slot[k];
+    if ((r.off_mask >> k) & 1ull) sc.rel_off = c->rel_off[k];
+    if (r.implicit & TFRG_IMPLICIT_ORDER) sc.order_word = (uint16_t)(c->tpl_h[kLtSlot + 3 * k] >> 16);
+    if ((r.implicit & TFRG_IMPLICIT_BYTES_LEN) && k < c->const_len.size()) sc.elem_len = c->const_len[k];
+  }
+  r.req = q;
+  c->res = r;
   return 0;
 }
 
@@ -992,14 +991,16 @@ int tfrg_decode_host(tfrg_ctx* c, const uint8_t* h_bytes, uint64_t nbytes, const
     if (b > a) total += b - a;
     if (h_end[i] > a && h_end[i] - a > widest) widest = h_end[i] - a;
   }
-  if (!c->tpl_learned && c->n_keys && c->tpl_on) {  // record shapes of the first host batch of a schema
+  if (!c->tpl_learned && c->n_keys && c->sw.tpl_on) {  // record shapes of the first host batch of a schema
     const int t = tfrg_learn_templates(c, h_bytes, nbytes, h_start, h_end, n, flags);
     if (t < 0) return t;
   }
-  c->cap_hint = total;
-  c->call_bound = widest ? widest : 1;
-  return tfrg_decode_device(c, c->in_bytes.as<uint8_t>(), nbytes, c->in_start.as<uint64_t>(),
-                            c->in_end.as<uint64_t>(), n, flags, st);
+  DecodeReq q{c->in_bytes.as<uint8_t>(), nbytes, {}, n, flags, st};
+  q.off.s64 = c->in_start.as<uint64_t>();
+  q.off.e64 = c->in_end.as<uint64_t>();
+  q.cap_in = total;
+  q.bound = widest ? widest : 1;
+  return decode_device_any(c, q);
 }
 
 // The last decode's info words and kind totals (synchronizes its stream). The same decode is re-run
@@ -1010,38 +1011,33 @@ static int finish_decode(tfrg_ctx* c, uint32_t* h, uint64_t* kt) {
   bool widened = false;
   // (into pinned memory, allocated with the context: two DMA copies instead of staged pageable ones)
   for (;;) {
+    Result& r = c->res;
     HIP_TRY(hipMemcpyAsync(c->info_pin, c->info.as<uint32_t>() + c->info_slot * kInfoCount, kInfoCount * 4,
                            hipMemcpyDeviceToHost, c->last_stream));
     HIP_TRY(hipMemcpyAsync(c->info_pin + kInfoCount, c->kind_totals.p, 32, hipMemcpyDeviceToHost, c->last_stream));
     HIP_TRY(hipStreamSynchronize(c->last_stream));
     memcpy(h, c->info_pin, kInfoCount * 4);
     memcpy(kt, c->info_pin + kInfoCount, 32);
-    const bool full = c->opt_pending && h[kInfoResid] != 0;  // (records no template took)
-    const bool widen = h[kInfoOverflow] && c->hinted && !widened;
+    const bool full = r.opt_pending && h[kInfoResid] != 0;  // (records no template took)
+    const bool widen = h[kInfoOverflow] && r.hinted && !widened;
     if (!full && !widen) {
-      if (!c->mat_pending) break;
+      if (!r.mat_pending) break;
       // a confirmed optimistic decode: its byte views now, then its info words again (the gather
       // reports an overflow there)
-      c->mat_pending = false;
-      const tfrg_ctx::LastCall& L = c->last;
-      HIP_TRY(launch_materialize_last(c, L.d_bytes, L.nbytes, L.cap_in, c->cap_b, c->last_stream));
+      r.mat_pending = false;
+      HIP_TRY(launch_materialize_last(c, r.req, r.cap_b));
       continue;
     }
-    const tfrg_ctx::LastCall L = c->last;
-    c->no_quiet = true;
-    c->no_hints = widen;
-    c->cap_hint = L.cap_in;
-    c->call_bound = L.bound;
+    DecodeReq again = r.req;  // (a copy: the decode replaces the result)
+    again.full = true;
+    again.worst_case = widen;
     c->tsum_dirty = true;  // (the optimistic pass skipped the tile sums; clear every scan word)
-    const int rc = decode_device_any(c, L.d_bytes, L.nbytes, c->last_off, L.n, L.flags, L.st);
-    c->no_quiet = false;
-    c->no_hints = false;
-    if (rc) return rc;
+    if (const int rc = decode_device_any(c, again)) return rc;
     widened |= widen;
     ++c->hint_reruns;
   }
-  c->opt_pending = false;
-  c->hinted = false;  // (confirmed: the capacities held, or the worst-case re-run replaced it)
+  c->res.opt_pending = false;
+  c->res.hinted = false;  // (confirmed: the capacities held, or the worst-case re-run replaced it)
   return 0;
 }
 
@@ -1056,7 +1052,7 @@ static int overflow_status(const uint32_t* h) {
 // An optimistic decode, or one whose value capacities were hinted below the worst case, is confirmed
 // (or re-run in full / at the worst case) before anything reads its columns on the device.
 static int confirm_pending(tfrg_ctx* c) {
-  if (!c->opt_pending && !c->hinted) return 0;
+  if (!c->res.opt_pending && !c->res.hinted) return 0;
   HIP_TRY(hipSetDevice(c->device));
   uint32_t h[kInfoCount];
   uint64_t kt[4];
@@ -1065,19 +1061,19 @@ static int confirm_pending(tfrg_ctx* c) {
 }
 
 int tfrg_result_info(tfrg_ctx* c, tfrg_info* info) {
-  if (!c || !c->have_result) return TFRG_E_ARG;
+  if (!c || !c->res.valid) return TFRG_E_ARG;
   HIP_TRY(hipSetDevice(c->device));
   uint32_t h[kInfoCount] = {0};
   uint64_t kt[4] = {0, 0, 0, 0};
-  const int rc = finish_decode(c, h, kt);
-  if (rc) return rc;
+  if (const int rc = finish_decode(c, h, kt)) return rc;
+  const Result& r = c->res;
   uint64_t blen = 0;
-  if (c->materialized && !h[kInfoOverflow]) {  // the byte column's length: offsets[nb]
-    const uint64_t nb = c->n ? kt[TFRG_KIND_BYTES] : 0;
+  if (r.materialized && !h[kInfoOverflow]) {  // the byte column's length: offsets[nb]
+    const uint64_t nb = r.req.n ? kt[TFRG_KIND_BYTES] : 0;
     HIP_TRY(hipMemcpy(&blen, c->boff64.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost));
   }
   memset(info, 0, sizeof(*info));
-  info->n_records = c->n;
+  info->n_records = r.req.n;
   info->n_slots = c->n_slots;
   info->n_errors = h[kInfoErrors];
   info->first_error = ~h[kInfoFirstError];  // (stored inverted by atomicMax; 0 = no error -> 0xffffffff)
@@ -1086,12 +1082,12 @@ int tfrg_result_info(tfrg_ctx* c, tfrg_info* info) {
   info->n_big = h[kInfoBigRecs];
   info->scan_timeout = h[kInfoScanTimeout];
   for (int k = 0; k < 4; ++k) info->kind_totals[k] = kt[k];
-  info->nbytes = c->nbytes;
+  info->nbytes = r.req.nbytes;
   info->bytes_data_len = blen;
   info->tpl_groups_missed = h[kInfoResid];
   info->placed_slots = ((uint64_t)h[kInfoPlacedHi] << 32) | h[kInfoPlacedLo];
-  info->implicit_cols = c->last_implicit;
-  info->implicit_off_slots = c->last_off_mask;
+  info->implicit_cols = r.implicit;
+  info->implicit_off_slots = r.off_mask;
   return overflow_status(h);
 }
 
@@ -1101,80 +1097,93 @@ int tfrg_ctx_rel_off(const tfrg_ctx* c, uint32_t slot, int32_t* delta) {
   return 0;
 }
 
-// (TFRG_IMPLICIT_BYTES_LEN) per bytes slot of an optimistic decode: its first row in the bytes
-// columns and its constant length. Every slot is placed, so slot k's rows are n * (its rank among
-// the bytes slots), as tpl_quiet_finish sets the column bases.
-static std::vector<std::pair<uint64_t, uint32_t>> implicit_len_runs(const tfrg_ctx* c) {
-  std::vector<std::pair<uint64_t, uint32_t>> out;
-  uint64_t base = 0;
-  for (uint32_t k = 0; k < c->n_slots; ++k) {
-    if ((c->slot_kind_h[k] & 3u) != TFRG_KIND_BYTES) continue;
-    out.push_back({base, k < c->const_len.size() ? c->const_len[k] : 0u});
-    base += c->n;
-  }
+// The bytes slots of an optimistic decode with their first row in the bytes columns. Every slot is
+// placed, so slot k's rows are n * (its rank among the bytes slots), as tpl_quiet_finish sets the
+// column bases.
+static std::vector<std::pair<uint32_t, uint64_t>> bytes_slot_rows(const tfrg_ctx* c) {
+  std::vector<std::pair<uint32_t, uint64_t>> out;
+  for (uint32_t k = 0; k < c->n_slots; ++k)
+    if ((c->slot_kind_h[k] & 3u) == TFRG_KIND_BYTES) out.push_back({k, out.size() * (uint64_t)c->res.req.n});
   return out;
 }
 
-// (tfrg_info.implicit_off_slots) the same rule for the bytes_off words: per masked slot its first row
-// in the bytes columns and its end-relative offset (element r is end32[r] + that)
-static std::vector<std::pair<uint64_t, uint32_t>> implicit_off_runs(const tfrg_ctx* c) {
-  std::vector<std::pair<uint64_t, uint32_t>> out;
-  uint64_t base = 0;
-  for (uint32_t k = 0; k < c->n_slots; ++k) {
-    if ((c->slot_kind_h[k] & 3u) != TFRG_KIND_BYTES) continue;
-    if (k < 64u && ((c->last_off_mask >> k) & 1ull)) out.push_back({base, (uint32_t)c->last_rel_off[k]});
-    base += c->n;
+// (TFRG_IMPLICIT_BYTES_LEN) a bytes slot's constant element length, as the decode ran with it
+static uint32_t implicit_len(const Result& r, uint32_t slot) { return slot < kLeanMaxSlots ? r.slot[slot].elem_len : 0u; }
+
+// The constant columns of the last decode (tfrg_info.implicit_cols, and the aux words of an optimistic
+// decode with stored statuses): rows [first, first + rows) of `col` hold `value` in elements of `width`
+// bytes. tfrg_result_device writes them into the device columns, tfrg_result_fetch into the caller's.
+enum Col { kColStatus, kColAux, kColVerdict, kColOrder, kColBytesLen, kNumCols };
+struct Fill {
+  Col col;
+  uint64_t first, rows;
+  uint32_t value, width;
+};
+static std::vector<Fill> constant_fills(const tfrg_ctx* c) {
+  const Result& r = c->res;
+  const uint64_t n = r.req.n;
+  std::vector<Fill> out;
+  if (r.implicit & TFRG_IMPLICIT_STATUS) {
+    out.push_back({kColStatus, 0, n, 0u, 4});
+    out.push_back({kColVerdict, 0, n, TFRG_V_LEN_MATCH | TFRG_V_LEN_CRC | TFRG_V_DATA_CRC, 1});
   }
+  if ((r.implicit & TFRG_IMPLICIT_STATUS) || r.aux_zero) out.push_back({kColAux, 0, n, 0u, 8});
+  if (r.implicit & TFRG_IMPLICIT_ORDER)
+    for (uint32_t k = 0; k < c->n_slots && k < kLeanMaxSlots; ++k) out.push_back({kColOrder, k * n, n, r.slot[k].order_word, 2});
+  if (r.implicit & TFRG_IMPLICIT_BYTES_LEN)
+    for (const auto& [slot, base] : bytes_slot_rows(c)) out.push_back({kColBytesLen, base, n, implicit_len(r, slot), 4});
   return out;
 }
 
-// The implicit bytes_off words written into the device column, once per decode, on the decode's
+// The implicit bytes_off words (tfrg_info.implicit_off_slots: element r of a masked slot is end32[r] +
+// the slot's end-relative offset) written into the device column, once per decode, on the decode's
 // stream, from the decode's u32 ends (the caller keeps them in place while the result is read:
 // tfrg.h). The one place that formula is evaluated outside the consumers' kernels: tfrg_result_device
 // hands out the column, tfrg_result_fetch copies it. Only after the decode is confirmed.
 static int fill_implicit_off(tfrg_ctx* c) {
-  if (!c->last_off_mask || c->off_complete || !c->n) return 0;
+  Result& r = c->res;
+  if (!r.off_mask || r.off_complete || !r.req.n) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  for (const auto& [base, delta] : implicit_off_runs(c)) {
-    if (base >= c->cap_b) continue;  // (an overflowed result is an error: tfrg_result_info)
-    const uint32_t rows = (uint32_t)std::min<uint64_t>(c->n, c->cap_b - base);
-    HIP_TRY(launch_fill_rel_off(c->b_off.as<uint32_t>() + base, c->last_off.e32, delta, rows, c->last_stream));
+  for (const auto& [slot, base] : bytes_slot_rows(c)) {
+    if (slot >= kLeanMaxSlots || !((r.off_mask >> slot) & 1ull)) continue;
+    if (base >= r.cap_b) continue;  // (an overflowed result is an error: tfrg_result_info)
+    const uint32_t rows = (uint32_t)std::min<uint64_t>(r.req.n, r.cap_b - base);
+    HIP_TRY(launch_fill_rel_off(c->b_off.as<uint32_t>() + base, r.req.off.e32, (uint32_t)r.slot[slot].rel_off, rows,
+                                c->last_stream));
   }
-  c->off_complete = true;
+  r.off_complete = true;
   return 0;
 }
 
 int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
-  if (!c || !c->have_result) return TFRG_E_ARG;
+  if (!c || !c->res.valid) return TFRG_E_ARG;
   if (const int rc = confirm_pending(c)) return rc;  // (before the view, as tfrg_result_info does)
-  if (!c->rs_complete && c->n_slots && c->n) {
+  Result& r = c->res;
+  if (!r.rs_complete && c->n_slots && r.req.n) {
     // a self-consistent view: the identity rows of the finally placed slots, which the decode does
     // not store, are written by one small kernel on the decode's stream (placed mask read on the
     // device), once per decode
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_fill_placed_rows(c->rs.as<uint32_t>(), c->info.as<uint32_t>() + c->info_slot * kInfoCount,
-                                    c->n_slots, c->n, c->last_stream));
+                                    c->n_slots, r.req.n, c->last_stream));
   }
-  c->rs_complete = true;
-  if ((c->last_implicit || c->last_aux_zero) && !c->cols_complete) {  // the constant columns of an optimistic decode
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = c->n;
-    if (c->last_aux_zero) HIP_TRY(hipMemsetAsync(c->aux.p, 0, n * 8, c->last_stream));
-    if (c->last_implicit & TFRG_IMPLICIT_STATUS) {
-      HIP_TRY(hipMemsetAsync(c->status.p, 0, n * 4, c->last_stream));
-      HIP_TRY(hipMemsetAsync(c->aux.p, 0, n * 8, c->last_stream));
-      HIP_TRY(hipMemsetAsync(c->verdict.p, (int)(TFRG_V_LEN_MATCH | TFRG_V_LEN_CRC | TFRG_V_DATA_CRC), n, c->last_stream));
+  r.rs_complete = true;
+  if (!r.cols_complete) {  // the constant columns of an optimistic decode, once per decode
+    DBuf* const col[kNumCols] = {&c->status, &c->aux, &c->verdict, &c->order, &c->b_len};
+    const std::vector<Fill> fills = constant_fills(c);
+    if (!fills.empty()) HIP_TRY(hipSetDevice(c->device));
+    for (const Fill& f : fills) {
+      const hipDeviceptr_t p = col[f.col]->as<uint8_t>() + f.first * f.width;
+      if (f.width == 2) {
+        HIP_TRY(hipMemsetD16Async(p, (unsigned short)f.value, f.rows, c->last_stream));
+      } else if (f.width == 4) {
+        HIP_TRY(hipMemsetD32Async(p, (int)f.value, f.rows, c->last_stream));
+      } else {  // (bytes, or the 8-byte aux words, which are 0)
+        HIP_TRY(hipMemsetAsync(p, (int)f.value, f.rows * f.width, c->last_stream));
+      }
     }
-    if (c->last_implicit & TFRG_IMPLICIT_ORDER)
-      for (uint32_t k = 0; k < c->n_slots; ++k)
-        HIP_TRY(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(c->order.as<uint16_t>() + (size_t)k * n),
-                                  (unsigned short)(c->tpl_h[kLtSlot + 3 * k] >> 16), n, c->last_stream));
-    if (c->last_implicit & TFRG_IMPLICIT_BYTES_LEN)
-      for (const auto& [base, len] : implicit_len_runs(c))
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->b_len.as<uint32_t>() + base), (int)len, n,
-                                  c->last_stream));
   }
-  c->cols_complete = true;
+  r.cols_complete = true;
   if (const int rc = fill_implicit_off(c)) return rc;
   d->status = c->status.as<int32_t>();
   d->aux = c->aux.as<int64_t>();
@@ -1187,8 +1196,8 @@ int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
   d->bytes_off = c->b_off.as<uint32_t>();
   d->bytes_len = c->b_len.as<uint32_t>();
   d->miss = c->miss.as<uint32_t>();
-  d->bytes_data = c->materialized ? c->bdata.as<uint8_t>() : nullptr;
-  d->bytes_offsets = c->materialized ? c->boff64.as<uint64_t>() : nullptr;
+  d->bytes_data = r.materialized ? c->bdata.as<uint8_t>() : nullptr;
+  d->bytes_offsets = r.materialized ? c->boff64.as<uint64_t>() : nullptr;
   return 0;
 }
 
@@ -1198,7 +1207,7 @@ extern "C++" {
 template <class Bad>
 static int check_result(const tfrg_ctx* c, const Bad& bad) {
   if (!c) return bad("no context");
-  if (!c->have_result) return bad("no result (decode first)");
+  if (!c->res.valid) return bad("no result (decode first)");
   return 0;
 }
 template <class Bad>
@@ -1248,19 +1257,20 @@ static void fill_columns(const tfrg_ctx* c, Args& a) {
   a.i64 = view_col<int64_t>(c, c->i64);
   a.f32 = view_col<uint32_t>(c, c->f32);
   a.b_len = view_col<uint32_t>(c, c->b_len);
-  if (c->materialized) a.b_off64 = view_col<uint64_t>(c, c->boff64);
+  if (c->res.materialized) a.b_off64 = view_col<uint64_t>(c, c->boff64);
   a.info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
-  a.n = c->n;
+  a.n = c->res.req.n;
 }
 // The bytes' source: the views' input buffer, readable to round_up(nbytes, 16), or the byte column
 template <class Args>
 static void fill_bytes_source(const tfrg_ctx* c, Args& a) {
   a.b_off = view_col<uint32_t>(c, c->b_off);
-  a.in = c->materialized ? c->bdata.as<uint8_t>() : c->last.d_bytes;
-  const uint64_t bound = c->materialized ? (uint64_t)c->bdata.cap & ~15ull : (c->last.nbytes + 15ull) & ~15ull;
+  const Result& r = c->res;
+  a.in = r.materialized ? c->bdata.as<uint8_t>() : r.req.d_bytes;
+  const uint64_t bound = r.materialized ? (uint64_t)c->bdata.cap & ~15ull : (r.req.nbytes + 15ull) & ~15ull;
   a.in_bound = a.in ? (uint32_t)std::min<uint64_t>(bound, 0xfffffff0ull) : 0;
   // (the decode's u32 ends, for the specs with a const_off: read for such a spec only)
-  a.end32 = c->last_off_mask ? c->last_off.e32 : nullptr;
+  a.end32 = r.off_mask ? r.req.off.e32 : nullptr;
 }
 }  // extern "C++"
 
@@ -1269,17 +1279,17 @@ static void fill_bytes_source(const tfrg_ctx* c, Args& a) {
 // column is stored" sentinel.
 static_assert(kDenseOffStored == kRaggedOffStored, "one const_off lookup serves both");
 static int32_t const_off_of(const tfrg_ctx* c, uint32_t slot, bool reads_off) {
-  if (!reads_off || slot >= 64u || !((c->last_off_mask >> slot) & 1ull)) return kDenseOffStored;
-  return c->last_rel_off[slot];
+  if (!reads_off || slot >= kLeanMaxSlots || !((c->res.off_mask >> slot) & 1ull)) return kDenseOffStored;
+  return c->res.slot[slot].rel_off;
 }
 
 // A bytes slot's constant element length where the last decode did not store the bytes_len column (as
-// implicit_len_runs: the shapes' length holds); else, or for a spec / term that reads no length, the
+// constant_fills: the shapes' length holds); else, or for a spec / term that reads no length, the
 // kernels' "the column is stored" sentinel.
 static_assert(kDenseNoLen == kRaggedNoLen && kRaggedNoLen == kSelNoLen, "one const_len lookup serves all three");
 static uint32_t const_len_of(const tfrg_ctx* c, uint32_t slot, bool reads_len) {
-  if (!reads_len || !(c->last_implicit & TFRG_IMPLICIT_BYTES_LEN)) return kDenseNoLen;
-  return slot < c->const_len.size() ? c->const_len[slot] : 0u;
+  if (!reads_len || !(c->res.implicit & TFRG_IMPLICIT_BYTES_LEN)) return kDenseNoLen;
+  return implicit_len(c->res, slot);
 }
 
 // The consumer-stream fence: the work an entry point puts on the decode's stream *st starts after what
@@ -1334,11 +1344,11 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
     if (const int rc = check_rows_dtype(rows.d_rows, rows.dtype, true, bad)) return rc;
     if (const int rc = check_rows_m(rows.d_rows, rows.m, true, bad)) return rc;
   }
-  if (!by_rows && c->n == 0) return 0;
+  if (!by_rows && c->res.req.n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   if (const int rc = confirm_pending(c)) return rc;
   // the rows of every output
-  const uint32_t out_rows = by_rows ? rows.m : c->n;
+  const uint32_t out_rows = by_rows ? rows.m : c->res.req.n;
   DenseArgs a{};
   if (by_rows) {
     a.rows = rows.d_rows;
@@ -1351,7 +1361,7 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
   fill_bytes_source(c, a);
   a.stats = d_stats;
   a.n_specs = n_specs;
-  a.nt = (uint32_t)c->dense_nt;
+  a.nt = (uint32_t)c->sw.dense_nt;
   // workgroups per spec: one per chunk of its output, within an even share of 16 per CU
   const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 16u / n_specs);
   uint32_t blocks = 0;
@@ -1377,12 +1387,12 @@ static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_de
   hipStream_t st, cs;
   if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
   // (counters that lie back to back, stats first, are zeroed by one memset: one launch less per step)
-  const bool one_memset = by_rows && c->n && d_stats && rows.d_skipped == d_stats + 4 * (size_t)n_specs;
+  const bool one_memset = by_rows && c->res.req.n && d_stats && rows.d_skipped == d_stats + 4 * (size_t)n_specs;
   if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * (one_memset ? 20 : 16), st));
   // (a row list over an empty result: no record to read, every row is skipped)
   if (by_rows && rows.d_skipped && !one_memset)
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rows.d_skipped), c->n ? 0 : (int)rows.m, n_specs, st));
-  if (out_rows && c->n) HIP_TRY(launch_dense(a, blocks, st));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rows.d_skipped), c->res.req.n ? 0 : (int)rows.m, n_specs, st));
+  if (out_rows && c->res.req.n) HIP_TRY(launch_dense(a, blocks, st));
   return fence_close(c, st, cs);
 }
 
@@ -1439,7 +1449,7 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
   if (tiles * n_specs * split > 0x7fffffffull) return bad("too many tiles for one launch: raise the ragged tile");
   HIP_TRY(hipSetDevice(c->device));
   if (const int rc = confirm_pending(c)) return rc;
-  const bool run = m && c->n;
+  const bool run = m && c->res.req.n;
   if (run) HIP_TRY(c->rg_tsum.ensure((size_t)(tiles * n_specs) * 8));
   hipStream_t st, cs;
   if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
@@ -1525,8 +1535,8 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
   if (!d_count) return bad("d_count is NULL");
   if (((uintptr_t)d_count & 7u) || ((uintptr_t)d_out & (out_dtype == TFRG_ROWS_I64 ? 7u : 3u)))
     return bad("d_out and d_count must be aligned to their element size");
-  if (out_dtype == TFRG_ROWS_I32 && c->n &&
-      (row0 < (int64_t)INT32_MIN || row0 > (int64_t)INT32_MAX - ((int64_t)c->n - 1)))
+  if (out_dtype == TFRG_ROWS_I32 && c->res.req.n &&
+      (row0 < (int64_t)INT32_MIN || row0 > (int64_t)INT32_MAX - ((int64_t)c->res.req.n - 1)))
     return bad("rows [row0, row0 + n) do not fit an int32 output");
   if (flags & ~TFRG_SEL_APPEND) return bad("unknown flag bits");
   const bool append = (flags & TFRG_SEL_APPEND) != 0;
@@ -1534,7 +1544,7 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
   if (const int rc = confirm_pending(c)) return rc;
   const uint32_t tile = c->select_tile;
   const uint64_t tiles = ((uint64_t)m + tile - 1) / tile, nwords = ((uint64_t)m + 63) / 64;
-  const bool run = m && c->n;
+  const bool run = m && c->res.req.n;
   if (run) HIP_TRY(c->sel_buf.ensure((size_t)(nwords + tiles) * 8));
   hipStream_t st, cs;
   if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
@@ -1542,7 +1552,7 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
   if (run) {
     SelectArgs a{};
     fill_columns(c, a);
-    a.status = (c->last_implicit & TFRG_IMPLICIT_STATUS) ? nullptr : c->status.as<int32_t>();
+    a.status = (c->res.implicit & TFRG_IMPLICIT_STATUS) ? nullptr : c->status.as<int32_t>();
     a.stats = d_stats;
     a.count = d_count;
     a.words = c->sel_buf.as<uint64_t>();
@@ -1590,30 +1600,32 @@ int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {
   int rc = tfrg_result_info(c, &info);
   if (rc) return rc;
   const hipStream_t st = c->last_stream;
-  const size_t n = c->n, S = c->n_slots;
+  const Result& r = c->res;
+  const size_t n = r.req.n, S = c->n_slots;
   auto cp = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
     if (!dst || !bytes) return hipSuccess;
     return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
   };
-  // (an optimistic decode's constant columns are written here, not copied: tfrg_info.implicit_cols)
-  if (info.implicit_cols & TFRG_IMPLICIT_STATUS) {
-    if (h->status) memset(h->status, 0, n * 4);
-    if (h->aux) memset(h->aux, 0, n * 8);
-    if (h->verdict) memset(h->verdict, TFRG_V_LEN_MATCH | TFRG_V_LEN_CRC | TFRG_V_DATA_CRC, n);
-  } else {
-    HIP_TRY(cp(h->status, c->status.p, n * 4));
-    if (c->last_aux_zero) {
-      if (h->aux) memset(h->aux, 0, n * 8);
-    } else {
-      HIP_TRY(cp(h->aux, c->aux.p, n * 8));
+  // (clamped to the capacities: a result that overflowed them fails in tfrg_result_info above)
+  auto cl = [](uint64_t v, uint64_t cap) { return v < cap ? v : cap; };
+  const uint64_t nb = cl(info.kind_totals[TFRG_KIND_BYTES], r.cap_b);
+  // an optimistic decode's constant columns are written here, the others copied
+  void* const col[kNumCols] = {h->status, h->aux, h->verdict, h->order, h->bytes_len};
+  const void* const dcol[kNumCols] = {c->status.p, c->aux.p, c->verdict.p, c->order.p, c->b_len.p};
+  size_t col_bytes[kNumCols] = {n * 4, n * 8, n, S * n * 2, nb * 4};
+  for (const Fill& f : constant_fills(c)) {
+    col_bytes[f.col] = 0;
+    if (!col[f.col]) continue;
+    uint8_t* const p = static_cast<uint8_t*>(col[f.col]) + f.first * f.width;
+    if (f.width == 2) {
+      std::fill_n(reinterpret_cast<uint16_t*>(p), f.rows, (uint16_t)f.value);
+    } else if (f.width == 4) {
+      std::fill_n(reinterpret_cast<uint32_t*>(p), f.rows, f.value);
+    } else {  // (bytes, or the 8-byte aux words, which are 0)
+      memset(p, (int)f.value, f.rows * f.width);
     }
-    HIP_TRY(cp(h->verdict, c->verdict.p, n));
   }
-  if ((info.implicit_cols & TFRG_IMPLICIT_ORDER) && h->order) {
-    for (size_t k = 0; k < S; ++k) std::fill_n(h->order + k * n, n, (uint16_t)(c->tpl_h[kLtSlot + 3 * k] >> 16));
-  } else {
-    HIP_TRY(cp(h->order, c->order.p, S * n * 2));
-  }
+  for (int k = 0; k < kNumCols; ++k) HIP_TRY(cp(col[k], dcol[k], col_bytes[k]));
   // row splits: a placed slot's are the identity, never stored by the decode; they copy from a
   // device identity row (filled once per size), as fast as the stored rows and as asynchronous
   if (h->row_splits) {
@@ -1633,20 +1645,13 @@ int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {
     }
   }
   HIP_TRY(cp(h->slot_base, c->slot_base.p, S * 8));
-  // (clamped to the capacities: a result that overflowed them fails in tfrg_result_info above)
-  auto cl = [](uint64_t v, uint64_t cap) { return v < cap ? v : cap; };
-  HIP_TRY(cp(h->i64, c->i64.p, cl(info.kind_totals[TFRG_KIND_INT64], c->cap_i64) * 8));
-  HIP_TRY(cp(h->f32, c->f32.p, cl(info.kind_totals[TFRG_KIND_FLOAT], c->cap_f32) * 4));
+  HIP_TRY(cp(h->i64, c->i64.p, cl(info.kind_totals[TFRG_KIND_INT64], r.cap_i64) * 8));
+  HIP_TRY(cp(h->f32, c->f32.p, cl(info.kind_totals[TFRG_KIND_FLOAT], r.cap_f32) * 4));
   // (implicit offset words: written into the device column first, by the device view's fill)
   if (h->bytes_off)
     if (const int rc2 = fill_implicit_off(c)) return rc2;
-  HIP_TRY(cp(h->bytes_off, c->b_off.p, cl(info.kind_totals[TFRG_KIND_BYTES], c->cap_b) * 4));
-  if ((info.implicit_cols & TFRG_IMPLICIT_BYTES_LEN) && h->bytes_len) {
-    for (const auto& [base, len] : implicit_len_runs(c)) std::fill_n(h->bytes_len + base, n, len);
-  } else {
-    HIP_TRY(cp(h->bytes_len, c->b_len.p, cl(info.kind_totals[TFRG_KIND_BYTES], c->cap_b) * 4));
-  }
-  if (c->materialized) {
+  HIP_TRY(cp(h->bytes_off, c->b_off.p, nb * 4));
+  if (r.materialized) {
     HIP_TRY(cp(h->bytes_data, c->bdata.p, info.bytes_data_len));
     HIP_TRY(cp(h->bytes_offsets, c->boff64.p, (info.kind_totals[TFRG_KIND_BYTES] + 1) * 8));
   }
