@@ -543,6 +543,75 @@ int tfrg_result_select_rows(tfrg_ctx* ctx, const tfrg_select_term* terms, uint32
  * default (1024). A tuning/testing knob, as tfrg_ctx_set_ragged_tile. */
 int tfrg_ctx_set_select_tile(tfrg_ctx* ctx, uint32_t rows);
 
+/* Filtered row lists with predicates on bytes features: `name = 'cat'`, `path LIKE 'train/%'`,
+ * `name ~ 'rose'`, `id IN (...)` (the two queries of the reference's README.md filter on a string
+ * feature). tfrg_result_select_match is tfrg_result_select_rows -- every parameter after patterns_len is
+ * that call's, with the same meaning -- plus two subjects, three ops and the byte-string operands they
+ * take. Candidates, skipped candidates, groups, output, d_count, d_stats, TFRG_SEL_APPEND, stream order,
+ * the single confirmation of an optimistic or hinted decode, determinism (two equal calls write equal
+ * bytes) and the m == 0 / n == 0 cases are exactly as documented there; the subjects and ops of
+ * tfrg_result_select_rows work unchanged through this call and may be mixed with the new ones in one
+ * term table. tfrg_result_select_rows itself still refuses the new subjects and ops.
+ * Patterns: `patterns` is HOST memory, patterns_len <= TFRG_SEL_MAX_PATTERN_BYTES bytes holding the
+ * operands back to back. It is consumed before the call returns (the caller may free or overwrite it at
+ * once): the bytes travel to the kernel inside its launch argument, beside the term table, with no
+ * device allocation, no copy on a stream and no host synchronisation. A pattern is a range of it of at
+ * most TFRG_SEL_MAX_PATTERN bytes; terms may share a pattern, and patterns may overlap.
+ * New subjects, on bytes_list slots only. For both, operand = pattern offset | (uint64_t)pattern
+ * length << 32, with [offset, offset + length) inside [0, patterns_len):
+ *   TFRG_SEL_BYTES: element `index` of the record's list. False, whatever the op (NE included), if the
+ *     record has <= index elements (TFRG_SEL_VALUE's rule); else element op pattern;
+ *   TFRG_SEL_BYTES_ANY: true iff some element of the record's list satisfies the op (false for an empty
+ *     or absent list); index must be 0.
+ * A failed record (status != 0) has no values: every bytes term is false for it.
+ * Ops: TFRG_SEL_EQ .. TFRG_SEL_GE compare the element with the pattern as Python compares bytes objects:
+ * byte by byte as unsigned values (0x80 > 0x7f), the first difference decides, and a proper prefix is
+ * less than the longer string. TFRG_SEL_PREFIX / TFRG_SEL_SUFFIX / TFRG_SEL_CONTAINS (valid with the two
+ * new subjects only): the element starts with / ends with / contains the pattern as a contiguous
+ * substring. The empty pattern equals the empty element alone, and is a prefix, a suffix and a substring
+ * of every element that is present (the empty one included).
+ * An element's bytes are the ones tfrg_result_dense (TFRG_DENSE_U8) reads for it, from whichever source
+ * the decode left: the (offset, length) views into d_bytes, the materialized byte column
+ * (TFRG_FLAG_MATERIALIZE_BYTES), or for a slot of tfrg_info.implicit_off_slots the view at
+ * d_end32[g] + tfrg_ctx_rel_off, with the constant length of TFRG_IMPLICIT_BYTES_LEN where that bit is
+ * set; the columns an optimistic decode left implicit are neither read nor written. d_bytes and d_end32
+ * must stay in place and unchanged as documented for tfrg_result_dense / tfrg_info.implicit_off_slots.
+ * Nothing at or past round_up(nbytes, 16) of d_bytes (the byte column: its capacity) is touched: a byte
+ * of a view that lies there reads as 0. An element of the last record that ends at nbytes, whatever
+ * nbytes % 16 is, is compared in full.
+ * Cost: EQ .. GE, PREFIX and SUFFIX read at most the pattern's length of an element, whatever its size
+ * (a 512 KiB element compared for equality costs a length test), one lane per candidate. CONTAINS reads
+ * an element until the first match: its lane walks an element of up to tfrg_ctx_set_select_scan bytes;
+ * a longer one is streamed by the whole wave in coalesced 2 KiB chunks through LDS, pattern length - 1
+ * bytes carried from chunk to chunk. A term table without a bytes subject runs the kernels of
+ * tfrg_result_select_rows.
+ * TFRG_E_ARG (text in tfrg_last_error, prefixed "tfrg_result_select_match: "): everything
+ * tfrg_result_select_rows refuses, with subjects up to TFRG_SEL_BYTES_ANY and ops up to
+ * TFRG_SEL_CONTAINS known; a bytes subject on a slot that is not a bytes_list; TFRG_SEL_PREFIX /
+ * _SUFFIX / _CONTAINS with another subject; index != 0 outside TFRG_SEL_VALUE and TFRG_SEL_BYTES; a
+ * pattern longer than TFRG_SEL_MAX_PATTERN; patterns_len > TFRG_SEL_MAX_PATTERN_BYTES; a pattern range
+ * that is not inside [0, patterns_len); patterns NULL with patterns_len > 0. (patterns NULL with
+ * patterns_len 0 is allowed: every pattern is then empty. As in tfrg_result_select_rows nothing is
+ * launched or written when the call fails.) */
+#define TFRG_SEL_MAX_PATTERN 256u
+#define TFRG_SEL_MAX_PATTERN_BYTES 2048u
+/* subjects of tfrg_result_select_match alone */
+#define TFRG_SEL_BYTES 5      /* element `index` of the record's list (bytes_list slot) against a pattern */
+#define TFRG_SEL_BYTES_ANY 6  /* any element of the record's list (bytes_list slot) against a pattern */
+/* ops of tfrg_result_select_match alone, with the two subjects above */
+#define TFRG_SEL_PREFIX 6
+#define TFRG_SEL_SUFFIX 7
+#define TFRG_SEL_CONTAINS 8
+int tfrg_result_select_match(tfrg_ctx* ctx, const tfrg_select_term* terms, uint32_t n_terms,
+                             const uint8_t* patterns, uint64_t patterns_len,
+                             const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
+                             void* d_out, uint32_t out_dtype, uint64_t cap, uint64_t* d_count,
+                             uint32_t* d_stats, uint32_t flags, void* consumer_stream);
+/* TFRG_SEL_CONTAINS: elements longer than `bytes` are scanned by their whole wave, shorter ones by the
+ * candidate's lane: 4 to 65536, 0 = the default (256). The result does not depend on it. A
+ * tuning/testing knob: with 4, elements of a few bytes exercise the wave scan. */
+int tfrg_ctx_set_select_scan(tfrg_ctx* ctx, uint32_t bytes);
+
 /* ---------------------------------------------------------------------------------------------
  * Double-buffered host -> HBM decode stream (replaces reader.py:212-247's per-record ThreadPool
  * read+decode for whole-dataset reads). Two slots, each with a pinned staging buffer of batch_bytes,

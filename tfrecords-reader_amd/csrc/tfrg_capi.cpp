@@ -218,6 +218,7 @@ struct tfrg_ctx : Arena {
   uint32_t index_chunk = kIndexChunkDefault;  // tfrg_ctx_set_index_chunk
   uint32_t ragged_tile = kRaggedTileDefault;  // tfrg_ctx_set_ragged_tile: rows per tile
   uint32_t select_tile = kSelTileDefault;     // tfrg_ctx_set_select_tile: candidates per tile
+  uint32_t select_scan = kSelScanDefault;     // tfrg_ctx_set_select_scan: CONTAINS elements above it go by wave
   void* fr_pin = nullptr;  // tfrg_index_device: pinned host staging
   size_t fr_pin_cap = 0;
 };
@@ -390,6 +391,16 @@ int tfrg_ctx_set_select_tile(tfrg_ctx* c, uint32_t rows) {
     return TFRG_E_ARG;
   }
   c->select_tile = rows ? rows : kSelTileDefault;
+  return 0;
+}
+
+int tfrg_ctx_set_select_scan(tfrg_ctx* c, uint32_t bytes) {
+  if (!c) return TFRG_E_ARG;
+  if (bytes && (bytes < kSelScanMin || bytes > kSelScanMax)) {
+    set_error("select scan must be from 4 to 65536 bytes (0: the default)");
+    return TFRG_E_ARG;
+  }
+  c->select_scan = bytes ? bytes : kSelScanDefault;
   return 0;
 }
 
@@ -1495,51 +1506,88 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
 }
 
 // The WHERE clause over the last result (tfrg_select.h: verdicts, tile scan, write). Every grid size
-// comes from m and the tile: nothing is read back from the device.
-int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t n_terms, const void* d_rows,
-                            uint32_t rows_dtype, uint32_t m, int64_t row0, void* d_out, uint32_t out_dtype,
-                            uint64_t cap, uint64_t* d_count, uint32_t* d_stats, uint32_t flags, void* consumer_stream) {
-  auto bad = [](const std::string& why) {
-    set_error("tfrg_result_select_rows: " + why);
+// comes from m and the tile: nothing is read back from the device. One implementation behind both entry
+// points: tfrg_result_select_rows is tfrg_result_select_match without patterns (`match` false: the
+// bytes subjects and the ops past GE are unknown to it).
+struct SelectCall {
+  const void* d_rows;
+  uint32_t rows_dtype, m;
+  int64_t row0;
+  void* d_out;
+  uint32_t out_dtype;
+  uint64_t cap;
+  uint64_t* d_count;
+  uint32_t* d_stats;
+  uint32_t flags;
+  void* consumer_stream;
+};
+
+static bool sel_bytes_subject(uint32_t subject) { return subject == TFRG_SEL_BYTES || subject == TFRG_SEL_BYTES_ANY; }
+
+static int result_select(const char* fn, bool match, tfrg_ctx* c, const tfrg_select_term* terms, uint32_t n_terms,
+                         const uint8_t* patterns, uint64_t patterns_len, const SelectCall& q) {
+  auto bad = [fn](const std::string& why) {
+    set_error(std::string(fn) + ": " + why);
     return TFRG_E_ARG;
   };
   if (const int rc = check_result(c, bad)) return rc;
   static_assert(TFRG_SEL_MAX_TERMS == kSelMaxTerms && TFRG_SEL_VALUE == kSelValue && TFRG_SEL_ANY == kSelAny &&
                     TFRG_SEL_COUNT == kSelCount && TFRG_SEL_BYTES_LEN == kSelBytesLen &&
-                    TFRG_SEL_STATUS == kSelStatus && TFRG_SEL_EQ == kSelEq && TFRG_SEL_GE == kSelGe &&
+                    TFRG_SEL_STATUS == kSelStatus && TFRG_SEL_BYTES == kSelBytes && TFRG_SEL_BYTES_ANY == kSelBytesAny &&
+                    TFRG_SEL_EQ == kSelEq && TFRG_SEL_GE == kSelGe && TFRG_SEL_PREFIX == kSelPrefix &&
+                    TFRG_SEL_SUFFIX == kSelSuffix && TFRG_SEL_CONTAINS == kSelContains &&
+                    TFRG_SEL_MAX_PATTERN == kSelMaxPattern && TFRG_SEL_MAX_PATTERN_BYTES == kSelMaxPatternBytes &&
                     sizeof(tfrg_select_term) == 32,
                 "tfrg.h mirrors tfrg_select.h");
+  const uint32_t max_subject = match ? TFRG_SEL_BYTES_ANY : TFRG_SEL_STATUS, max_op = match ? TFRG_SEL_CONTAINS : TFRG_SEL_GE;
   if (n_terms > TFRG_SEL_MAX_TERMS) return bad("n_terms must be at most " + std::to_string(TFRG_SEL_MAX_TERMS));
   if (n_terms && !terms) return bad("terms is NULL");
+  if (patterns_len > TFRG_SEL_MAX_PATTERN_BYTES)
+    return bad("patterns_len must be at most " + std::to_string(TFRG_SEL_MAX_PATTERN_BYTES));
+  if (patterns_len && !patterns) return bad("patterns is NULL");
+  bool any_bytes = false;
   for (uint32_t i = 0; i < n_terms; ++i) {
     const tfrg_select_term& t = terms[i];
     const std::string at = "term " + std::to_string(i) + ": ";
     if (t.slot >= c->n_slots) return bad(at + "slot " + std::to_string(t.slot) + " >= n_slots");
-    if (t.subject > TFRG_SEL_STATUS) return bad(at + "unknown subject " + std::to_string(t.subject));
-    if (t.op > TFRG_SEL_GE) return bad(at + "unknown op " + std::to_string(t.op));
+    if (t.subject > max_subject) return bad(at + "unknown subject " + std::to_string(t.subject));
+    if (t.op > max_op) return bad(at + "unknown op " + std::to_string(t.op));
     if (t.group >= 32) return bad(at + "group must be below 32");
     const uint32_t kind = c->slot_kind_h[t.slot] & 3u;
     const bool list = t.subject == TFRG_SEL_VALUE || t.subject == TFRG_SEL_ANY;
+    const bool bytes = sel_bytes_subject(t.subject);
     if ((list && kind != TFRG_KIND_INT64 && kind != TFRG_KIND_FLOAT) ||
-        (t.subject == TFRG_SEL_BYTES_LEN && kind != TFRG_KIND_BYTES) || (t.subject == TFRG_SEL_STATUS && t.slot != 0))
+        ((t.subject == TFRG_SEL_BYTES_LEN || bytes) && kind != TFRG_KIND_BYTES) ||
+        (t.subject == TFRG_SEL_STATUS && t.slot != 0))
       return bad(at + "subject " + std::to_string(t.subject) + " does not fit slot " + std::to_string(t.slot) +
                  " of kind " + std::to_string(kind));
-    if (t.index && t.subject != TFRG_SEL_VALUE) return bad(at + "index must be 0 outside TFRG_SEL_VALUE");
+    if (t.op > TFRG_SEL_GE && !bytes)
+      return bad(at + "op " + std::to_string(t.op) + " needs TFRG_SEL_BYTES or TFRG_SEL_BYTES_ANY");
+    if (t.index && t.subject != TFRG_SEL_VALUE && t.subject != TFRG_SEL_BYTES)
+      return bad(at + (match ? "index must be 0 outside TFRG_SEL_VALUE and TFRG_SEL_BYTES" : "index must be 0 outside TFRG_SEL_VALUE"));
     if (t.reserved) return bad(at + "reserved must be 0");
     if (list && kind == TFRG_KIND_FLOAT && (t.operand >> 32)) return bad(at + "a float operand has its high 32 bits set");
+    if (bytes) {
+      const uint64_t off = t.operand & 0xffffffffull, len = t.operand >> 32;
+      if (len > TFRG_SEL_MAX_PATTERN) return bad(at + "a pattern is at most " + std::to_string(TFRG_SEL_MAX_PATTERN) + " bytes long");
+      if (off + len > patterns_len) return bad(at + "the pattern lies outside patterns");
+      any_bytes = true;
+    }
   }
-  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
-  if (out_dtype != TFRG_ROWS_I32 && out_dtype != TFRG_ROWS_I64)
-    return bad("out_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(out_dtype));
-  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
-  if (!d_count) return bad("d_count is NULL");
-  if (((uintptr_t)d_count & 7u) || ((uintptr_t)d_out & (out_dtype == TFRG_ROWS_I64 ? 7u : 3u)))
+  if (const int rc = check_rows_dtype(q.d_rows, q.rows_dtype, false, bad)) return rc;
+  if (q.out_dtype != TFRG_ROWS_I32 && q.out_dtype != TFRG_ROWS_I64)
+    return bad("out_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(q.out_dtype));
+  if (const int rc = check_rows_m(q.d_rows, q.m, false, bad)) return rc;
+  if (!q.d_count) return bad("d_count is NULL");
+  if (((uintptr_t)q.d_count & 7u) || ((uintptr_t)q.d_out & (q.out_dtype == TFRG_ROWS_I64 ? 7u : 3u)))
     return bad("d_out and d_count must be aligned to their element size");
-  if (out_dtype == TFRG_ROWS_I32 && c->res.req.n &&
-      (row0 < (int64_t)INT32_MIN || row0 > (int64_t)INT32_MAX - ((int64_t)c->res.req.n - 1)))
+  if (q.out_dtype == TFRG_ROWS_I32 && c->res.req.n &&
+      (q.row0 < (int64_t)INT32_MIN || q.row0 > (int64_t)INT32_MAX - ((int64_t)c->res.req.n - 1)))
     return bad("rows [row0, row0 + n) do not fit an int32 output");
-  if (flags & ~TFRG_SEL_APPEND) return bad("unknown flag bits");
-  const bool append = (flags & TFRG_SEL_APPEND) != 0;
+  if (q.flags & ~TFRG_SEL_APPEND) return bad("unknown flag bits");
+  const bool append = (q.flags & TFRG_SEL_APPEND) != 0;
+  const uint32_t m = q.m;
+  uint32_t* const d_stats = q.d_stats;
   HIP_TRY(hipSetDevice(c->device));
   if (const int rc = confirm_pending(c)) return rc;
   const uint32_t tile = c->select_tile;
@@ -1547,23 +1595,25 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
   const bool run = m && c->res.req.n;
   if (run) HIP_TRY(c->sel_buf.ensure((size_t)(nwords + tiles) * 8));
   hipStream_t st, cs;
-  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
+  if (const int rc = fence_open(c, q.consumer_stream, &st, &cs)) return rc;
   if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, 8, st));
   if (run) {
-    SelectArgs a{};
+    // (the bytes fields and the patterns are filled, and travel, only where a bytes term asks for them)
+    SelectBytesArgs ba{};
+    SelectArgs& a = ba.s;
     fill_columns(c, a);
     a.status = (c->res.implicit & TFRG_IMPLICIT_STATUS) ? nullptr : c->status.as<int32_t>();
     a.stats = d_stats;
-    a.count = d_count;
+    a.count = q.d_count;
     a.words = c->sel_buf.as<uint64_t>();
     a.tsum = a.words + nwords;
-    a.rows = d_rows;
-    a.out = d_out;
-    a.cap = d_out ? cap : 0;
-    a.row0 = row0;
+    a.rows = q.d_rows;
+    a.out = q.d_out;
+    a.cap = q.d_out ? q.cap : 0;
+    a.row0 = q.row0;
     a.m = m;
-    a.rows64 = rows_dtype == TFRG_ROWS_I64;
-    a.out64 = out_dtype == TFRG_ROWS_I64;
+    a.rows64 = q.rows_dtype == TFRG_ROWS_I64;
+    a.out64 = q.out_dtype == TFRG_ROWS_I64;
     a.n_terms = n_terms;
     a.tile = tile;
     a.tiles = (uint32_t)tiles;
@@ -1583,16 +1633,41 @@ int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t
         d.rhs_nan = sel_float_nan((uint32_t)t.operand);
         d.rhs = d.rhs_nan ? 0 : sel_float_key((uint32_t)t.operand);
       }
-      d.const_len = const_len_of(c, t.slot, t.subject == TFRG_SEL_BYTES_LEN);
+      const bool bytes = sel_bytes_subject(t.subject);
+      d.const_len = const_len_of(c, t.slot, t.subject == TFRG_SEL_BYTES_LEN || bytes);
+      ba.const_off[i] = const_off_of(c, t.slot, bytes);
       a.all_groups |= 1u << t.group;
     }
-    HIP_TRY(launch_select(a, st));
+    if (any_bytes) {
+      static_assert(kDenseOffStored == kSelOffStored, "const_off_of serves select too");
+      fill_bytes_source(c, ba);
+      ba.scan_min = c->select_scan;
+      if (patterns_len) memcpy(ba.pat, patterns, (size_t)patterns_len);
+      HIP_TRY(launch_select_bytes(ba, st));
+    } else {
+      HIP_TRY(launch_select(a, st));
+    }
   } else {
     // no candidate, or no record (every candidate is skipped): nothing is selected
-    if (!append) HIP_TRY(hipMemsetAsync(d_count, 0, 8, st));
+    if (!append) HIP_TRY(hipMemsetAsync(q.d_count, 0, 8, st));
     if (d_stats && m) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 1), (int)m, 1, st));
   }
   return fence_close(c, st, cs);
+}
+
+int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t n_terms, const void* d_rows,
+                            uint32_t rows_dtype, uint32_t m, int64_t row0, void* d_out, uint32_t out_dtype,
+                            uint64_t cap, uint64_t* d_count, uint32_t* d_stats, uint32_t flags, void* consumer_stream) {
+  return result_select("tfrg_result_select_rows", false, c, terms, n_terms, nullptr, 0,
+                       SelectCall{d_rows, rows_dtype, m, row0, d_out, out_dtype, cap, d_count, d_stats, flags, consumer_stream});
+}
+
+int tfrg_result_select_match(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t n_terms, const uint8_t* patterns,
+                             uint64_t patterns_len, const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
+                             void* d_out, uint32_t out_dtype, uint64_t cap, uint64_t* d_count, uint32_t* d_stats,
+                             uint32_t flags, void* consumer_stream) {
+  return result_select("tfrg_result_select_match", true, c, terms, n_terms, patterns, patterns_len,
+                       SelectCall{d_rows, rows_dtype, m, row0, d_out, out_dtype, cap, d_count, d_stats, flags, consumer_stream});
 }
 
 int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {

@@ -1,6 +1,6 @@
-// tfrg_select.h — arguments of the three kernels of tfrg_select.hip behind tfrg_result_select_rows:
-// predicates over the decoded columns of a list of candidate rows in, the entries of the passing
-// candidates compacted into a device row list out. Shared with tfrg_capi.cpp only.
+// tfrg_select.h — arguments of the three kernels of tfrg_select.hip behind tfrg_result_select_rows and
+// tfrg_result_select_match: predicates over the decoded columns of a list of candidate rows in, the
+// entries of the passing candidates compacted into a device row list out. Shared with tfrg_capi.cpp only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -13,15 +13,24 @@ constexpr uint32_t kSelTileMin = 64, kSelTileMax = 4096, kSelTileDefault = 1024;
 // k_sel_scan's workgroup: it takes that many tile sums per pass and carries across passes
 constexpr uint32_t kSelScanThreads = 1024;
 constexpr uint32_t kSelNoLen = 0xffffffffu;  // SelTerm::const_len: the bytes_len column is stored
+constexpr int32_t kSelOffStored = 0x7fffffff;  // SelectBytesArgs::const_off: the bytes_off column is stored
+// byte-string operands (tfrg.h TFRG_SEL_MAX_PATTERN, TFRG_SEL_MAX_PATTERN_BYTES)
+constexpr uint32_t kSelMaxPattern = 256, kSelMaxPatternBytes = 2048;
+// CONTAINS: elements longer than this many bytes are scanned by their wave (tfrg_ctx_set_select_scan)
+constexpr uint32_t kSelScanMin = 4, kSelScanMax = 65536, kSelScanDefault = 256;
 
-enum SelSubject : uint32_t { kSelValue = 0, kSelAny = 1, kSelCount = 2, kSelBytesLen = 3, kSelStatus = 4 };  // (TFRG_SEL_*)
-enum SelOp : uint32_t { kSelEq = 0, kSelNe = 1, kSelLt = 2, kSelLe = 3, kSelGt = 4, kSelGe = 5 };
+enum SelSubject : uint32_t {  // (TFRG_SEL_*)
+  kSelValue = 0, kSelAny = 1, kSelCount = 2, kSelBytesLen = 3, kSelStatus = 4, kSelBytes = 5, kSelBytesAny = 6
+};
+enum SelOp : uint32_t {
+  kSelEq = 0, kSelNe = 1, kSelLt = 2, kSelLe = 3, kSelGt = 4, kSelGe = 5, kSelPrefix = 6, kSelSuffix = 7, kSelContains = 8
+};
 
 // One term, as the kernel takes it. Every subject ends in one signed 64-bit compare `lhs op rhs`:
 // floats are compared through sel_float_key (an integer key in the order of the values, -0.0 on
 // 0.0), with NaN on either side decided apart (true under NE alone).
 struct SelTerm {
-  int64_t rhs;         // the operand; float slots: its key
+  int64_t rhs;         // the operand; float slots: its key; kSelBytes / kSelBytesAny: pattern offset | length << 32
   uint32_t slot;
   uint32_t subject;    // SelSubject
   uint32_t op;         // SelOp
@@ -71,7 +80,25 @@ struct SelectArgs {
 };
 static_assert(sizeof(SelectArgs) <= 4096, "the term table travels as the kernel argument");
 
+// Kernel argument of k_sel_eval's instantiation for term tables with a kSelBytes / kSelBytesAny term
+// (the other two kernels take its SelectArgs): the bytes' source, as RaggedArgs has it, and the patterns
+struct SelectBytesArgs {
+  SelectArgs s;
+  const uint32_t* b_off;      // bytes views into `in` (not read where materialized or implicit)
+  const uint32_t* end32;      // [n] the decode's u32 record ends (read for terms with a const_off only)
+  const uint8_t* in;          // the batch (views) or the materialized byte column
+  uint32_t in_bound;          // readable bytes of `in` (a multiple of 16): bytes past it are 0
+  uint32_t scan_min;          // CONTAINS: elements longer than this take the wave scan
+  int32_t const_off[kSelMaxTerms];  // bytes term under tfrg_info.implicit_off_slots: the element of record g
+                                    // lies at end32[g] + const_off; else kSelOffStored
+  // the operands back to back, read as aligned dword pairs (hence the words after the last pattern byte)
+  uint32_t pat[kSelMaxPatternBytes / 4 + 2];
+};
+static_assert(sizeof(SelectBytesArgs) <= 4096, "the patterns travel as the kernel argument");
+
 // (m > 0 and n > 0)
 hipError_t launch_select(const SelectArgs& a, hipStream_t st);
+// the same three launches with the bytes instantiation of the first
+hipError_t launch_select_bytes(const SelectBytesArgs& a, hipStream_t st);
 
 }  // namespace tfrg

@@ -164,6 +164,17 @@ SEL_LT = 2
 SEL_LE = 3
 SEL_GT = 4
 SEL_GE = 5
+SEL_BYTES = 5  # tfrg_result_select_match alone: subjects whose operand is a byte string ...
+SEL_BYTES_ANY = 6
+SEL_PREFIX = 6  # ... and the ops that only they take
+SEL_SUFFIX = 7
+SEL_CONTAINS = 8
+SEL_MAX_PATTERN = 256  # bytes per pattern, and of all patterns of a call
+SEL_MAX_PATTERN_BYTES = 2048
+# tfrg_ctx_set_select_scan's range and default (csrc/tfrg_select.h)
+SEL_SCAN_MIN = 4
+SEL_SCAN_MAX = 65536
+SEL_SCAN_DEFAULT = 256
 SEL_APPEND = 1  # tfrg_result_select_rows flags
 # tfrg_ctx_set_select_tile's range and default (csrc/tfrg_select.h), and the tile sums its scan kernel
 # takes per pass
@@ -257,6 +268,10 @@ SIGNATURES: dict[str, tuple] = {
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_uint32, C.c_void_p]),
     "tfrg_ctx_set_select_tile": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "tfrg_result_select_match": (C.c_int, [C.c_void_p, C.POINTER(TfrgSelectTerm), C.c_uint32, C.c_char_p, C.c_uint64,
+                                           C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.c_void_p, C.c_uint32,
+                                           C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tfrg_ctx_set_select_scan": (C.c_int, [C.c_void_p, C.c_uint32]),
 }
 
 FLAG_PAYLOAD_ONLY = 1

@@ -537,10 +537,16 @@ class HipDecoder:
         """Candidates per workgroup tile of ``select`` (a power of two from 64 to 4096; 0: the default 1024)."""
         N.check(self._lib.tfrg_ctx_set_select_tile(self._ctx, int(rows)), "tfrg_ctx_set_select_tile")
 
+    def set_select_scan(self, nbytes: int) -> None:
+        """``select`` with a "contains" ``BytesTerm``: elements longer than ``nbytes`` are scanned by a whole
+        wave, shorter ones by one lane (4 to 65536; 0: the default 256). The result does not depend on it."""
+        N.check(self._lib.tfrg_ctx_set_select_scan(self._ctx, int(nbytes)), "tfrg_ctx_set_select_scan")
+
     def select(self, where, *, rows=None, capacity=None, dtype: str = "int64", out=None, stream: int | None = None):
-        """The rows of the last decode that pass ``where`` (``tfr_reader.select.Term``s), as a row
-        list on this decoder's device that ``dense`` / ``ragged`` take as ``rows=``
-        (tfrg_result_select_rows); see ``tfr_reader.select.decoder_select``."""
+        """The rows of the last decode that pass ``where`` (``tfr_reader.select.Term``s and
+        ``BytesTerm``s), as a row list on this decoder's device that ``dense`` / ``ragged`` take as
+        ``rows=`` (tfrg_result_select_rows / tfrg_result_select_match); see
+        ``tfr_reader.select.decoder_select``."""
         from tfr_reader import select as S  # noqa: PLC0415
 
         return S.decoder_select(self, where, rows=rows, capacity=capacity, dtype=dtype, out=out, stream=stream)

@@ -14,8 +14,14 @@ an operand:
 Integers compare as signed 64-bit, float32 values by value (NaN is false under every op but ``!=``,
 ``-0.0 == 0.0``, denormals are not flushed). ``Status(op, operand)`` compares the record's decode status.
 
+A ``BytesTerm`` compares an element of a bytes list with a byte string -- ``name == b"cat"``,
+``path.startswith(b"train/")``, ``b"rose" in name`` -- by Python's own ``bytes`` semantics, for element
+``index`` (``subject="value"``) or for any element (``subject="any"``); ``bytes_in`` builds the OR group
+of ``id IN (...)``.
+
 * ``HipDecoder.select`` / ``ShardDecoder.select`` evaluate a ``where`` on the device over the columns
-  where the decode left them (``tfrg_result_select_rows``) and return a ``Selection`` whose ``.rows``
+  where the decode left them (``tfrg_result_select_rows``; with a ``BytesTerm``,
+  ``tfrg_result_select_match``) and return a ``Selection`` whose ``.rows``
   -- a device tensor -- is ``rows=`` of ``dense`` / ``ragged`` / ``minibatches`` as it is; with
   ``capacity=`` nothing synchronises with the host;
 * ``BatchResult.select`` / ``selectify`` compute the same function with numpy from fetched columns,
@@ -130,18 +136,82 @@ def is_in(key: str, dtype: str, values: Sequence) -> list[Term]:
     return [Term(key, dtype, "==", v) for v in values]
 
 
+BYTES_OPS = {**OPS, "startswith": N.SEL_PREFIX, "endswith": N.SEL_SUFFIX, "contains": N.SEL_CONTAINS}
+BYTES_SUBJECTS = {"value": N.SEL_BYTES, "any": N.SEL_BYTES_ANY}
+# element op operand, as Python's own bytes objects have it
+_PY_BYTES_OPS = {**_PY_OPS, "startswith": bytes.startswith, "endswith": bytes.endswith,
+                 "contains": lambda element, operand: operand in element}
+
+
+@dataclass(frozen=True)
+class BytesTerm:
+    """An element of ``key``'s bytes list under ``op`` against the byte string ``operand`` (``bytes``,
+    or a ``str``, which is encoded as UTF-8; at most ``N.SEL_MAX_PATTERN`` bytes). ``op``: "==", "!=",
+    "<", "<=", ">", ">=" compare as ``bytes`` objects do (unsigned bytes, the first difference decides,
+    a proper prefix is less); "startswith", "endswith", "contains" as the ``bytes`` methods and ``in``
+    do. ``subject``: "value" -- element ``index`` of the list, false whatever the op for a record that
+    has no such element; "any" -- true iff some element of the list satisfies the op."""
+
+    key: str
+    op: str
+    operand: bytes | str
+    subject: str = "value"
+    index: int = 0
+
+    dtype = "uint8"  # (the slot kind, as for ``Dense`` and ``Term``)
+
+    def __post_init__(self) -> None:
+        what = f"BytesTerm({self.key!r})"
+        if not isinstance(self.key, str):
+            raise TypeError(f"BytesTerm key must be a str, not {type(self.key).__name__}")
+        if self.op not in BYTES_OPS:
+            raise ValueError(f"{what}: op must be one of {list(BYTES_OPS)}, not {self.op!r}")
+        if self.subject not in BYTES_SUBJECTS:
+            raise ValueError(f"{what}: subject must be one of {list(BYTES_SUBJECTS)}, not {self.subject!r}")
+        if isinstance(self.index, (bool, np.bool_)) or not isinstance(self.index, (int, np.integer)) \
+                or not 0 <= int(self.index) < 1 << 32:
+            raise ValueError(f"{what}: index must be in 0..2^32 - 1, not {self.index!r}")
+        if self.index and self.subject != "value":
+            raise ValueError(f"{what}: index is for subject 'value' alone")
+        if isinstance(self.operand, str):
+            object.__setattr__(self, "operand", self.operand.encode("utf-8"))
+        elif isinstance(self.operand, (bytes, bytearray)):
+            object.__setattr__(self, "operand", bytes(self.operand))
+        else:
+            raise TypeError(f"{what}: the operand must be bytes or str, not {self.operand!r}")
+        if len(self.operand) > N.SEL_MAX_PATTERN:
+            raise ValueError(f"{what}: the operand has {len(self.operand)} bytes, more than {N.SEL_MAX_PATTERN}")
+
+    @property
+    def kind(self) -> int:
+        return D.DTYPES[self.dtype][1]
+
+
+def bytes_in(key: str, values: Sequence) -> list[BytesTerm]:
+    """An OR group: ``key``'s first element is one of ``values``."""
+    return [BytesTerm(key, "==", v) for v in values]
+
+
+def pack_pattern(offset: int, length: int) -> int:
+    """``tfrg_select_term.operand`` of a bytes term: the pattern's range in the call's patterns."""
+    return offset | (length << 32)
+
+
+_TERMS = (Term, Status, BytesTerm)
+
+
 def check_where(where) -> list[list]:
-    """``where`` as a list of OR groups (lists of ``Term`` / ``Status``), validated: at most
-    ``N.SEL_MAX_TERMS`` terms in at most 32 groups."""
-    if isinstance(where, (Term, Status)) or not isinstance(where, Sequence) or isinstance(where, (str, bytes)):
+    """``where`` as a list of OR groups (lists of ``Term`` / ``BytesTerm`` / ``Status``), validated:
+    at most ``N.SEL_MAX_TERMS`` terms in at most 32 groups."""
+    if isinstance(where, _TERMS) or not isinstance(where, Sequence) or isinstance(where, (str, bytes)):
         raise TypeError("where must be a list of Terms (ANDed) and lists of Terms (OR groups)")
     groups = []
     for item in where:
-        if isinstance(item, (Term, Status)):
+        if isinstance(item, _TERMS):
             groups.append([item])
         elif isinstance(item, Sequence) and not isinstance(item, (str, bytes)):
             for t in item:
-                if not isinstance(t, (Term, Status)):
+                if not isinstance(t, _TERMS):
                     raise TypeError(f"an OR group holds Terms, not {type(t).__name__}")
             groups.append(list(item))
         else:
@@ -156,13 +226,22 @@ def check_where(where) -> list[list]:
 # ---------------------------------------------------------------------- host path (numpy)
 def select_mask(where, *, n: int, slot_key: Sequence[str | None], slot_kind: Sequence[int], row_splits: np.ndarray,
                 slot_base: np.ndarray, i64: np.ndarray, f32: np.ndarray, status: np.ndarray,
-                bytes_len: np.ndarray | None = None, bytes_offsets: np.ndarray | None = None) -> np.ndarray:
+                bytes_len: np.ndarray | None = None, bytes_offsets: np.ndarray | None = None,
+                bytes_off: np.ndarray | None = None, buf: np.ndarray | None = None,
+                bytes_data: np.ndarray | None = None) -> np.ndarray:
     """Which of the n records pass ``where`` (bool ``[n]``), from plain result columns, record by
-    record and term by term. A key without a slot is absent from every record."""
+    record and term by term. A key without a slot is absent from every record. A ``BytesTerm`` reads
+    its elements as ``bytes``: from ``bytes_data`` / ``bytes_offsets`` where the bytes are
+    materialized, else from the ``(bytes_off, bytes_len)`` views into ``buf``."""
     groups = check_where(where)
     cols = {}
 
-    def column(t: Term):
+    def element(e: int) -> bytes:
+        if bytes_data is not None:
+            return bytes_data[int(bytes_offsets[e]) : int(bytes_offsets[e + 1])].tobytes()
+        return buf[int(bytes_off[e]) : int(bytes_off[e]) + int(bytes_len[e])].tobytes()
+
+    def column(t):
         s = D.find_slot(slot_key, slot_kind, t.key, t.kind)
         if s is None:
             return None
@@ -173,7 +252,7 @@ def select_mask(where, *, n: int, slot_key: Sequence[str | None], slot_kind: Seq
     f32v = np.asarray(f32).view(np.float32)
 
     def true_for(t, g: int) -> bool:
-        cmp = _PY_OPS[t.op]
+        cmp = _PY_BYTES_OPS[t.op]
         if isinstance(t, Status):
             return cmp(int(status[g]), int(t.operand))
         col = column(t)
@@ -181,6 +260,10 @@ def select_mask(where, *, n: int, slot_key: Sequence[str | None], slot_kind: Seq
         if col is not None:
             base, rs = col
             lo, c = base + rs[g], rs[g + 1] - rs[g]
+        if isinstance(t, BytesTerm):
+            if t.subject == "value":
+                return c > t.index and bool(cmp(element(lo + int(t.index)), t.operand))
+            return any(cmp(element(lo + j), t.operand) for j in range(c))
         if t.subject == "count":
             return cmp(c, t.rhs)
         if t.subject == "bytes_len":
@@ -224,7 +307,8 @@ def selectify(where, *, rows=None, row0: int = 0, **columns) -> tuple[np.ndarray
 def batch_columns(res) -> dict:
     return dict(n=len(res), slot_key=res.slot_key, slot_kind=res.slot_kind, row_splits=res.row_splits,
                 slot_base=res.slot_base, i64=res.i64, f32=res.f32, status=res.status, bytes_len=res.bytes_len,
-                bytes_offsets=res.bytes_offsets if res.bytes_data is not None else None)
+                bytes_offsets=res.bytes_offsets if res.bytes_data is not None else None, bytes_off=res.bytes_off,
+                buf=res.buf, bytes_data=res.bytes_data)
 
 
 def batch_select(res, where, rows=None, row0: int = 0) -> tuple[np.ndarray, tuple[int, int]]:
@@ -235,24 +319,41 @@ def batch_select(res, where, rows=None, row0: int = 0) -> tuple[np.ndarray, tupl
 # ---------------------------------------------------------------------- device path
 def launch(dec, terms: Sequence[tuple], rows: tuple | None, m: int, row0: int, out: tuple | None, cap: int,
            count_ptr: int, stats_ptr: int | None, flags: int, consumer: int | None) -> None:
-    """One ``tfrg_result_select_rows`` call: terms are (slot, subject, op, group, index, operand bits);
-    ``rows``: (device pointer, TFRG_ROWS_* id) or None; ``out``: (device pointer or None, TFRG_ROWS_* id)."""
+    """One select call: terms are (slot, subject, op, group, index, operand bits); ``rows``: (device
+    pointer, TFRG_ROWS_* id) or None; ``out``: (device pointer or None, TFRG_ROWS_* id). A table with a
+    bytes term (``fold``'s ``TermTable``, whose ``patterns`` its operands index) goes through
+    ``tfrg_result_select_match``, any other through ``tfrg_result_select_rows``."""
     arr = (N.TfrgSelectTerm * max(len(terms), 1))()
     for a, (slot, subject, op, group, index, operand) in zip(arr, terms):
         a.slot, a.subject, a.op, a.group, a.index, a.reserved, a.operand = slot, subject, op, group, index, 0, operand
     ptr, rdt = rows if rows is not None else (None, 0)
     optr, odt = out if out is not None else (None, N.ROWS_I64)
-    N.check(dec._lib.tfrg_result_select_rows(dec._ctx, arr, len(terms), D.vp(ptr), rdt, m, row0, D.vp(optr), odt, cap,
-                                             D.vp(count_ptr), D.vp(stats_ptr), flags, D.vp(consumer)),
-            "tfrg_result_select_rows")
+    tail = (D.vp(ptr), rdt, m, row0, D.vp(optr), odt, cap, D.vp(count_ptr), D.vp(stats_ptr), flags, D.vp(consumer))
+    if any(t[1] in (N.SEL_BYTES, N.SEL_BYTES_ANY) for t in terms):
+        patterns = bytes(getattr(terms, "patterns", b""))
+        N.check(dec._lib.tfrg_result_select_match(dec._ctx, arr, len(terms), patterns, len(patterns), *tail),
+                "tfrg_result_select_match")
+        return
+    N.check(dec._lib.tfrg_result_select_rows(dec._ctx, arr, len(terms), *tail), "tfrg_result_select_rows")
 
 
-def fold(dec, groups: Sequence[Sequence]) -> list[tuple] | None:
+class TermTable(list):
+    """``fold``'s term table: a list of (slot, subject, op, group, index, operand bits), and the byte
+    strings its bytes terms index (``patterns``: the operands back to back, each stored once)."""
+
+    def __init__(self, terms=(), patterns: bytes = b"") -> None:
+        super().__init__(terms)
+        self.patterns = patterns
+
+
+def fold(dec, groups: Sequence[Sequence]) -> TermTable | None:
     """The term table of ``groups`` on ``dec``. A key or kind that is not in its key table is absent
-    from every record, so its terms are constants: value / any terms are false, count / bytes_len
-    terms compare 0. A false term leaves its group, a true one removes its group; None: a group was
-    emptied, nothing can pass."""
+    from every record, so its terms are constants: value / any terms (bytes terms included) are false,
+    count / bytes_len terms compare 0. A false term leaves its group, a true one removes its group;
+    None: a group was emptied, nothing can pass. The operands of the bytes terms that are kept go into
+    the table's ``patterns``, equal ones once (ValueError above ``N.SEL_MAX_PATTERN_BYTES``)."""
     terms = []
+    blob = bytearray()
     g = 0
     for grp in groups:
         kept, true = [], False
@@ -261,6 +362,10 @@ def fold(dec, groups: Sequence[Sequence]) -> list[tuple] | None:
                 kept.append((0, N.SEL_STATUS, OPS[t.op], 0, int(t.operand) & 0xFFFFFFFFFFFFFFFF))
                 continue
             slot = D.resolve_slot(dec, t)
+            if isinstance(t, BytesTerm):
+                if slot is not None:
+                    kept.append((slot, BYTES_SUBJECTS[t.subject], BYTES_OPS[t.op], int(t.index), t.operand))
+                continue
             if slot is None:
                 true |= t.subject in ("count", "bytes_len") and bool(_PY_OPS[t.op](0, t.rhs))
                 continue
@@ -269,9 +374,19 @@ def fold(dec, groups: Sequence[Sequence]) -> list[tuple] | None:
             continue
         if not kept:
             return None
-        terms += [(slot, subject, op, g, index, bits) for slot, subject, op, index, bits in kept]
+        for slot, subject, op, index, bits in kept:
+            if isinstance(bits, bytes):
+                at = blob.find(bits)  # (an operand that is already there, as a whole or inside another)
+                if at < 0:
+                    at = len(blob)
+                    blob += bits
+                bits = pack_pattern(at, len(bits))
+            terms.append((slot, subject, op, g, index, bits))
         g += 1
-    return terms
+    if len(blob) > N.SEL_MAX_PATTERN_BYTES:
+        raise ValueError(f"the byte-string operands of a where take at most {N.SEL_MAX_PATTERN_BYTES} bytes, "
+                         f"not {len(blob)}")
+    return TermTable(terms, bytes(blob))
 
 
 class Selection:
