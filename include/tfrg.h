@@ -466,6 +466,58 @@ int tfrg_result_ragged_rows(tfrg_ctx* ctx, const tfrg_ragged_spec* specs, uint32
  * (1024). A tuning/testing knob: with small tiles small row lists exercise the multi-tile logic. */
 int tfrg_ctx_set_ragged_tile(tfrg_ctx* ctx, uint32_t rows);
 
+/* Two-level ragged outputs: EVERY element of a bytes_list slot for a list of rows (the class strings
+ * of a detection record, tags, several encoded frames), as three flat arrays: a list (rows) of lists
+ * (elements) of byte strings. Rows (d_rows, rows_dtype, m, row0, a NULL d_rows as the identity list, the
+ * rule for entries outside [0, n)) are exactly tfrg_result_ragged_rows's; a skipped row is an empty row.
+ * Per spec and output row k < m, with g the row's record:
+ *   C(k): record g's element count, 0 for a skipped row, an absent key or an empty list;
+ *     cnt(k) = C(k), or min(C(k), max_elems) with max_elems != 0;
+ *   row_offsets[0] = 0, row_offsets[k + 1] = row_offsets[k] + cnt(k): all m + 1 are written, whatever
+ *     the capacities are. E = row_offsets[m];
+ *   output element e, row_offsets[k] <= e < row_offsets[k + 1], is element e - row_offsets[k] of
+ *     record g's list; L(e): its byte length; len(e) = L(e), or min(L(e), max_len) with max_len != 0;
+ *   elem_offsets[0] = 0, elem_offsets[e + 1] = elem_offsets[e] + len(e) for e < E' = min(E, elem_cap):
+ *     entries 0 .. E' are written and nothing else in the array;
+ *   values[elem_offsets[e] + i] for e < E', i < len(e): byte i of element e, the byte
+ *     tfrg_result_ragged_rows (TFRG_DENSE_U8) reads for an element (from the views into d_bytes, the
+ *     materialized column, or the end-relative view of an implicit_off_slots slot; zero past the
+ *     readable input). Only positions < cap are stored and nothing else in values is written.
+ * d_totals (device, [n_specs][2] u64, or NULL): E, and B = the sum of len(e) over all E elements (not
+ * only the first E'), so a first call without elem_offsets and values sizes both arrays exactly.
+ * d_stats (device, [n_specs][4] u32, or NULL; zeroed by the call on the stream): rows with
+ * C(k) > max_elems != 0; taken elements with L(e) > max_len != 0; rows that are not skipped and have
+ * C(k) == 0; skipped rows. A record drawn twice counts twice.
+ * m == 0: row_offsets[0] = 0, elem_offsets[0] = 0 where given, totals 0, no kernel. n == 0: every row
+ * is skipped, all offsets and totals are 0. Two equal calls write equal bytes. With max_elems == 0 over
+ * a decode whose records hold at most one element in the slot, values and B equal
+ * tfrg_result_ragged_rows's (U8) values and total over the same rows, and
+ * elem_offsets[row_offsets[k]] its offsets[k].
+ * Four launches on the decode's stream (counts and byte sums per tile of rows, a scan of the tile
+ * sums, the offsets, the copy); no device value is read back. Stream order, confirmation of an
+ * optimistic or hinted decode (the only host synchronisation, once per decode), the implicit columns
+ * that are neither written nor read, the full view afterwards and any number of calls per decode are
+ * as for tfrg_result_ragged_rows; the rows per tile are tfrg_ctx_set_ragged_tile's.
+ * TFRG_E_ARG (text in tfrg_last_error, nothing launched or written): no context, no result, n_specs
+ * outside 1..TFRG_ELEMS_MAX_SPECS, a slot >= n_slots or not a bytes_list slot, a NULL row_offsets,
+ * row_offsets or elem_offsets not 8-byte aligned, values without elem_offsets, a nonzero reserved, an
+ * unknown rows_dtype with a non-NULL d_rows, m >= 2^31. */
+#define TFRG_ELEMS_MAX_SPECS 32
+typedef struct tfrg_elems_spec {
+  uint32_t slot;         /* a bytes_list slot, as in tfrg_set_schema */
+  uint32_t max_elems;    /* 0: every element of a row; else at most its first max_elems */
+  uint32_t max_len;      /* 0: whole elements; else at most the first max_len bytes of each */
+  uint32_t reserved;     /* 0 */
+  uint64_t elem_cap;     /* elements that elem_offsets can describe (it holds elem_cap + 1 entries) */
+  uint64_t cap;          /* bytes that values can hold */
+  uint8_t* values;       /* device [cap], caller-owned; NULL: offsets and counters only */
+  int64_t* elem_offsets; /* device [elem_cap + 1], caller-owned; NULL: row offsets and counters only */
+  int64_t* row_offsets;  /* device [m + 1], caller-owned, not NULL */
+} tfrg_elems_spec;       /* 56 bytes */
+int tfrg_result_ragged_elems(tfrg_ctx* ctx, const tfrg_elems_spec* specs, uint32_t n_specs,
+                             const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
+                             uint64_t* d_totals, uint32_t* d_stats, void* consumer_stream);
+
 /* Filtered row lists: the WHERE clause over the last result, on the device. Predicates over the
  * decoded columns in, the compacted list of the passing rows in device memory out -- usable as it is
  * as d_rows of tfrg_result_dense_rows / tfrg_result_ragged_rows of the same context(s), with the same

@@ -15,6 +15,7 @@
 #include "../../include/tfrg.h"
 #include "crc32c.h"
 #include "tfrg_dense.h"
+#include "tfrg_elems.h"
 #include "tfrg_ragged.h"
 #include "tfrg_select.h"
 #include "tfrg_frame.h"
@@ -133,6 +134,7 @@ struct Arena {
   DBuf tpl, spec;  // record-shape templates, speculative placement (tfrg_learn_templates)
   DBuf fr_tab, fr_dev;  // tfrg_index_device: chunk table, piece rows + summary
   DBuf rg_tsum;  // tfrg_result_ragged_rows: the per-tile sums
+  DBuf el_tsum;  // tfrg_result_ragged_elems: the per-tile element counts and byte sums
   DBuf sel_buf;  // tfrg_result_select_rows: the candidates' ballot words, then the per-tile sums
   template <class F>
   void each(F f) {
@@ -140,7 +142,8 @@ struct Arena {
                          &in_bytes, &in_start, &in_end, &status, &aux, &verdict, &order, &count, &loc, &rs, &slot_base,
                          &totals, &kind_totals, &ident, &i64, &f32, &b_off, &b_len, &big_list, &slow_list, &miss, &info,
                          &tsum, &crc_rec, &crc_base, &crc_part, &dq, &dq_cnt, &lmask, &rlist, &bdata, &boff64, &blb,
-                         &bbig, &tpl, &spec, &fr_tab, &fr_dev, &rg_tsum, &sel_buf};
+                         &bbig, &tpl, &spec, &fr_tab, &fr_dev, &rg_tsum, &el_tsum,
+                         &sel_buf};
     static_assert(sizeof(all) / sizeof(*all) * sizeof(DBuf) == sizeof(Arena), "a buffer is missing from the list");
     for (DBuf* b : all) f(*b);
   }
@@ -1298,6 +1301,7 @@ static int32_t const_off_of(const tfrg_ctx* c, uint32_t slot, bool reads_off) {
 // constant_fills: the shapes' length holds); else, or for a spec / term that reads no length, the
 // kernels' "the column is stored" sentinel.
 static_assert(kDenseNoLen == kRaggedNoLen && kRaggedNoLen == kSelNoLen, "one const_len lookup serves all three");
+static_assert(kElemsNoLen == kDenseNoLen && kElemsOffStored == kDenseOffStored, "and tfrg_elems.h's kernels");
 static uint32_t const_len_of(const tfrg_ctx* c, uint32_t slot, bool reads_len) {
   if (!reads_len || !(c->res.implicit & TFRG_IMPLICIT_BYTES_LEN)) return kDenseNoLen;
   return implicit_len(c->res, slot);
@@ -1501,6 +1505,97 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
     }
     if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 8, st));
+  }
+  return fence_close(c, st, cs);
+}
+
+// Every element of a bytes_list slot for a list of rows: bytes + element offsets + row offsets
+// (tfrg_elems.h: counts and byte sums, tile scan, offsets, copy). Every grid size comes from m, n_specs,
+// the tile and the split: nothing is read back from the device.
+int tfrg_result_ragged_elems(tfrg_ctx* c, const tfrg_elems_spec* specs, uint32_t n_specs, const void* d_rows,
+                             uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
+                             void* consumer_stream) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_result_ragged_elems: " + why);
+    return TFRG_E_ARG;
+  };
+  if (const int rc = check_specs(c, specs, n_specs, TFRG_ELEMS_MAX_SPECS, bad)) return rc;
+  static_assert(TFRG_ELEMS_MAX_SPECS == kElemsMaxSpecs, "tfrg.h mirrors tfrg_elems.h");
+  static_assert(sizeof(tfrg_elems_spec) == 56, "tfrg.h states the size");
+  bool any_values = false;
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_elems_spec& s = specs[i];
+    const std::string at = "spec " + std::to_string(i) + ": ";
+    if (s.slot >= c->n_slots) return bad(at + "slot " + std::to_string(s.slot) + " >= n_slots");
+    const uint32_t kind = c->slot_kind_h[s.slot] & 3u;
+    if (kind != TFRG_KIND_BYTES)
+      return bad(at + "slot " + std::to_string(s.slot) + " is not a bytes_list slot (kind " + std::to_string(kind) + ")");
+    if (!s.row_offsets) return bad(at + "row_offsets is NULL");
+    if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.elem_offsets & 7u))
+      return bad(at + "row_offsets and elem_offsets must be 8-byte aligned");
+    if (s.values && !s.elem_offsets) return bad(at + "values without elem_offsets");
+    if (s.reserved) return bad(at + "reserved must be 0");
+    any_values |= s.values != nullptr && s.cap != 0 && s.elem_cap != 0;
+  }
+  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
+  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
+  const uint32_t tile = c->ragged_tile;
+  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile;
+  // workgroups per tile that share its bytes: up to kElemsMaxSplit while the launch is below 4 per CU
+  // (0: no spec has bytes to store, and the copy is not launched)
+  uint64_t split = 0;
+  if (any_values && tiles) {
+    const uint64_t want = (uint64_t)std::max(c->num_cus, 1) * 4u, have = tiles * n_specs;
+    split = std::min<uint64_t>(kElemsMaxSplit, std::max<uint64_t>(1, (want + have - 1) / have));
+  }
+  if (tiles * n_specs * std::max<uint64_t>(split, 1) > 0x7fffffffull)
+    return bad("too many tiles for one launch: raise the ragged tile");
+  HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = confirm_pending(c)) return rc;
+  const bool run = m && c->res.req.n;
+  if (run) HIP_TRY(c->el_tsum.ensure((size_t)(tiles * n_specs) * 16));
+  hipStream_t st, cs;
+  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
+  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
+  if (run) {
+    ElemsArgs a{};
+    fill_columns(c, a);
+    fill_bytes_source(c, a);
+    a.stats = d_stats;
+    a.totals = d_totals;
+    a.tsum = c->el_tsum.as<uint64_t>();
+    a.rows = d_rows;
+    a.rows64 = rows_dtype == TFRG_ROWS_I64;
+    a.row0 = row0;
+    a.m = m;
+    a.n_specs = n_specs;
+    a.tile = tile;
+    a.tiles = (uint32_t)tiles;
+    a.split = (uint32_t)split;
+    for (uint32_t i = 0; i < n_specs; ++i) {
+      const tfrg_elems_spec& s = specs[i];
+      ElemsSpec& d = a.sp[i];
+      d.values = s.values;
+      d.elem_offsets = s.elem_offsets;
+      d.row_offsets = s.row_offsets;
+      d.elem_cap = s.elem_cap;
+      d.cap = s.cap;
+      d.slot = s.slot;
+      d.max_elems = s.max_elems;
+      d.max_len = s.max_len;
+      d.const_len = const_len_of(c, s.slot, true);
+      d.const_off = const_off_of(c, s.slot, true);
+    }
+    HIP_TRY(launch_elems(a, st));
+  } else {
+    // no row, or no record (every row is skipped): all offsets and totals are 0
+    for (uint32_t i = 0; i < n_specs; ++i) {
+      HIP_TRY(hipMemsetAsync(specs[i].row_offsets, 0, ((size_t)m + 1) * 8, st));
+      if (specs[i].elem_offsets) HIP_TRY(hipMemsetAsync(specs[i].elem_offsets, 0, 8, st));
+      if (d_stats && m)
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
+    }
+    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 16, st));
   }
   return fence_close(c, st, cs);
 }

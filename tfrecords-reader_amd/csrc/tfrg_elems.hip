@@ -1,0 +1,607 @@
+// tfrg_elems.hip — the kernels behind tfrg_result_ragged_elems: for a list of m rows (row k is record
+// g = entry(k) - row0) and every requested bytes_list slot, EVERY element of the rows' lists: the
+// elements' bytes back to back (values), the E + 1 offsets of the elements in them (elem_offsets) and
+// the m + 1 offsets of the rows in elements (row_offsets). Four launches on the decode's stream, no
+// workgroup ever waiting on another (the shape of k_rg_len / k_rg_scan / k_rg_gather in tfrg_ragged.hip):
+//
+//   k_el_len   per (spec, tile of `tile` rows): the rows' element counts scanned into LDS, then the
+//              tile's elements shared by the lanes (lane t takes tile-local elements t, t + 256, ...
+//              and finds each one's row by a binary search in LDS) for the tile's byte sum; both sums
+//              into the scratch, and the four counters (per-lane tallies, one wave reduction, at most
+//              one atomic per wave and counter);
+//   k_el_scan  one workgroup per spec: both tile sums to their exclusive bases, carrying across passes
+//              of kElemsScanThreads tiles; row_offsets[m], the totals (E, B), and elem_offsets[E] = B
+//              where E <= elem_cap;
+//   k_el_offs  per (spec, tile): the tile's row_offsets; then the elements again, in passes of 256 whose
+//              lengths are scanned from the tile's byte base: element e < E writes its start to
+//              elem_offsets[e] where e <= elem_cap (so with E > elem_cap the entry elem_cap is the end
+//              of the last described element);
+//   k_el_copy  per (spec, tile, s < S): the tile's span [elem_offsets[e0], min(elem_offsets[e1], cap))
+//              of its elements [e0, e1) below elem_cap, copied with work laid out along the OUTPUT as
+//              k_rg_gather does: after the bytes up to the first 16-byte boundary of the output's
+//              address, lane l of a wave stores the 16-byte unit after lane l - 1's; a unit finds its
+//              element by a binary search in the elem_offsets k_el_offs wrote, the element's row (and so
+//              its source) in the tile's row table in LDS, and walks on over element and row ends. The
+//              span's chunks of kElemsChunk units are dealt to the tile's S workgroups in S consecutive
+//              runs, so one long element is shared by all of them, and a lane's next unit lies 4 KB after
+//              its last: it keeps its element, or searches on from it.
+//
+// Tiles are not balanced against each other: a tile whose rows hold many elements takes longer than its
+// neighbours in k_el_len and k_el_offs (the copy is spread by bytes within a tile only).
+//
+// Not read (as k_rg_*): the row splits of a placed slot, the bytes_len column of a slot whose length is
+// constant (ElemsSpec::const_len), the bytes_off words of a slot the decode left implicit
+// (ElemsSpec::const_off: the decode's u32 record ends are read in their place), status / aux / verdict /
+// order and the numeric columns. The input of the bytes views is read through a buffer resource bounded
+// to the batch: a view that runs past it reads zeros.
+//
+// A row whose g is not in [0, n) is an empty row: nothing indexed by g is loaded for it (it reads
+// record 0 and drops it), and it counts in the fourth counter alone.
+#include <hip/hip_runtime.h>
+
+#include "tfrg_dev.h"
+#include "tfrg_elems.h"
+#include "tfrg_internal.h"
+
+namespace tfrg {
+namespace {
+
+typedef uint32_t el_u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr uint32_t kBlk = 256;
+
+// The kernel argument is read in place, in the constant address space (scalar loads)
+typedef const __attribute__((address_space(4))) ElemsArgs* KArgs;
+typedef const __attribute__((address_space(4))) ElemsSpec* KSpec;
+
+// the spec a workgroup works in (uniform)
+struct Sp {
+  KArgs a;
+  KSpec s;
+  const uint32_t* rs;  // the slot's row splits; null: placed (record g holds one element, at index g)
+  uint64_t base;       // slot_base[slot]
+  uint32_t max_elems, max_len;
+  bool by_end;         // the element of record g lies at end32[g] + const_off
+  __amdgpu_buffer_rsrc_t in;
+  const uint8_t* rows;
+  int64_t row0;
+  uint32_t rsh, rhi;
+};
+
+__device__ __forceinline__ Sp make_sp(KArgs a, uint32_t si) {
+  const KSpec s = &a->sp[si];
+  const uint32_t* const info = a->info;
+  const uint64_t placed = ((uint64_t)info[kInfoPlacedHi] << 32) | info[kInfoPlacedLo];
+  const uint32_t slot = s->slot;
+  Sp x;
+  x.a = a;
+  x.s = s;
+  x.base = a->slot_base[slot];
+  x.rs = (slot < 64u && ((placed >> slot) & 1ull)) ? nullptr : a->rs + (uint64_t)slot * ((uint64_t)a->n + 1u);
+  x.max_elems = s->max_elems;
+  x.max_len = s->max_len;
+  x.by_end = !a->b_off64 && s->const_off != kElemsOffStored;
+  x.in = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a->in), (short)0, (int)a->in_bound, 0x00020000);
+  x.rows = static_cast<const uint8_t*>(a->rows);
+  x.row0 = a->row0;
+  x.rsh = a->rows64 ? 3u : 2u;
+  x.rhi = a->rows64 ? 4u : 0u;
+  return x;
+}
+
+// The record of row k < m (tfrg_dense.hip rec_of's rule: compared before the subtraction, whose
+// unsigned result is then the true difference, so no entry wraps into range)
+struct Rec {
+  uint32_t g;
+  uint32_t ok;  // 0 / 1, in a vector register
+};
+
+__device__ __forceinline__ Rec rec_of(const Sp& x, uint32_t k) {
+  int64_t v = (int64_t)k;
+  if (x.rows) {
+    const uint8_t* const p = x.rows + ((uint64_t)k << x.rsh);
+    const uint32_t lo = *reinterpret_cast<const uint32_t*>(p);
+    const uint32_t hi = *reinterpret_cast<const uint32_t*>(p + x.rhi);
+    v = x.rhi ? (int64_t)(((uint64_t)hi << 32) | lo) : (int64_t)(int32_t)lo;
+  }
+  const uint64_t d = (uint64_t)v - (uint64_t)x.row0;
+  const bool ok = v >= x.row0 && d < (uint64_t)x.a->n;
+  uint32_t okv = ok ? 1u : 0u;
+  asm("" : "+v"(okv));  // (kept as a value)
+  return Rec{ok ? (uint32_t)d : 0u, okv};
+}
+
+// One row of the output: its first `cnt` elements, element j being number src + j of the slot's column
+// (by_end: src is the record, whose one element lies at its end plus a constant)
+struct Row {
+  uint32_t cnt;  // after max_elems; 0 for a skipped row
+  uint32_t C;    // the record's element count
+  uint32_t src;
+  uint32_t ok;
+};
+
+__device__ __forceinline__ Row row_of(const Sp& x, uint32_t k) {
+  const Rec q = rec_of(x, k);
+  uint32_t lo = q.g, c = 1u;
+  if (x.rs) {
+    lo = x.rs[q.g];
+    c = x.rs[q.g + 1u] - lo;
+  }
+  c = q.ok ? c : 0u;  // (a skipped row is a record without an element to everything that loads)
+  Row r;
+  r.ok = q.ok;
+  r.C = c;
+  r.cnt = (x.max_elems && c > x.max_elems) ? x.max_elems : c;
+  r.src = x.by_end ? q.g : lo;
+  return r;
+}
+
+// the byte length of element j of the row whose elements start at src
+__device__ __forceinline__ uint32_t elem_L(const Sp& x, uint32_t src, uint32_t j) {
+  const uint64_t es = x.base + src + j;
+  if (x.a->b_off64) {
+    const uint64_t l = x.a->b_off64[es + 1] - x.a->b_off64[es];
+    return l < 0xffffffffull ? (uint32_t)l : 0xffffffffu;
+  }
+  return x.s->const_len != kElemsNoLen ? x.s->const_len : x.a->b_len[es];
+}
+
+__device__ __forceinline__ uint32_t clamp_len(const Sp& x, uint32_t L) { return (x.max_len && L > x.max_len) ? x.max_len : L; }
+
+// the position of its first byte in the bytes' source
+__device__ __forceinline__ uint32_t elem_off(const Sp& x, uint32_t src, uint32_t j) {
+  const uint64_t es = x.base + src + j;
+  if (x.a->b_off64) {
+    const uint64_t o0 = x.a->b_off64[es];
+    return o0 < 0xffffffffull ? (uint32_t)o0 : 0xffffffffu;
+  }
+  return x.by_end ? x.a->end32[src] + (uint32_t)x.s->const_off : x.a->b_off[es];
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+  return v;
+}
+
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += (uint64_t)__shfl_down((unsigned long long)v, d, 64);
+  return v;
+}
+
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t u = (uint64_t)__shfl_up((unsigned long long)v, o, 64);
+    if (lane >= (uint32_t)o) v += u;
+  }
+  return v;
+}
+
+// exclusive scan of v over the workgroup (W waves, every thread calls); *total: the workgroup's sum
+// (tfrg_ragged.hip's block_excl_scan64)
+template <int W>
+__device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t* part, uint64_t* total) {
+  const uint64_t inc = wave_incl_scan64(v);
+  const uint32_t w = threadIdx.x >> 6;
+  __syncthreads();  // (part may still be read from a previous call)
+  if ((threadIdx.x & 63u) == 63u) part[w] = inc;
+  __syncthreads();
+  uint64_t before = 0, all = 0;
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    const uint64_t s = part[i];
+    before += (uint32_t)i < w ? s : 0ull;
+    all += s;
+  }
+  *total = all;
+  return before + inc - v;
+}
+
+// The tile in LDS: eo[r] for r <= nrows are the absolute element offsets of its rows (eo[nrows]: of the
+// row after the tile), src[r] the row's source.
+struct Tile {
+  const uint64_t* eo;
+  const uint32_t* src;
+  uint32_t nrows;
+};
+
+// dynamic LDS of the three kernels with a row table: eo [tile + 2] u64, src [tile] u32, part [16] u64
+struct Lds {
+  uint64_t* eo;
+  uint32_t* src;
+  uint64_t* part;
+};
+
+__device__ __forceinline__ Lds carve(uint8_t* lds, uint32_t tile) {
+  Lds l;
+  l.eo = reinterpret_cast<uint64_t*>(lds);
+  l.src = reinterpret_cast<uint32_t*>(l.eo + tile + 2u);
+  l.part = reinterpret_cast<uint64_t*>(l.src + tile);
+  return l;
+}
+
+// the row of element e, eo[0] <= e < eo[nrows]: the last r with eo[r] <= e (rows without an element
+// share their offset with the row after them)
+__device__ __forceinline__ uint32_t row_at(const Tile& T, uint64_t e) {
+  uint32_t lo = 0, hi = T.nrows;
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (T.eo[mid] <= e) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Elements per lane and pass in k_el_len and k_el_offs: the lane's kPer elements (t, t + 256, ... of the
+// pass) are searched in lockstep and their lengths loaded together, so a pass waits for one LDS chain
+// and one memory latency, not kPer of each
+constexpr uint32_t kPer = 4;
+
+// row_at for kPer elements at once: the same number of steps for each (nrows alone decides it)
+__device__ __forceinline__ void rows_at(const Tile& T, const uint64_t (&e)[kPer], uint32_t (&r)[kPer]) {
+#pragma unroll
+  for (uint32_t i = 0; i < kPer; ++i) r[i] = 0u;
+  for (uint32_t s = 1u << (31 - __builtin_clz(T.nrows)); s; s >>= 1) {
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; ++i) {
+      const uint32_t mid = r[i] + s;
+      if (mid < T.nrows && T.eo[mid] <= e[i]) r[i] = mid;
+    }
+  }
+}
+
+// the tile's rows into LDS: element counts scanned from the tile's base, sources. TALLY: the three
+// per-row counters into the lane's tallies.
+template <bool TALLY>
+__device__ __forceinline__ void scan_rows(const Sp& x, uint32_t t0, uint32_t nrows, uint64_t base, const Lds& l,
+                                          uint32_t& rtrunc, uint32_t& empty, uint32_t& skip) {
+  uint64_t carry = base;
+  for (uint32_t r0 = 0; r0 < nrows; r0 += kBlk) {
+    const uint32_t r = r0 + threadIdx.x;
+    Row w{};
+    if (r < nrows) {
+      w = row_of(x, t0 + r);
+      if constexpr (TALLY) {
+        // (branch-free: a skipped row counts in `skip` alone; its C is 0)
+        rtrunc += w.C > w.cnt;
+        empty += w.ok & (uint32_t)(w.C == 0u);
+        skip += w.ok ^ 1u;
+      }
+    }
+    uint64_t total;
+    const uint64_t ex = block_excl_scan64<kBlk / 64>((uint64_t)w.cnt, l.part, &total);
+    if (r < nrows) {
+      l.eo[r] = carry + ex;
+      l.src[r] = w.src;
+    }
+    carry += total;
+  }
+  if (threadIdx.x == 0) l.eo[nrows] = carry;
+  __syncthreads();
+}
+
+// ------------------------------------------------------------------ 1. counts and byte sums
+__global__ __launch_bounds__(kBlk) void k_el_len(const ElemsArgs) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t el_lds[];
+  const KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();  // (the only argument)
+  const uint32_t tiles = a->tiles, tile = a->tile;
+  const uint32_t si = blockIdx.x / tiles, ti = blockIdx.x - si * tiles;
+  const Lds l = carve(el_lds, tile);
+  const Sp x = make_sp(a, si);
+  const uint32_t t0 = ti * tile;
+  const uint32_t nrows = a->m - t0 < tile ? a->m - t0 : tile;
+  uint32_t rtrunc = 0, etrunc = 0, empty = 0, skip = 0;
+  scan_rows<true>(x, t0, nrows, 0ull, l, rtrunc, empty, skip);
+  const Tile T{l.eo, l.src, nrows};
+  const uint64_t et = l.eo[nrows];
+  uint64_t sum = 0;
+  for (uint64_t p0 = 0; p0 < et; p0 += kPer * kBlk) {
+    uint64_t e[kPer];
+    uint32_t r[kPer], L[kPer];
+    bool on[kPer];
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; ++i) {
+      e[i] = p0 + i * kBlk + threadIdx.x;
+      on[i] = e[i] < et;
+      e[i] = on[i] ? e[i] : p0;  // (an element past the tile's reads the pass's first one and drops it)
+    }
+    rows_at(T, e, r);
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; ++i) L[i] = elem_L(x, T.src[r[i]], (uint32_t)(e[i] - T.eo[r[i]]));
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; ++i) {
+      const uint32_t len = clamp_len(x, L[i]);
+      sum += on[i] ? len : 0u;
+      etrunc += on[i] && L[i] > len;
+    }
+  }
+  sum = wave_sum64(sum);
+  __syncthreads();  // (part was last read by scan_rows)
+  if ((threadIdx.x & 63u) == 0u) l.part[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t all = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < kBlk / 64; ++i) all += l.part[i];
+    a->tsum[blockIdx.x] = et;
+    a->tsum[(uint64_t)a->n_specs * tiles + blockIdx.x] = all;
+  }
+  uint32_t* const stats = a->stats;
+  if (!stats) return;
+  // one atomic per wave and counter at the most
+  const uint32_t rt = wave_sum(rtrunc), tr = wave_sum(etrunc), em = wave_sum(empty), sk = wave_sum(skip);
+  if ((threadIdx.x & 63u) == 0u) {
+    uint32_t* st = stats + 4u * si;
+    if (rt) atomicAdd(st + 0, rt);
+    if (tr) atomicAdd(st + 1, tr);
+    if (em) atomicAdd(st + 2, em);
+    if (sk) atomicAdd(st + 3, sk);
+  }
+}
+
+// ------------------------------------------------------------------ 2. tile scan
+// one workgroup per spec: both tile sums to their exclusive prefixes, E to row_offsets[m], (E, B) to the
+// totals, and B to elem_offsets[E] where that entry exists
+__global__ __launch_bounds__(kElemsScanThreads) void k_el_scan(const ElemsArgs) {
+  __shared__ uint64_t part[kElemsScanThreads / 64];
+  const KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  const uint32_t tiles = a->tiles, si = blockIdx.x;
+  uint64_t tot[2];
+#pragma unroll
+  for (uint32_t w = 0; w < 2u; ++w) {
+    uint64_t* const tsum = a->tsum + ((uint64_t)w * a->n_specs + si) * tiles;
+    uint64_t carry = 0;
+    for (uint32_t b0 = 0; b0 < tiles; b0 += kElemsScanThreads) {
+      const uint32_t i = b0 + threadIdx.x;
+      const uint64_t v = i < tiles ? tsum[i] : 0ull;
+      uint64_t total;
+      const uint64_t ex = block_excl_scan64<kElemsScanThreads / 64>(v, part, &total);
+      if (i < tiles) tsum[i] = carry + ex;
+      carry += total;
+    }
+    tot[w] = carry;
+  }
+  if (threadIdx.x == 0) {
+    const KSpec s = &a->sp[si];
+    s->row_offsets[a->m] = (int64_t)tot[0];
+    if (s->elem_offsets && tot[0] <= s->elem_cap) s->elem_offsets[tot[0]] = (int64_t)tot[1];
+    if (a->totals) {
+      a->totals[2u * si] = tot[0];
+      a->totals[2u * si + 1u] = tot[1];
+    }
+  }
+}
+
+// ------------------------------------------------------------------ 3. offsets
+__global__ __launch_bounds__(kBlk) void k_el_offs(const ElemsArgs) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t el_lds[];
+  const KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  const uint32_t tiles = a->tiles, tile = a->tile;
+  const uint32_t si = blockIdx.x / tiles, ti = blockIdx.x - si * tiles;
+  const Lds l = carve(el_lds, tile);
+  const Sp x = make_sp(a, si);
+  const uint32_t t0 = ti * tile;
+  const uint32_t nrows = a->m - t0 < tile ? a->m - t0 : tile;
+  const uint64_t eb = a->tsum[blockIdx.x];
+  const uint64_t bb = a->tsum[(uint64_t)a->n_specs * tiles + blockIdx.x];
+  uint32_t u0 = 0, u1 = 0, u2 = 0;
+  scan_rows<false>(x, t0, nrows, eb, l, u0, u1, u2);
+  int64_t* const ro = x.s->row_offsets + t0;  // (row_offsets[m] is k_el_scan's)
+  for (uint32_t r = threadIdx.x; r < nrows; r += kBlk) ro[r] = (int64_t)l.eo[r];
+  int64_t* const eoffs = x.s->elem_offsets;
+  if (!eoffs) return;
+  // the tile's elements whose start is an entry of elem_offsets: e <= elem_cap
+  const Tile T{l.eo, l.src, nrows};
+  const uint64_t ecap = x.s->elem_cap;
+  const uint64_t e1 = l.eo[nrows];
+  const uint64_t lim = ecap < e1 ? ecap + 1u : e1;  // (at or below eb: none of them)
+  uint64_t carry = bb;
+  const uint32_t w = threadIdx.x >> 6;
+  for (uint64_t p0 = eb; p0 < lim; p0 += kPer * kBlk) {
+    uint64_t e[kPer], inc[kPer];
+    uint32_t r[kPer], len[kPer];
+    bool on[kPer];
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; ++i) {
+      e[i] = p0 + i * kBlk + threadIdx.x;
+      on[i] = e[i] < lim;
+      e[i] = on[i] ? e[i] : p0;  // (as k_el_len)
+    }
+    rows_at(T, e, r);
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; ++i) len[i] = elem_L(x, T.src[r[i]], (uint32_t)(e[i] - T.eo[r[i]]));
+    // kPer exclusive scans of 256 lengths, one after the other in element order, behind one pair of
+    // barriers: the waves' sums of every block go to LDS together
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; ++i) {
+      len[i] = on[i] ? clamp_len(x, len[i]) : 0u;
+      inc[i] = wave_incl_scan64((uint64_t)len[i]);
+    }
+    __syncthreads();  // (part may still be read from the pass before, or from scan_rows)
+    if ((threadIdx.x & 63u) == 63u) {
+#pragma unroll
+      for (uint32_t i = 0; i < kPer; ++i) l.part[i * (kBlk / 64) + w] = inc[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; ++i) {
+      uint64_t before = 0, all = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < kBlk / 64; ++j) {
+        const uint64_t s = l.part[i * (kBlk / 64) + j];
+        before += j < w ? s : 0ull;
+        all += s;
+      }
+      if (on[i]) eoffs[e[i]] = (int64_t)(carry + before + inc[i] - len[i]);
+      carry += all;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ 4. copy
+// The copy's place in the output: element e = [start, end) of values, in row `row` of the tile, its
+// first byte at `off` of the bytes' source
+struct Cur {
+  uint64_t e, start, end;
+  uint32_t row, off;
+};
+
+struct Span {
+  const int64_t* eoffs;  // the spec's elem_offsets
+  uint64_t e0, e1;       // the tile's elements below elem_cap
+};
+
+// the element of byte pos, eoffs[e0] <= pos < eoffs[e1]: the last e with eoffs[e] <= pos (elements
+// without a byte share their offset with the element after them)
+__device__ __forceinline__ Cur seek(const Sp& x, const Tile& T, const Span& sp, uint64_t pos, uint64_t from) {
+  // `from`: an element at or before pos's. A lane's next unit lies 4 KB after its last one, so the
+  // elements 1, 3 and 7 after `from` are tried before the rest of the span is searched: inside a long
+  // element, or a few short ones on, the search ends after a load or two
+  uint64_t lo = from, hi = sp.e1;
+#pragma unroll 1
+  for (uint64_t step = 1; step <= 4u; step <<= 1) {
+    const uint64_t probe = lo + step;
+    if (probe >= hi) break;
+    if ((uint64_t)sp.eoffs[probe] <= pos) {
+      lo = probe;
+    } else {
+      hi = probe;
+      break;
+    }
+  }
+  while (hi - lo > 1u) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if ((uint64_t)sp.eoffs[mid] <= pos) lo = mid;
+    else hi = mid;
+  }
+  Cur c;
+  c.e = lo;
+  c.start = (uint64_t)sp.eoffs[lo];
+  c.end = (uint64_t)sp.eoffs[lo + 1u];
+  c.row = row_at(T, lo);
+  c.off = elem_off(x, T.src[c.row], (uint32_t)(lo - T.eo[c.row]));
+  return c;
+}
+
+// on to the element of pos, at or after the cursor's; pos < eoffs[e1]
+__device__ __forceinline__ void walk_to(const Sp& x, const Tile& T, const Span& sp, Cur& c, uint64_t pos) {
+  if (pos < c.end) return;
+  do {
+    ++c.e;
+    c.start = c.end;
+    c.end = (uint64_t)sp.eoffs[c.e + 1u];
+  } while (pos >= c.end);
+  while (c.e >= T.eo[c.row + 1u]) ++c.row;
+  c.off = elem_off(x, T.src[c.row], (uint32_t)(c.e - T.eo[c.row]));
+}
+
+// byte j of the element at byte s of the input, zero past the input
+__device__ __forceinline__ uint32_t in_byte(const Sp& x, uint32_t s, uint64_t j) {
+  const uint64_t p = (uint64_t)s + j;
+  if (p >= x.a->in_bound) return 0u;
+  return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(x.in, (uint32_t)p, 0, 0);
+}
+
+// The output dword at positions pos .. pos + 3 (all below eoffs[e1]); the cursor: an element at or
+// before pos's, advanced to the element of pos + 3. A dword inside one element is built from two aligned
+// input dwords (one past the bound reads zeros without a memory access), any other byte by byte.
+__device__ __forceinline__ uint32_t u8_dword(const Sp& x, const Tile& T, const Span& sp, Cur& c, uint64_t pos) {
+  walk_to(x, T, sp, c, pos);
+  if (c.end - pos >= 4u) {
+    const uint64_t p = (uint64_t)c.off + (pos - c.start);
+    const bool ok = p < x.a->in_bound;
+    const uint32_t p0 = ok ? ((uint32_t)p & ~3u) : 0xfffffff8u;  // (in_bound <= 0xfffffff0: p0 + 4 does not wrap)
+    const uint32_t d0 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(x.in, p0, 0, 0);
+    const uint32_t d1 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(x.in, p0 + 4u, 0, 0);
+    return __builtin_amdgcn_alignbyte(d1, d0, (uint32_t)p & 3u);
+  }
+  uint32_t w = 0u;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; ++k) {
+    walk_to(x, T, sp, c, pos + k);
+    w |= in_byte(x, c.off, pos + k - c.start) << (8u * k);
+  }
+  return w;
+}
+
+// dynamic LDS as k_el_len
+__global__ __launch_bounds__(kBlk) void k_el_copy(const ElemsArgs) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t el_lds[];
+  const KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  const uint32_t tiles = a->tiles, S = a->split, tile = a->tile;
+  const uint32_t per_spec = tiles * S;
+  const uint32_t si = blockIdx.x / per_spec, rem = blockIdx.x - si * per_spec;
+  const uint32_t ti = rem / S, s = rem - ti * S;
+  const KSpec ks = &a->sp[si];
+  uint8_t* const out = ks->values;
+  const uint64_t ecap = ks->elem_offsets ? ks->elem_cap : 0ull;
+  const uint64_t cap = out ? ks->cap : 0ull;
+  const uint64_t eb = a->tsum[(uint64_t)si * tiles + ti];
+  const uint64_t bb = a->tsum[((uint64_t)a->n_specs + si) * tiles + ti];
+  // (uniform: nothing of this tile is described, or nothing of it fits)
+  if (eb >= ecap || bb >= cap) return;
+  const Lds l = carve(el_lds, tile);
+  const Sp x = make_sp(a, si);
+  const uint32_t t0 = ti * tile;
+  const uint32_t nrows = a->m - t0 < tile ? a->m - t0 : tile;
+  uint32_t u0 = 0, u1 = 0, u2 = 0;
+  scan_rows<false>(x, t0, nrows, eb, l, u0, u1, u2);
+  const Tile T{l.eo, l.src, nrows};
+  const uint64_t ee = l.eo[nrows];
+  const Span sp{ks->elem_offsets, eb, ee < ecap ? ee : ecap};
+  if (sp.e1 <= sp.e0) return;
+  // the tile's span of the output: bytes up to the first 16-byte boundary of the output's address,
+  // whole units, the rest
+  const uint64_t p0 = bb, pe = (uint64_t)sp.eoffs[sp.e1];
+  const uint64_t p1 = pe < cap ? pe : cap;
+  if (p0 >= p1) return;
+  const uint64_t addr = (uint64_t)(uintptr_t)out + p0;
+  uint64_t head = (16u - (uint32_t)(addr & 15u)) & 15u;
+  if (head > p1 - p0) head = p1 - p0;
+  const uint64_t h0 = p0 + head;
+  const uint64_t units = (p1 - h0) >> 4;
+  const uint64_t tail0 = h0 + (units << 4);
+  const uint32_t tid = threadIdx.x;
+  if (s == 0u) {
+    const uint32_t ends = (uint32_t)head + (uint32_t)(p1 - tail0);  // < 32
+    if (tid < ends) {
+      const uint64_t pos = tid < (uint32_t)head ? p0 + tid : tail0 + (tid - (uint32_t)head);
+      const Cur c = seek(x, T, sp, pos, sp.e0);
+      out[pos] = (uint8_t)in_byte(x, c.off, pos - c.start);
+    }
+  }
+  // the s-th of S runs of whole chunks
+  const uint64_t chunks = (units + kElemsChunk - 1u) / kElemsChunk;
+  const uint64_t ua = chunks * s / S * kElemsChunk;
+  uint64_t ub = chunks * (s + 1u) / S * kElemsChunk;
+  if (ub > units) ub = units;
+  Cur c{sp.e0, 0ull, 0ull, 0u, 0u};  // (end 0: the first unit seeks)
+#pragma unroll 1
+  for (uint64_t u = ua + tid; u < ub; u += kBlk) {
+    const uint64_t pos = h0 + (u << 4);
+    if (pos >= c.end) c = seek(x, T, sp, pos, c.e);  // (else still inside the element of the unit before)
+    el_u32x4 o;
+    o.x = u8_dword(x, T, sp, c, pos);
+    o.y = u8_dword(x, T, sp, c, pos + 4u);
+    o.z = u8_dword(x, T, sp, c, pos + 8u);
+    o.w = u8_dword(x, T, sp, c, pos + 12u);
+    *reinterpret_cast<el_u32x4*>(out + pos) = o;
+  }
+}
+
+}  // namespace
+
+hipError_t launch_elems(const ElemsArgs& a, hipStream_t st) {
+  const uint32_t per_spec = a.n_specs * a.tiles;
+  const size_t lds = elems_lds_bytes(a.tile);
+  hipLaunchKernelGGL(k_el_len, dim3(per_spec), dim3(kBlk), lds, st, a);
+  hipLaunchKernelGGL(k_el_scan, dim3(a.n_specs), dim3(kElemsScanThreads), 0, st, a);
+  hipLaunchKernelGGL(k_el_offs, dim3(per_spec), dim3(kBlk), lds, st, a);
+  if (a.split) hipLaunchKernelGGL(k_el_copy, dim3(per_spec * a.split), dim3(kBlk), lds, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace tfrg

@@ -140,6 +140,24 @@ RAGGED_TILE_DEFAULT = 1024
 RAGGED_SCAN_THREADS = 1024
 
 
+class TfrgElemsSpec(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("max_elems", C.c_uint32),
+        ("max_len", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("elem_cap", C.c_uint64),
+        ("cap", C.c_uint64),
+        ("values", C.c_void_p),
+        ("elem_offsets", C.c_void_p),
+        ("row_offsets", C.c_void_p),
+    ]
+
+
+ELEMS_MAX_SPECS = 32
+ELEMS_SCAN_THREADS = 1024  # (csrc/tfrg_elems.h: the tile sums its scan kernel takes per pass)
+
+
 class TfrgSelectTerm(C.Structure):
     _fields_ = [
         ("slot", C.c_uint32),
@@ -264,6 +282,8 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_result_ragged_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgRaggedSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_ctx_set_ragged_tile": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "tfrg_result_ragged_elems": (C.c_int, [C.c_void_p, C.POINTER(TfrgElemsSpec), C.c_uint32, C.c_void_p, C.c_uint32,
+                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_result_select_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgSelectTerm), C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -524,6 +524,15 @@ class HipDecoder:
 
         return R.decoder_ragged(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
 
+    def ragged_elements(self, specs, *, rows=None, capacity=None, out=None, stream: int | None = None):
+        """Every element of the ``bytes_list``s of the last decode as ``(values, elem_offsets,
+        row_offsets)`` torch tensors on this decoder's device, one triple per
+        ``tfr_reader.ragged.RaggedElements`` spec, for every record or for the list ``rows``
+        (tfrg_result_ragged_elems); see ``tfr_reader.ragged.decoder_ragged_elements``."""
+        from tfr_reader import ragged as R  # noqa: PLC0415
+
+        return R.decoder_ragged_elements(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
+
     def ragged_minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False, capacity=None,
                            where=None):
         """One epoch of shuffled ``batch_size``-row ``RaggedBatch``es over the last decode (``where``:
@@ -827,6 +836,14 @@ class BatchResult:
         from tfr_reader import ragged as R  # noqa: PLC0415
 
         return R.batch_ragged(self, specs, rows)
+
+    def ragged_elements(self, specs, rows=None):
+        """``(values, elem_offsets, row_offsets)`` numpy arrays of ``tfr_reader.ragged.RaggedElements``
+        specs from the fetched columns (the host counterpart of ``HipDecoder.ragged_elements``): an
+        ``ElementsBatch`` with ``.totals`` and ``.stats``. ``rows``: as for ``ragged``."""
+        from tfr_reader import ragged as R  # noqa: PLC0415
+
+        return R.batch_ragged_elements(self, specs, rows)
 
     def select(self, where, rows=None, row0: int = 0):
         """The candidates that pass ``where`` (``tfr_reader.select.Term``s), from the fetched columns
