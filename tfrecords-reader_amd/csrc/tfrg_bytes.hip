@@ -10,6 +10,7 @@
 // The element count nb is device-resident (kind_totals[1], written by k_spine), so neither pass
 // needs a host round trip.
 #include <hip/hip_runtime.h>
+#include "tfrg_dev.h"
 #include "tfrg_internal.h"
 #include "../../include/tfrg_status.h"
 
@@ -20,15 +21,6 @@ constexpr int kBsItems = 16;
 constexpr uint32_t kBsTile = kBsBlock * kBsItems;  // elements per scan tile
 constexpr uint32_t kBigElem = 128;                 // longer elements: one wave each
 constexpr uint64_t kLbFlagShift = 62;              // look-back word: flag (1 total, 2 prefix) << 62 | value
-
-__device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v, uint32_t lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(v, d, 64);
-    if (lane >= (uint32_t)d) v += y;
-  }
-  return v;
-}
 
 __global__ __launch_bounds__(kBsBlock) void k_bytes_scan(DevBytes d) {
   __shared__ uint32_t s_ticket;
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(kBsBlock) void k_bytes_scan(DevBytes d) {
       for (int j = 0; j < kBsItems; ++j)
         if (v[j] > kBigElem) d.big_list[b0++] = (uint32_t)(i0 + j);
     }
-    const uint64_t incl = wave_incl_scan_u64(sum, lane);
+    const uint64_t incl = wave_incl_scan(sum);
     if (lane == 63) s_w[wid] = incl;
     __syncthreads();
     uint64_t pre = 0, tot = 0;

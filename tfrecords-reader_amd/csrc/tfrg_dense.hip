@@ -20,8 +20,8 @@
 // bounded to the batch: a view that runs past it reads zeros.
 //
 // k_dense_rows (tfrg_result_dense_rows) is the same kernel behind one level of indirection:
-// the output has m rows, and row k is record g = rows[k] - row0 (rec_of). The row list is a per-lane
-// vector load and one phase of its own, ahead of the row splits. A k whose g is not in [0, n) is a
+// the output has m rows, and row k is record g = rows[k] - row0 (the row rule of tfrg_rows.h). The
+// row list is a per-lane vector load and one phase of its own, ahead of the row splits. A k whose g is not in [0, n) is a
 // skipped row: nothing indexed by g is loaded for it (it reads record 0, whose columns every
 // non-empty result has, as a record without a value reads element 0), none of its output elements
 // and no lengths[k] are stored, and it counts in skipped[spec] alone. A 16-byte unit with a skipped
@@ -29,8 +29,8 @@
 #include <hip/hip_runtime.h>
 
 #include "tfrg_dense.h"
-#include "tfrg_dev.h"
 #include "tfrg_internal.h"
+#include "tfrg_rows.h"
 
 namespace tfrg {
 namespace {
@@ -56,36 +56,14 @@ struct Sp {
   uint64_t base;       // slot_base[slot]
   uint32_t W;
   __amdgpu_buffer_rsrc_t in;
-  // the row list (ROWS only): entry k is the dword at rows + (k << rsh), and for int64 entries the
-  // dword rhi bytes after it (rhi 0: an int32 entry, whose second load repeats the first)
-  const uint8_t* rows;
-  int64_t row0;
-  uint32_t rsh, rhi;
+  RowList rl;  // (ROWS only)
 };
 
-// The record of output row r. Without a row list it is r. With one, r < m and the record is
-// rows[r] - row0; ok: that is in [0, n) (compared before the subtraction, whose unsigned result is
-// then the true difference: no entry, INT64_MIN and INT64_MAX included, wraps into range).
-struct Rec {
-  uint32_t g;
-  uint32_t ok;  // 0 / 1, in a vector register: a lane mask per row in flight would cost two scalar ones
-};
-
+// The record of output row r: r itself without a row list; with one, r < m and the row rule decides
 template <bool ROWS>
-__device__ __forceinline__ Rec rec_of(const Sp& x, uint32_t r) {
-  if constexpr (!ROWS) {
-    return Rec{r, 1u};
-  } else {
-    const uint8_t* const p = x.rows + ((uint64_t)r << x.rsh);
-    const uint32_t lo = *reinterpret_cast<const uint32_t*>(p);
-    const uint32_t hi = *reinterpret_cast<const uint32_t*>(p + x.rhi);
-    const int64_t v = x.rhi ? (int64_t)(((uint64_t)hi << 32) | lo) : (int64_t)(int32_t)lo;
-    const uint64_t d = (uint64_t)v - (uint64_t)x.row0;
-    const bool ok = v >= x.row0 && d < (uint64_t)x.a->n;
-    uint32_t okv = ok ? 1u : 0u;
-    asm("" : "+v"(okv));  // (kept as a value: see Rec)
-    return Rec{ok ? (uint32_t)d : 0u, okv};
-  }
+__device__ __forceinline__ Rec row_rec(const Sp& x, uint32_t r) {
+  if constexpr (!ROWS) return Rec{r, 1u};
+  else return rec_of(x.a, x.rl.row0, row_entry(x.rl, r));
 }
 
 // first value index and value count of record g (g < n)
@@ -180,7 +158,7 @@ __device__ __forceinline__ uint32_t values_from(const Sp& x, Tally& t, uint32_t 
       j = wrap ? 0u : j;
     }
 #pragma unroll
-    for (int k = 0; k < K; ++k) q[k] = rec_of<true>(x, rr[k]);
+    for (int k = 0; k < K; ++k) q[k] = row_rec<true>(x, rr[k]);
 #pragma unroll
     for (int k = 0; k < K; ++k) row_of(x, q[k], e[k], c[k]);
 #pragma unroll
@@ -224,7 +202,7 @@ __device__ __forceinline__ BRow brow_of(const Sp& x, const Rec& q) {
 
 template <bool ROWS>
 __device__ __forceinline__ BRow brow_of(const Sp& x, uint32_t r, uint32_t& ok) {
-  const Rec q = rec_of<ROWS>(x, r);
+  const Rec q = row_rec<ROWS>(x, r);
   ok = q.ok;
   return brow_of(x, q);
 }
@@ -263,7 +241,7 @@ __device__ __forceinline__ uint32_t u8_dwords4(const Sp& x, Tally& t, uint32_t r
     j = wrap ? 0u : j;
   }
 #pragma unroll
-  for (int k = 0; k < K; ++k) q[k] = rec_of<ROWS>(x, rr[k]);
+  for (int k = 0; k < K; ++k) q[k] = row_rec<ROWS>(x, rr[k]);
 #pragma unroll
   for (int k = 0; k < K; ++k) bb[k] = brow_of(x, q[k]);
   uint32_t d0[K], d1[K];
@@ -463,12 +441,6 @@ __device__ __forceinline__ void dense_spec(const Sp& x, Tally& t, uint32_t wg) {
   }
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
-}
-
 template <bool NT, bool ROWS>
 __device__ __forceinline__ void dense_body() {
   const KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();  // (the only argument)
@@ -476,22 +448,15 @@ __device__ __forceinline__ void dense_body() {
   uint32_t si = 0;
   while (si + 1u < a->n_specs && a->sp[si + 1u].blk0 <= blockIdx.x) ++si;
   const KSpec s = &a->sp[si];
-  const uint32_t* const info = a->info;
-  const uint64_t placed = ((uint64_t)info[kInfoPlacedHi] << 32) | info[kInfoPlacedLo];
   const uint32_t slot = s->slot;
   Sp x;
   x.a = a;
   x.s = s;
   x.W = s->width;
   x.base = a->slot_base[slot];
-  x.rs = (slot < 64u && ((placed >> slot) & 1ull)) ? nullptr : a->rs + (uint64_t)slot * ((uint64_t)a->n + 1u);
-  x.in = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a->in), (short)0, (int)a->in_bound, 0x00020000);
-  if constexpr (ROWS) {
-    x.rows = static_cast<const uint8_t*>(a->rows);
-    x.row0 = a->row0;
-    x.rsh = a->rows64 ? 3u : 2u;
-    x.rhi = a->rows64 ? 4u : 0u;
-  }
+  x.rs = slot_splits(a, slot);
+  x.in = bytes_source(a);
+  if constexpr (ROWS) x.rl = make_row_list(a);
   const uint32_t wg = blockIdx.x - s->blk0;
   Tally t;
   switch (s->dtype) {
@@ -502,21 +467,13 @@ __device__ __forceinline__ void dense_body() {
   }
   if constexpr (ROWS) {
     if (a->skipped) {
-      const uint32_t sk = wave_sum(t.skip);
+      const uint32_t sk = wave_sum32(t.skip);
       if ((threadIdx.x & 63u) == 0u && sk) atomicAdd(a->skipped + si, sk);
     }
   }
   uint32_t* const stats = a->stats;
   if (!stats) return;
-  // one atomic per wave and counter at the most
-  const uint32_t tr = wave_sum(t.trunc), pd = wave_sum(t.pad), ze = wave_sum(t.zero), mu = wave_sum(t.multi);
-  if ((threadIdx.x & 63u) == 0u) {
-    uint32_t* st = stats + 4u * si;
-    if (tr) atomicAdd(st + 0, tr);
-    if (pd) atomicAdd(st + 1, pd);
-    if (ze) atomicAdd(st + 2, ze);
-    if (mu) atomicAdd(st + 3, mu);
-  }
+  add_stats4(stats, si, t.trunc, t.pad, t.zero, t.multi);
 }
 
 template <bool NT>

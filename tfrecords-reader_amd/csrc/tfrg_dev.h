@@ -1,7 +1,8 @@
 // tfrg_dev.h — the device helpers that more than one kernel file uses, each defined once: byte and
-// word primitives, the readfirstlane wrappers, the nt store, and the bookkeeping that ends an
-// optimistic decode (all_placed_finish). Included by tfrg_kernels.hip, tfrg_scan.hip, tfrg_tpl.hip and
-// tfrg_dense.hip.
+// word primitives, the readfirstlane wrappers, the wave sums and the wave and workgroup scans, the nt
+// store, and the bookkeeping that ends an optimistic decode (all_placed_finish). Included by
+// tfrg_kernels.hip, tfrg_scan.hip, tfrg_tpl.hip, tfrg_bytes.hip, tfrg_frame.hip and, through
+// tfrg_rows.h, by the row-list passes (tfrg_dense.hip, tfrg_ragged.hip, tfrg_elems.hip, tfrg_select.hip).
 #pragma once
 #include "tfrg_internal.h"
 #include "../../include/tfrg_status.h"
@@ -60,6 +61,53 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, uint32_t) {
   s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x142, 0xa, 0xf, false);            // row_bcast:15
   s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x143, 0xc, 0xf, false);            // row_bcast:31
   return s;
+}
+
+// Sums over the wave (every lane active) by __shfl_down: lane 0 holds the total. (tfrg_tpl.hip's
+// wave_sum and tfrg_kernels.hip's wave_sum_u32 are other algorithms, which leave it in every lane.)
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+  return v;
+}
+
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += (uint64_t)__shfl_down((unsigned long long)v, d, 64);
+  return v;
+}
+
+// Inclusive prefix sum over the wave by the __shfl_up ladder, for uint32_t and uint64_t (the scans
+// that run once per tile or pass; wave_incl_scan_u32 above is the DPP one of the decode's hot path)
+template <class T>
+__device__ __forceinline__ T wave_incl_scan(T v) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T u = (T)__shfl_up(v, o, 64);
+    if (lane >= (uint32_t)o) v += u;
+  }
+  return v;
+}
+
+// exclusive scan of v over the workgroup (W waves, every thread calls; part: W words of LDS);
+// *total: the workgroup's sum
+template <int W, class T>
+__device__ __forceinline__ T block_excl_scan(T v, T* part, T* total) {
+  const T inc = wave_incl_scan(v);
+  const uint32_t w = threadIdx.x >> 6;
+  __syncthreads();  // (part may still be read from a previous call)
+  if ((threadIdx.x & 63u) == 63u) part[w] = inc;
+  __syncthreads();
+  T before = 0, all = 0;
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    const T s = part[i];
+    before += (uint32_t)i < w ? s : (T)0;
+    all += s;
+  }
+  *total = all;
+  return before + inc - v;
 }
 
 // single value stored in the loc word by the count pass

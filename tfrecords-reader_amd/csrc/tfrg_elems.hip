@@ -2,7 +2,8 @@
 // g = entry(k) - row0) and every requested bytes_list slot, EVERY element of the rows' lists: the
 // elements' bytes back to back (values), the E + 1 offsets of the elements in them (elem_offsets) and
 // the m + 1 offsets of the rows in elements (row_offsets). Four launches on the decode's stream, no
-// workgroup ever waiting on another (the shape of k_rg_len / k_rg_scan / k_rg_gather in tfrg_ragged.hip):
+// workgroup ever waiting on another (the shape of k_rg_len / k_rg_scan / k_rg_gather in tfrg_ragged.hip;
+// the row rule, the scans and the row table in LDS are those of tfrg_rows.h):
 //
 //   k_el_len   per (spec, tile of `tile` rows): the rows' element counts scanned into LDS, then the
 //              tile's elements shared by the lanes (lane t takes tile-local elements t, t + 256, ...
@@ -39,9 +40,9 @@
 // record 0 and drops it), and it counts in the fourth counter alone.
 #include <hip/hip_runtime.h>
 
-#include "tfrg_dev.h"
 #include "tfrg_elems.h"
 #include "tfrg_internal.h"
+#include "tfrg_rows.h"
 
 namespace tfrg {
 namespace {
@@ -63,52 +64,23 @@ struct Sp {
   uint32_t max_elems, max_len;
   bool by_end;         // the element of record g lies at end32[g] + const_off
   __amdgpu_buffer_rsrc_t in;
-  const uint8_t* rows;
-  int64_t row0;
-  uint32_t rsh, rhi;
+  RowList rl;  // (rows null: entry k is k)
 };
 
 __device__ __forceinline__ Sp make_sp(KArgs a, uint32_t si) {
   const KSpec s = &a->sp[si];
-  const uint32_t* const info = a->info;
-  const uint64_t placed = ((uint64_t)info[kInfoPlacedHi] << 32) | info[kInfoPlacedLo];
   const uint32_t slot = s->slot;
   Sp x;
   x.a = a;
   x.s = s;
   x.base = a->slot_base[slot];
-  x.rs = (slot < 64u && ((placed >> slot) & 1ull)) ? nullptr : a->rs + (uint64_t)slot * ((uint64_t)a->n + 1u);
+  x.rs = slot_splits(a, slot);
   x.max_elems = s->max_elems;
   x.max_len = s->max_len;
   x.by_end = !a->b_off64 && s->const_off != kElemsOffStored;
-  x.in = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a->in), (short)0, (int)a->in_bound, 0x00020000);
-  x.rows = static_cast<const uint8_t*>(a->rows);
-  x.row0 = a->row0;
-  x.rsh = a->rows64 ? 3u : 2u;
-  x.rhi = a->rows64 ? 4u : 0u;
+  x.in = bytes_source(a);
+  x.rl = make_row_list(a);
   return x;
-}
-
-// The record of row k < m (tfrg_dense.hip rec_of's rule: compared before the subtraction, whose
-// unsigned result is then the true difference, so no entry wraps into range)
-struct Rec {
-  uint32_t g;
-  uint32_t ok;  // 0 / 1, in a vector register
-};
-
-__device__ __forceinline__ Rec rec_of(const Sp& x, uint32_t k) {
-  int64_t v = (int64_t)k;
-  if (x.rows) {
-    const uint8_t* const p = x.rows + ((uint64_t)k << x.rsh);
-    const uint32_t lo = *reinterpret_cast<const uint32_t*>(p);
-    const uint32_t hi = *reinterpret_cast<const uint32_t*>(p + x.rhi);
-    v = x.rhi ? (int64_t)(((uint64_t)hi << 32) | lo) : (int64_t)(int32_t)lo;
-  }
-  const uint64_t d = (uint64_t)v - (uint64_t)x.row0;
-  const bool ok = v >= x.row0 && d < (uint64_t)x.a->n;
-  uint32_t okv = ok ? 1u : 0u;
-  asm("" : "+v"(okv));  // (kept as a value)
-  return Rec{ok ? (uint32_t)d : 0u, okv};
 }
 
 // One row of the output: its first `cnt` elements, element j being number src + j of the slot's column
@@ -121,7 +93,7 @@ struct Row {
 };
 
 __device__ __forceinline__ Row row_of(const Sp& x, uint32_t k) {
-  const Rec q = rec_of(x, k);
+  const Rec q = rec_of(x.a, x.rl.row0, x.rl.rows ? row_entry(x.rl, k) : (int64_t)k);
   uint32_t lo = q.g, c = 1u;
   if (x.rs) {
     lo = x.rs[q.g];
@@ -158,48 +130,6 @@ __device__ __forceinline__ uint32_t elem_off(const Sp& x, uint32_t src, uint32_t
   return x.by_end ? x.a->end32[src] + (uint32_t)x.s->const_off : x.a->b_off[es];
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (uint64_t)__shfl_down((unsigned long long)v, d, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t u = (uint64_t)__shfl_up((unsigned long long)v, o, 64);
-    if (lane >= (uint32_t)o) v += u;
-  }
-  return v;
-}
-
-// exclusive scan of v over the workgroup (W waves, every thread calls); *total: the workgroup's sum
-// (tfrg_ragged.hip's block_excl_scan64)
-template <int W>
-__device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t* part, uint64_t* total) {
-  const uint64_t inc = wave_incl_scan64(v);
-  const uint32_t w = threadIdx.x >> 6;
-  __syncthreads();  // (part may still be read from a previous call)
-  if ((threadIdx.x & 63u) == 63u) part[w] = inc;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (int i = 0; i < W; ++i) {
-    const uint64_t s = part[i];
-    before += (uint32_t)i < w ? s : 0ull;
-    all += s;
-  }
-  *total = all;
-  return before + inc - v;
-}
-
 // The tile in LDS: eo[r] for r <= nrows are the absolute element offsets of its rows (eo[nrows]: of the
 // row after the tile), src[r] the row's source.
 struct Tile {
@@ -207,33 +137,6 @@ struct Tile {
   const uint32_t* src;
   uint32_t nrows;
 };
-
-// dynamic LDS of the three kernels with a row table: eo [tile + 2] u64, src [tile] u32, part [16] u64
-struct Lds {
-  uint64_t* eo;
-  uint32_t* src;
-  uint64_t* part;
-};
-
-__device__ __forceinline__ Lds carve(uint8_t* lds, uint32_t tile) {
-  Lds l;
-  l.eo = reinterpret_cast<uint64_t*>(lds);
-  l.src = reinterpret_cast<uint32_t*>(l.eo + tile + 2u);
-  l.part = reinterpret_cast<uint64_t*>(l.src + tile);
-  return l;
-}
-
-// the row of element e, eo[0] <= e < eo[nrows]: the last r with eo[r] <= e (rows without an element
-// share their offset with the row after them)
-__device__ __forceinline__ uint32_t row_at(const Tile& T, uint64_t e) {
-  uint32_t lo = 0, hi = T.nrows;
-  while (hi - lo > 1u) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (T.eo[mid] <= e) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // Elements per lane and pass in k_el_len and k_el_offs: the lane's kPer elements (t, t + 256, ... of the
 // pass) are searched in lockstep and their lengths loaded together, so a pass waits for one LDS chain
@@ -256,7 +159,7 @@ __device__ __forceinline__ void rows_at(const Tile& T, const uint64_t (&e)[kPer]
 // the tile's rows into LDS: element counts scanned from the tile's base, sources. TALLY: the three
 // per-row counters into the lane's tallies.
 template <bool TALLY>
-__device__ __forceinline__ void scan_rows(const Sp& x, uint32_t t0, uint32_t nrows, uint64_t base, const Lds& l,
+__device__ __forceinline__ void scan_rows(const Sp& x, uint32_t t0, uint32_t nrows, uint64_t base, const RowTable& l,
                                           uint32_t& rtrunc, uint32_t& empty, uint32_t& skip) {
   uint64_t carry = base;
   for (uint32_t r0 = 0; r0 < nrows; r0 += kBlk) {
@@ -272,31 +175,32 @@ __device__ __forceinline__ void scan_rows(const Sp& x, uint32_t t0, uint32_t nro
       }
     }
     uint64_t total;
-    const uint64_t ex = block_excl_scan64<kBlk / 64>((uint64_t)w.cnt, l.part, &total);
+    const uint64_t ex = block_excl_scan<kBlk / 64>((uint64_t)w.cnt, l.part, &total);
     if (r < nrows) {
-      l.eo[r] = carry + ex;
+      l.offs[r] = carry + ex;
       l.src[r] = w.src;
     }
     carry += total;
   }
-  if (threadIdx.x == 0) l.eo[nrows] = carry;
+  if (threadIdx.x == 0) l.offs[nrows] = carry;
   __syncthreads();
 }
 
 // ------------------------------------------------------------------ 1. counts and byte sums
+// dynamic LDS: the row table of tfrg_rows.h with part [16] u64 (elems_lds_bytes sizes it)
 __global__ __launch_bounds__(kBlk) void k_el_len(const ElemsArgs) {
   extern __shared__ __attribute__((aligned(16))) uint8_t el_lds[];
   const KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();  // (the only argument)
   const uint32_t tiles = a->tiles, tile = a->tile;
   const uint32_t si = blockIdx.x / tiles, ti = blockIdx.x - si * tiles;
-  const Lds l = carve(el_lds, tile);
+  const RowTable l = carve_row_table(el_lds, tile);
   const Sp x = make_sp(a, si);
   const uint32_t t0 = ti * tile;
   const uint32_t nrows = a->m - t0 < tile ? a->m - t0 : tile;
   uint32_t rtrunc = 0, etrunc = 0, empty = 0, skip = 0;
   scan_rows<true>(x, t0, nrows, 0ull, l, rtrunc, empty, skip);
-  const Tile T{l.eo, l.src, nrows};
-  const uint64_t et = l.eo[nrows];
+  const Tile T{l.offs, l.src, nrows};
+  const uint64_t et = l.offs[nrows];
   uint64_t sum = 0;
   for (uint64_t p0 = 0; p0 < et; p0 += kPer * kBlk) {
     uint64_t e[kPer];
@@ -331,15 +235,7 @@ __global__ __launch_bounds__(kBlk) void k_el_len(const ElemsArgs) {
   }
   uint32_t* const stats = a->stats;
   if (!stats) return;
-  // one atomic per wave and counter at the most
-  const uint32_t rt = wave_sum(rtrunc), tr = wave_sum(etrunc), em = wave_sum(empty), sk = wave_sum(skip);
-  if ((threadIdx.x & 63u) == 0u) {
-    uint32_t* st = stats + 4u * si;
-    if (rt) atomicAdd(st + 0, rt);
-    if (tr) atomicAdd(st + 1, tr);
-    if (em) atomicAdd(st + 2, em);
-    if (sk) atomicAdd(st + 3, sk);
-  }
+  add_stats4(stats, si, rtrunc, etrunc, empty, skip);
 }
 
 // ------------------------------------------------------------------ 2. tile scan
@@ -354,14 +250,7 @@ __global__ __launch_bounds__(kElemsScanThreads) void k_el_scan(const ElemsArgs) 
   for (uint32_t w = 0; w < 2u; ++w) {
     uint64_t* const tsum = a->tsum + ((uint64_t)w * a->n_specs + si) * tiles;
     uint64_t carry = 0;
-    for (uint32_t b0 = 0; b0 < tiles; b0 += kElemsScanThreads) {
-      const uint32_t i = b0 + threadIdx.x;
-      const uint64_t v = i < tiles ? tsum[i] : 0ull;
-      uint64_t total;
-      const uint64_t ex = block_excl_scan64<kElemsScanThreads / 64>(v, part, &total);
-      if (i < tiles) tsum[i] = carry + ex;
-      carry += total;
-    }
+    for (uint32_t b0 = 0; b0 < tiles; b0 += kElemsScanThreads) carry = scan_tile_sums<kElemsScanThreads>(tsum, tiles, b0, carry, part);
     tot[w] = carry;
   }
   if (threadIdx.x == 0) {
@@ -381,7 +270,7 @@ __global__ __launch_bounds__(kBlk) void k_el_offs(const ElemsArgs) {
   const KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
   const uint32_t tiles = a->tiles, tile = a->tile;
   const uint32_t si = blockIdx.x / tiles, ti = blockIdx.x - si * tiles;
-  const Lds l = carve(el_lds, tile);
+  const RowTable l = carve_row_table(el_lds, tile);
   const Sp x = make_sp(a, si);
   const uint32_t t0 = ti * tile;
   const uint32_t nrows = a->m - t0 < tile ? a->m - t0 : tile;
@@ -390,13 +279,13 @@ __global__ __launch_bounds__(kBlk) void k_el_offs(const ElemsArgs) {
   uint32_t u0 = 0, u1 = 0, u2 = 0;
   scan_rows<false>(x, t0, nrows, eb, l, u0, u1, u2);
   int64_t* const ro = x.s->row_offsets + t0;  // (row_offsets[m] is k_el_scan's)
-  for (uint32_t r = threadIdx.x; r < nrows; r += kBlk) ro[r] = (int64_t)l.eo[r];
+  for (uint32_t r = threadIdx.x; r < nrows; r += kBlk) ro[r] = (int64_t)l.offs[r];
   int64_t* const eoffs = x.s->elem_offsets;
   if (!eoffs) return;
   // the tile's elements whose start is an entry of elem_offsets: e <= elem_cap
-  const Tile T{l.eo, l.src, nrows};
+  const Tile T{l.offs, l.src, nrows};
   const uint64_t ecap = x.s->elem_cap;
-  const uint64_t e1 = l.eo[nrows];
+  const uint64_t e1 = l.offs[nrows];
   const uint64_t lim = ecap < e1 ? ecap + 1u : e1;  // (at or below eb: none of them)
   uint64_t carry = bb;
   const uint32_t w = threadIdx.x >> 6;
@@ -418,7 +307,7 @@ __global__ __launch_bounds__(kBlk) void k_el_offs(const ElemsArgs) {
 #pragma unroll
     for (uint32_t i = 0; i < kPer; ++i) {
       len[i] = on[i] ? clamp_len(x, len[i]) : 0u;
-      inc[i] = wave_incl_scan64((uint64_t)len[i]);
+      inc[i] = wave_incl_scan((uint64_t)len[i]);
     }
     __syncthreads();  // (part may still be read from the pass before, or from scan_rows)
     if ((threadIdx.x & 63u) == 63u) {
@@ -481,7 +370,7 @@ __device__ __forceinline__ Cur seek(const Sp& x, const Tile& T, const Span& sp, 
   c.e = lo;
   c.start = (uint64_t)sp.eoffs[lo];
   c.end = (uint64_t)sp.eoffs[lo + 1u];
-  c.row = row_at(T, lo);
+  c.row = row_at(T.eo, T.nrows, lo);
   c.off = elem_off(x, T.src[c.row], (uint32_t)(lo - T.eo[c.row]));
   return c;
 }
@@ -543,14 +432,14 @@ __global__ __launch_bounds__(kBlk) void k_el_copy(const ElemsArgs) {
   const uint64_t bb = a->tsum[((uint64_t)a->n_specs + si) * tiles + ti];
   // (uniform: nothing of this tile is described, or nothing of it fits)
   if (eb >= ecap || bb >= cap) return;
-  const Lds l = carve(el_lds, tile);
+  const RowTable l = carve_row_table(el_lds, tile);
   const Sp x = make_sp(a, si);
   const uint32_t t0 = ti * tile;
   const uint32_t nrows = a->m - t0 < tile ? a->m - t0 : tile;
   uint32_t u0 = 0, u1 = 0, u2 = 0;
   scan_rows<false>(x, t0, nrows, eb, l, u0, u1, u2);
-  const Tile T{l.eo, l.src, nrows};
-  const uint64_t ee = l.eo[nrows];
+  const Tile T{l.offs, l.src, nrows};
+  const uint64_t ee = l.offs[nrows];
   const Span sp{ks->elem_offsets, eb, ee < ecap ? ee : ecap};
   if (sp.e1 <= sp.e0) return;
   // the tile's span of the output: bytes up to the first 16-byte boundary of the output's address,

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 
+#include "tfrg_dev.h"
 #include "tfrg_frame.h"
 #include "tfrg_internal.h"
 
@@ -69,34 +70,6 @@ __global__ __launch_bounds__(kBlk) void k_fr_phase(const FrTab T, uint32_t r, ui
   } else {
     if (T.summ[kFsMism + r]) fr_repair_init(T, k);
   }
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(v, o, 64);
-    if (lane >= (uint32_t)o) v += u;
-  }
-  return v;
-}
-// exclusive scan of v over the workgroup (W waves, every thread calls); *total: the workgroup's sum
-template <int W>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* part, uint32_t* total) {
-  const uint32_t inc = wave_incl_scan(v);
-  const uint32_t w = threadIdx.x >> 6;
-  __syncthreads();  // (part may still be read from a previous call)
-  if ((threadIdx.x & 63u) == 63u) part[w] = inc;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int i = 0; i < W; ++i) {
-    const uint32_t s = part[i];
-    before += (uint32_t)i < w ? s : 0u;
-    all += s;
-  }
-  *total = all;
-  return before + inc - v;
 }
 
 __global__ __launch_bounds__(kBlk) void k_fr_sum(const FrTab T) {

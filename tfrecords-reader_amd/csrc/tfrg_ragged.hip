@@ -1,7 +1,8 @@
 // tfrg_ragged.hip — the kernels behind tfrg_result_ragged_rows: for a list of m rows (row k is record
 // g = entry(k) - row0) and every requested output, the packed values of the rows back to back and the
 // m + 1 offsets (cu_seqlens) of the rows in them. Three launches on the decode's stream, no workgroup
-// ever waiting on another (the shape of k_fr_sum / k_fr_scan / k_fr_write in tfrg_frame.hip):
+// ever waiting on another (the shape of k_fr_sum / k_fr_scan / k_fr_write in tfrg_frame.hip; the row
+// rule, the scans and the row table in LDS are those of tfrg_rows.h):
 //
 //   k_rg_len     per (spec, tile of `tile` rows): the rows' lengths, their u64 sum into the scratch
 //                tsum[spec][tile], and the four counters (per-lane tallies, one wave reduction, at most
@@ -24,14 +25,14 @@
 // a buffer resource bounded to the batch: a view that runs past it reads zeros.
 //
 // A row whose g is not in [0, n) is an empty row: nothing indexed by g is loaded for it (it reads
-// record 0 and drops it; validity is a 0 / 1 value in a vector register, see rec_of in tfrg_dense.hip),
+// record 0 and drops it; validity is a 0 / 1 value in a vector register, see the row rule in tfrg_rows.h),
 // and it counts in the fourth counter alone.
 #include <hip/hip_runtime.h>
 
 #include "tfrg_dense.h"
-#include "tfrg_dev.h"
 #include "tfrg_internal.h"
 #include "tfrg_ragged.h"
+#include "tfrg_rows.h"
 
 namespace tfrg {
 namespace {
@@ -53,52 +54,21 @@ struct Sp {
   uint64_t base;       // slot_base[slot]
   uint32_t max_len;
   __amdgpu_buffer_rsrc_t in;
-  // the row list: entry k is the dword at rows + (k << rsh), and for int64 entries the dword rhi bytes
-  // after it; null: entry k is k
-  const uint8_t* rows;
-  int64_t row0;
-  uint32_t rsh, rhi;
+  RowList rl;  // (rows null: entry k is k)
 };
 
 __device__ __forceinline__ Sp make_sp(KArgs a, uint32_t si) {
   const KSpec s = &a->sp[si];
-  const uint32_t* const info = a->info;
-  const uint64_t placed = ((uint64_t)info[kInfoPlacedHi] << 32) | info[kInfoPlacedLo];
   const uint32_t slot = s->slot;
   Sp x;
   x.a = a;
   x.s = s;
   x.base = a->slot_base[slot];
-  x.rs = (slot < 64u && ((placed >> slot) & 1ull)) ? nullptr : a->rs + (uint64_t)slot * ((uint64_t)a->n + 1u);
+  x.rs = slot_splits(a, slot);
   x.max_len = s->max_len;
-  x.in = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a->in), (short)0, (int)a->in_bound, 0x00020000);
-  x.rows = static_cast<const uint8_t*>(a->rows);
-  x.row0 = a->row0;
-  x.rsh = a->rows64 ? 3u : 2u;
-  x.rhi = a->rows64 ? 4u : 0u;
+  x.in = bytes_source(a);
+  x.rl = make_row_list(a);
   return x;
-}
-
-// The record of row k < m (tfrg_dense.hip rec_of's rule: compared before the subtraction, whose
-// unsigned result is then the true difference, so no entry wraps into range)
-struct Rec {
-  uint32_t g;
-  uint32_t ok;  // 0 / 1, in a vector register
-};
-
-__device__ __forceinline__ Rec rec_of(const Sp& x, uint32_t k) {
-  int64_t v = (int64_t)k;
-  if (x.rows) {
-    const uint8_t* const p = x.rows + ((uint64_t)k << x.rsh);
-    const uint32_t lo = *reinterpret_cast<const uint32_t*>(p);
-    const uint32_t hi = *reinterpret_cast<const uint32_t*>(p + x.rhi);
-    v = x.rhi ? (int64_t)(((uint64_t)hi << 32) | lo) : (int64_t)(int32_t)lo;
-  }
-  const uint64_t d = (uint64_t)v - (uint64_t)x.row0;
-  const bool ok = v >= x.row0 && d < (uint64_t)x.a->n;
-  uint32_t okv = ok ? 1u : 0u;
-  asm("" : "+v"(okv));  // (kept as a value)
-  return Rec{ok ? (uint32_t)d : 0u, okv};
 }
 
 // One row of the output: `len` elements (bytes on the uint8 path) from position `src` of its source
@@ -113,7 +83,7 @@ struct Row {
 
 template <bool U8>
 __device__ __forceinline__ Row row_of(const Sp& x, uint32_t k) {
-  const Rec q = rec_of(x, k);
+  const Rec q = rec_of(x.a, x.rl.row0, x.rl.rows ? row_entry(x.rl, k) : (int64_t)k);
   uint32_t lo = q.g, c = 1u;
   if (x.rs) {
     lo = x.rs[q.g];
@@ -146,48 +116,6 @@ __device__ __forceinline__ Row row_of(const Sp& x, uint32_t k) {
   }
   r.len = (x.max_len && r.L > x.max_len) ? x.max_len : r.L;
   return r;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (uint64_t)__shfl_down((unsigned long long)v, d, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t u = (uint64_t)__shfl_up((unsigned long long)v, o, 64);
-    if (lane >= (uint32_t)o) v += u;
-  }
-  return v;
-}
-
-// exclusive scan of v over the workgroup (W waves, every thread calls); *total: the workgroup's sum
-// (tfrg_frame.hip's block_excl_scan on 64-bit sums)
-template <int W>
-__device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t* part, uint64_t* total) {
-  const uint64_t inc = wave_incl_scan64(v);
-  const uint32_t w = threadIdx.x >> 6;
-  __syncthreads();  // (part may still be read from a previous call)
-  if ((threadIdx.x & 63u) == 63u) part[w] = inc;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (int i = 0; i < W; ++i) {
-    const uint64_t s = part[i];
-    before += (uint32_t)i < w ? s : 0ull;
-    all += s;
-  }
-  *total = all;
-  return before + inc - v;
 }
 
 // ------------------------------------------------------------------ 1. lengths
@@ -230,15 +158,7 @@ __global__ __launch_bounds__(kBlk) void k_rg_len(const RaggedArgs) {
   }
   uint32_t* const stats = a->stats;
   if (!stats) return;
-  // one atomic per wave and counter at the most
-  const uint32_t tr = wave_sum(trunc), em = wave_sum(empty), mu = wave_sum(multi), sk = wave_sum(skip);
-  if ((threadIdx.x & 63u) == 0u) {
-    uint32_t* st = stats + 4u * si;
-    if (tr) atomicAdd(st + 0, tr);
-    if (em) atomicAdd(st + 1, em);
-    if (mu) atomicAdd(st + 2, mu);
-    if (sk) atomicAdd(st + 3, sk);
-  }
+  add_stats4(stats, si, trunc, empty, multi, skip);
 }
 
 // ------------------------------------------------------------------ 2. tile scan
@@ -249,14 +169,7 @@ __global__ __launch_bounds__(kRaggedScanThreads) void k_rg_scan(const RaggedArgs
   const uint32_t tiles = a->tiles, si = blockIdx.x;
   uint64_t* const tsum = a->tsum + (uint64_t)si * tiles;
   uint64_t carry = 0;
-  for (uint32_t b0 = 0; b0 < tiles; b0 += kRaggedScanThreads) {
-    const uint32_t i = b0 + threadIdx.x;
-    const uint64_t v = i < tiles ? tsum[i] : 0ull;
-    uint64_t total;
-    const uint64_t ex = block_excl_scan64<kRaggedScanThreads / 64>(v, part, &total);
-    if (i < tiles) tsum[i] = carry + ex;
-    carry += total;
-  }
+  for (uint32_t b0 = 0; b0 < tiles; b0 += kRaggedScanThreads) carry = scan_tile_sums<kRaggedScanThreads>(tsum, tiles, b0, carry, part);
   if (threadIdx.x == 0) {
     a->sp[si].offsets[a->m] = (int64_t)carry;
     if (a->totals) a->totals[si] = carry;
@@ -271,18 +184,6 @@ struct Tile {
   const uint32_t* src;
   uint32_t nrows;
 };
-
-// the row of position pos, offs[0] <= pos < offs[nrows]: the last r with offs[r] <= pos (rows without
-// an element share their offset with the row after them)
-__device__ __forceinline__ uint32_t row_at(const Tile& T, uint64_t pos) {
-  uint32_t lo = 0, hi = T.nrows;
-  while (hi - lo > 1u) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (T.offs[mid] <= pos) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // the row of pos from `row` on (a row at or before it); pos < offs[nrows]
 __device__ __forceinline__ uint32_t walk_to(const Tile& T, uint32_t row, uint64_t pos) {
@@ -340,7 +241,7 @@ __device__ __forceinline__ uint32_t u8_dword(const Sp& x, const Tile& T, uint32_
 // one element (the ends of a span)
 template <uint32_t DT>
 __device__ __forceinline__ void copy_elem(const Sp& x, const Tile& T, uint8_t* out, uint64_t pos) {
-  const uint32_t row = row_at(T, pos);
+  const uint32_t row = row_at(T.offs, T.nrows, pos);
   const uint64_t j = pos - T.offs[row];
   if constexpr (DT == kDenseU8) out[pos] = (uint8_t)in_byte(x, T.src[row], j);
   else reinterpret_cast<typename ValT<DT>::type*>(out)[pos] = value_at<DT>(x, T.src[row], j);
@@ -350,7 +251,7 @@ __device__ __forceinline__ void copy_elem(const Sp& x, const Tile& T, uint8_t* o
 // is below offs[nrows])
 template <uint32_t DT>
 __device__ __forceinline__ void copy_unit(const Sp& x, const Tile& T, uint8_t* out, uint64_t pos) {
-  uint32_t row = row_at(T, pos);
+  uint32_t row = row_at(T.offs, T.nrows, pos);
   if constexpr (DT == kDenseU8) {
     rg_u32x4 o;
     o.x = u8_dword(x, T, row, pos);
@@ -426,7 +327,7 @@ __device__ __forceinline__ void scan_tile(const Sp& x, uint32_t t0, uint32_t nro
     Row w{};
     if (r < nrows) w = row_of<U8>(x, t0 + r);
     uint64_t total;
-    const uint64_t ex = block_excl_scan64<kBlk / 64>((uint64_t)w.len, part, &total);
+    const uint64_t ex = block_excl_scan<kBlk / 64>((uint64_t)w.len, part, &total);
     if (r < nrows) {
       offs[r] = carry + ex;
       src[r] = w.src;
@@ -437,7 +338,7 @@ __device__ __forceinline__ void scan_tile(const Sp& x, uint32_t t0, uint32_t nro
   __syncthreads();
 }
 
-// dynamic LDS: offs [tile + 2] u64, src [tile] u32, part [kBlk / 64] u64 (launch_ragged sizes it)
+// dynamic LDS: the row table of tfrg_rows.h with part [kBlk / 64] u64 (launch_ragged sizes it)
 __global__ __launch_bounds__(kBlk) void k_rg_gather(const RaggedArgs) {
   extern __shared__ __attribute__((aligned(16))) uint8_t rg_lds[];
   const KArgs a = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
@@ -445,21 +346,19 @@ __global__ __launch_bounds__(kBlk) void k_rg_gather(const RaggedArgs) {
   const uint32_t per_spec = tiles * S;
   const uint32_t si = blockIdx.x / per_spec, rem = blockIdx.x - si * per_spec;
   const uint32_t ti = rem / S, s = rem - ti * S;
-  uint64_t* const offs = reinterpret_cast<uint64_t*>(rg_lds);
-  uint32_t* const src = reinterpret_cast<uint32_t*>(offs + tile + 2u);
-  uint64_t* const part = reinterpret_cast<uint64_t*>(src + tile);
+  const RowTable l = carve_row_table(rg_lds, tile);
   const Sp x = make_sp(a, si);
   const uint32_t t0 = ti * tile;
   const uint32_t nrows = a->m - t0 < tile ? a->m - t0 : tile;
   const uint64_t base = a->tsum[(uint64_t)si * tiles + ti];
   const uint32_t dt = x.s->dtype;
-  if (dt == kDenseU8) scan_tile<true>(x, t0, nrows, base, offs, src, part);
-  else scan_tile<false>(x, t0, nrows, base, offs, src, part);
+  if (dt == kDenseU8) scan_tile<true>(x, t0, nrows, base, l.offs, l.src, l.part);
+  else scan_tile<false>(x, t0, nrows, base, l.offs, l.src, l.part);
   if (s == 0u) {
     int64_t* const o = x.s->offsets + t0;  // (offsets[m] is k_rg_scan's)
-    for (uint32_t r = threadIdx.x; r < nrows; r += kBlk) o[r] = (int64_t)offs[r];
+    for (uint32_t r = threadIdx.x; r < nrows; r += kBlk) o[r] = (int64_t)l.offs[r];
   }
-  const Tile T{offs, src, nrows};
+  const Tile T{l.offs, l.src, nrows};
   switch (dt) {
     case kDenseI64: gather_tile<kDenseI64>(x, T, s, S); break;
     case kDenseI32: gather_tile<kDenseI32>(x, T, s, S); break;

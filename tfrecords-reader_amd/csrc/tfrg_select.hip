@@ -2,7 +2,7 @@
 // For a list of m candidates (candidate k is record g = entry(k) - row0) and a table of terms (AND of
 // OR-groups), the entries of the candidates that pass, compacted in candidate order. Three launches on
 // the decode's stream, no workgroup ever waiting on another (the shape of k_rg_len / k_rg_scan /
-// k_rg_gather in tfrg_ragged.hip):
+// k_rg_gather in tfrg_ragged.hip; what it shares with the other row-list passes is in tfrg_rows.h):
 //
 //   k_sel_eval   per tile of `tile` candidates, a wave per 64 consecutive candidates: every term in a
 //                uniform loop over the table, each lane gathering the groups that hold a true term for
@@ -31,8 +31,8 @@
 // one through LDS with the whole wave (wave_contains).
 #include <hip/hip_runtime.h>
 
-#include "tfrg_dev.h"
 #include "tfrg_internal.h"
+#include "tfrg_rows.h"
 #include "tfrg_select.h"
 
 namespace tfrg {
@@ -367,15 +367,14 @@ __global__ __launch_bounds__(BYTES ? kBlkBytes : kBlk) void k_sel_eval(const typ
   const uint32_t t0 = blockIdx.x * tile;
   const uint32_t t1 = m - t0 < tile ? m : t0 + tile;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t* const info = a->info;
-  const uint64_t placed = ((uint64_t)info[kInfoPlacedHi] << 32) | info[kInfoPlacedLo];
+  const uint64_t placed = placed_slots(a);
   const uint32_t n_terms = a->n_terms, all = a->all_groups;
   const int64_t row0 = a->row0;
   [[maybe_unused]] BSrc x;
   if constexpr (BYTES) {
     __shared__ __attribute__((aligned(16))) uint32_t stage[kWaves][kScanStage / 4];
     x.b = (KBytes)__builtin_amdgcn_kernarg_segment_ptr();
-    x.in = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(x.b->in), (short)0, (int)x.b->in_bound, 0x00020000);
+    x.in = bytes_source(x.b);
     x.stage = stage[wave];
     x.lane = lane;
   }
@@ -386,7 +385,8 @@ __global__ __launch_bounds__(BYTES ? kBlkBytes : kBlk) void k_sel_eval(const typ
     bool ok = false;
     uint32_t g = 0;
     if (live) {
-      // (tfrg_dense.hip rec_of's rule: compared before the subtraction, so no entry wraps into range)
+      // (the row rule of tfrg_rows.h, written out: compared before the subtraction, so no entry wraps
+      // into range; rec_of's value pinned in a vector register would change this kernel's code)
       const int64_t v = entry_of(a, k);
       const uint64_t d = (uint64_t)v - (uint64_t)row0;
       ok = v >= row0 && d < (uint64_t)n;
@@ -419,17 +419,9 @@ __global__ __launch_bounds__(BYTES ? kBlkBytes : kBlk) void k_sel_eval(const typ
 }
 
 // ------------------------------------------------------------------ 2. tile scan
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t u = (uint64_t)__shfl_up((unsigned long long)v, o, 64);
-    if (lane >= (uint32_t)o) v += u;
-  }
-  return v;
-}
-
-// one workgroup: the tile sums to their first positions; *count and the selected counter
+// one workgroup: the tile sums to their first positions; *count and the selected counter. (The pass
+// is scan_tile_sums of tfrg_rows.h written out: this one adds carry + before + inc - v from the left,
+// and block_excl_scan's before + inc - v first would change the kernel's code.)
 __global__ __launch_bounds__(kSelScanThreads) void k_sel_scan(const SelectArgs) {
   constexpr uint32_t W = kSelScanThreads / 64;
   __shared__ uint64_t part[W];
@@ -441,7 +433,7 @@ __global__ __launch_bounds__(kSelScanThreads) void k_sel_scan(const SelectArgs) 
   for (uint32_t b0 = 0; b0 < tiles; b0 += kSelScanThreads) {
     const uint32_t i = b0 + threadIdx.x;
     const uint64_t v = i < tiles ? tsum[i] : 0ull;
-    const uint64_t inc = wave_incl_scan64(v);
+    const uint64_t inc = wave_incl_scan(v);
     const uint32_t w = threadIdx.x >> 6;
     __syncthreads();  // (part may still be read from the pass before)
     if ((threadIdx.x & 63u) == 63u) part[w] = inc;
