@@ -518,6 +518,101 @@ int tfrg_result_ragged_elems(tfrg_ctx* ctx, const tfrg_elems_spec* specs, uint32
                              const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
                              uint64_t* d_totals, uint32_t* d_stats, void* consumer_stream);
 
+/* Element ids: a bytes element as the integer a model takes (an embedding row, a class number), by a
+ * hash into N buckets, by an exact lookup in a vocabulary, or by both.
+ *
+ * tfrg_hash64: one function of a byte string, computed identically by the host, the device and the
+ * Python restatement in tfr_reader/ids.py (all arithmetic mod 2^64):
+ *   h = 0xcbf29ce484222325
+ *   for each 8-byte group w of the string, in order, read little-endian, the last one zero-padded:
+ *     h = (h ^ w) * 0x100000001b3
+ *   h ^= length
+ *   h ^= h >> 33;  h *= 0xff51afd7ed558ccd;  h ^= h >> 33;  h *= 0xc4ceb9fe1a85ec53;  h ^= h >> 33
+ * It is NOT TensorFlow's FarmHash (tf.strings.to_hash_bucket_fast gives other numbers): bucket numbers
+ * are this library's own. They are stable across versions of the library, since callers may persist
+ * them: the function above will not change. */
+uint64_t tfrg_hash64(const uint8_t* p, uint64_t n);
+
+/* A vocabulary: n_words distinct byte strings, each with an int64 id. Word i is
+ * words[offsets[i] .. offsets[i + 1]) and its id is ids[i], or i when ids is NULL. device == -1 builds
+ * the host table only: no HIP call is made, and tfrg_result_elem_ids refuses such a vocabulary.
+ * device >= 0 also uploads the table to that device, once. The arguments are copied.
+ * The table is an open-addressing table built on the host: capacity is the smallest power of two
+ * >= max(16, 2 * n_words); a slot is a u32 word index, or 0xffffffff for empty; the words are inserted
+ * in order, word i at tfrg_hash64(word i) & (capacity - 1) or, by linear probing, the first empty slot
+ * after it (wrapping); max_probe is the largest displacement of any word from its home slot. Beside it:
+ * the u32 word offsets, the word blob and the int64 ids. A match is byte equality: the hash picks the
+ * home slot only. n_words == 0 is a valid vocabulary that nothing matches.
+ * TFRG_E_ARG (text in tfrg_last_error): a word that occurs twice, n_words >= 2^31, words of 2^32
+ * bytes or more in all (2^32 - 16 with device >= 0), offsets that descend, a NULL out.
+ * tfrg_vocab_destroy synchronises the vocabulary's device before it frees the table, so work already
+ * queued that reads it has finished; the caller keeps the object until the work that uses it has been
+ * queued. NULL is accepted.
+ * tfrg_vocab_info: any of the four pointers may be NULL; device_bytes is 0 for a host-only vocabulary.
+ * tfrg_vocab_lookup_host: the id of the word equal to p[0 .. n), or `missing`. */
+typedef struct tfrg_vocab tfrg_vocab;
+int tfrg_vocab_create(int device, const uint8_t* words, const uint64_t* offsets, uint64_t n_words,
+                      const int64_t* ids, tfrg_vocab** out);
+int tfrg_vocab_destroy(tfrg_vocab* v);
+int tfrg_vocab_info(const tfrg_vocab* v, uint64_t* n_words, uint64_t* capacity, uint32_t* max_probe,
+                    uint64_t* device_bytes);
+int64_t tfrg_vocab_lookup_host(const tfrg_vocab* v, const uint8_t* p, uint64_t n, int64_t missing);
+
+/* The ids of EVERY element of a bytes_list slot for a list of rows: one int64 per element that
+ * tfrg_result_ragged_elems would describe, in its order, with its row offsets. Rows (d_rows,
+ * rows_dtype, m, row0, a NULL d_rows as the identity list, the rule for entries outside [0, n)) are
+ * word for word tfrg_result_ragged_elems's; a skipped row is an empty row. Per spec:
+ *   row_offsets[0 .. m] and the order of the elements are exactly those of tfrg_result_ragged_elems
+ *     with the same max_elems, so ids[e] belongs to the element that call describes at e and the two
+ *     outputs can be used side by side. All m + 1 row offsets are always written. E = row_offsets[m];
+ *   the id of an element with bytes s: the id of the vocabulary's word equal to s, if there is one;
+ *     else, with num_oov_buckets != 0, oov_base + (int64_t)(tfrg_hash64(s) % num_oov_buckets); else
+ *     default_id. (Pure hashing: vocab NULL, oov_base 0. Out-of-vocabulary ids after the vocabulary:
+ *     oov_base = n_words. Out-of-vocabulary ids first: ids[i] = i + k at tfrg_vocab_create, oov_base 0.)
+ *   s is what tfrg_result_ragged_elems reads for the element: from the views into d_bytes, the
+ *     materialized column, or the end-relative view of an implicit_off_slots slot with the constant
+ *     length of TFRG_IMPLICIT_BYTES_LEN; bytes past the readable input read as zero. Columns an
+ *     optimistic decode left implicit are neither read nor written.
+ *   Only positions < elem_cap of ids are stored and nothing else in ids is written.
+ * d_totals (device, [n_specs] u64, or NULL): E. d_stats (device, [n_specs][4] u32, or NULL; zeroed by
+ * the call on the stream), counted over all E taken elements and not only the stored ones: rows with
+ * more than max_elems != 0 elements; taken elements that matched no word (every element, with vocab
+ * NULL); rows that are not skipped and have no element; skipped rows. A record drawn twice counts twice.
+ * m == 0: row_offsets[0] = 0, totals 0, no kernel. n == 0: every row is skipped. Two equal calls write
+ * equal bytes.
+ * Three launches on the decode's stream (counts per tile of rows, the scan of the tile sums, then row
+ * offsets and ids); no device value is read back. Stream order with consumer_stream, the single
+ * confirmation of an optimistic or hinted decode, any number of calls per decode, the rows per tile
+ * (tfrg_ctx_set_ragged_tile) and scratch from the context's arena are as for tfrg_result_ragged_elems.
+ * Cost: an element is hashed, probed and compared by ONE lane, 8 bytes a step, so one very long element
+ * holds its wave for its whole length (accepted, as tfrg_result_select_match's CONTAINS scan is: cap
+ * such a slot's work with a vocabulary, below). An element longer than the vocabulary's longest word
+ * under num_oov_buckets == 0 can match nothing and needs no hash: its bytes are not read at all.
+ * Without d_stats, elements at or past elem_cap (all of them with ids NULL) are not read either: a
+ * first call with ids NULL and d_stats NULL that sizes ids costs the row pass alone.
+ * TFRG_E_ARG (text in tfrg_last_error prefixed "tfrg_result_elem_ids: ", nothing launched or
+ * written): everything tfrg_result_ragged_elems refuses about the context, the rows and m; n_specs
+ * outside 1..TFRG_IDS_MAX_SPECS; a slot >= n_slots or not a bytes_list slot; a NULL or misaligned
+ * row_offsets, a misaligned ids; nonzero reserved words; vocab NULL with num_oov_buckets == 0; a
+ * vocabulary built host-only or on another device than the context's. */
+#define TFRG_IDS_MAX_SPECS 32
+typedef struct tfrg_ids_spec {
+  uint32_t slot;            /* a bytes_list slot, as in tfrg_set_schema */
+  uint32_t max_elems;       /* 0: every element of a row; else at most its first max_elems */
+  uint32_t reserved0;       /* 0 */
+  uint32_t reserved1;       /* 0 */
+  const tfrg_vocab* vocab;  /* NULL: hash buckets only */
+  uint64_t num_oov_buckets; /* 0: an unmatched element gets default_id */
+  int64_t oov_base;
+  int64_t default_id;
+  uint64_t elem_cap;        /* ids that `ids` can hold */
+  int64_t* ids;             /* device [elem_cap], caller-owned; NULL: offsets and counters only */
+  int64_t* row_offsets;     /* device [m + 1], caller-owned, not NULL */
+} tfrg_ids_spec;            /* 72 bytes */
+int tfrg_result_elem_ids(tfrg_ctx* ctx, const tfrg_ids_spec* specs, uint32_t n_specs,
+                         const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
+                         uint64_t* d_totals, uint32_t* d_stats, void* consumer_stream);
+
 /* Filtered row lists: the WHERE clause over the last result, on the device. Predicates over the
  * decoded columns in, the compacted list of the passing rows in device memory out -- usable as it is
  * as d_rows of tfrg_result_dense_rows / tfrg_result_ragged_rows of the same context(s), with the same

@@ -16,11 +16,13 @@
 #include "crc32c.h"
 #include "tfrg_dense.h"
 #include "tfrg_elems.h"
+#include "tfrg_ids.h"
 #include "tfrg_ragged.h"
 #include "tfrg_select.h"
 #include "tfrg_frame.h"
 #include "tfrg_internal.h"
 #include "tfrg_learn.h"
+#include "tfrg_vocab.h"
 
 namespace tfrg {
 void set_error(const std::string& s);
@@ -135,6 +137,7 @@ struct Arena {
   DBuf fr_tab, fr_dev;  // tfrg_index_device: chunk table, piece rows + summary
   DBuf rg_tsum;  // tfrg_result_ragged_rows: the per-tile sums
   DBuf el_tsum;  // tfrg_result_ragged_elems: the per-tile element counts and byte sums
+  DBuf id_tsum;  // tfrg_result_elem_ids: the per-tile element counts
   DBuf sel_buf;  // tfrg_result_select_rows: the candidates' ballot words, then the per-tile sums
   template <class F>
   void each(F f) {
@@ -143,7 +146,7 @@ struct Arena {
                          &totals, &kind_totals, &ident, &i64, &f32, &b_off, &b_len, &big_list, &slow_list, &miss, &info,
                          &tsum, &crc_rec, &crc_base, &crc_part, &dq, &dq_cnt, &lmask, &rlist, &bdata, &boff64, &blb,
                          &bbig, &tpl, &spec, &fr_tab, &fr_dev, &rg_tsum, &el_tsum,
-                         &sel_buf};
+                         &id_tsum, &sel_buf};
     static_assert(sizeof(all) / sizeof(*all) * sizeof(DBuf) == sizeof(Arena), "a buffer is missing from the list");
     for (DBuf* b : all) f(*b);
   }
@@ -1596,6 +1599,143 @@ int tfrg_result_ragged_elems(tfrg_ctx* c, const tfrg_elems_spec* specs, uint32_t
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
     }
     if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 16, st));
+  }
+  return fence_close(c, st, cs);
+}
+
+// ---- The device half of a vocabulary (tfrg_vocab.h; the host half, tfrg_host.cpp, calls it through
+// g_vocab_device). One allocation: ids, table, offsets, then the blob and zeros to a multiple of 16.
+static int vocab_upload(tfrg_vocab* v) {
+  if (v->blob.size() >= 0xfffffff0ull) {  // (the kernels read the blob through a 32-bit buffer bound)
+    set_error("tfrg_vocab_create: words of 2^32 - 16 bytes or more in all cannot go to a device");
+    return TFRG_E_ARG;
+  }
+  HIP_TRY(hipSetDevice(v->device));
+  const size_t n_ids = v->ids.size() * 8, n_tab = v->table.size() * 4, n_off = v->offs.size() * 4;
+  const size_t at_tab = n_ids, at_off = at_tab + n_tab, at_blob = (at_off + n_off + 15) & ~(size_t)15;
+  const size_t blob_room = (v->blob.size() + 16) & ~(size_t)15;
+  const size_t total = at_blob + blob_room;
+  void* p = nullptr;
+  HIP_TRY(hipMalloc(&p, total));
+  uint8_t* const d = static_cast<uint8_t*>(p);
+  hipError_t e = hipMemset(d + at_blob, 0, blob_room);
+  if (e == hipSuccess && n_ids) e = hipMemcpy(d, v->ids.data(), n_ids, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + at_tab, v->table.data(), n_tab, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + at_off, v->offs.data(), n_off, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !v->blob.empty()) e = hipMemcpy(d + at_blob, v->blob.data(), v->blob.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    (void)hipFree(p);
+    v->d_mem = nullptr;
+    set_error(std::string("tfrg_vocab_create: upload: ") + hipGetErrorString(e));
+    return TFRG_E_HIP;
+  }
+  v->d_mem = p;
+  v->d_ids = reinterpret_cast<const int64_t*>(d);
+  v->d_table = reinterpret_cast<const uint32_t*>(d + at_tab);
+  v->d_offs = reinterpret_cast<const uint32_t*>(d + at_off);
+  v->d_blob = d + at_blob;
+  v->d_blob_bound = (uint32_t)std::min<uint64_t>(blob_room, 0xfffffff0ull);
+  v->device_bytes = total;
+  return 0;
+}
+static int vocab_release(tfrg_vocab* v) {
+  HIP_TRY(hipSetDevice(v->device));
+  HIP_TRY(hipDeviceSynchronize());  // (work already queued may still read the table)
+  HIP_TRY(hipFree(v->d_mem));
+  v->d_mem = nullptr;
+  return 0;
+}
+static const bool g_vocab_device_registered = (tfrg::g_vocab_device = {vocab_upload, vocab_release}, true);
+
+// One id per element of a bytes_list slot for a list of rows (tfrg_ids.h: counts, tile scan, row
+// offsets and ids). Every grid size comes from m, n_specs and the tile: nothing is read back.
+int tfrg_result_elem_ids(tfrg_ctx* c, const tfrg_ids_spec* specs, uint32_t n_specs, const void* d_rows,
+                         uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
+                         void* consumer_stream) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_result_elem_ids: " + why);
+    return TFRG_E_ARG;
+  };
+  if (const int rc = check_specs(c, specs, n_specs, TFRG_IDS_MAX_SPECS, bad)) return rc;
+  static_assert(TFRG_IDS_MAX_SPECS == kIdsMaxSpecs, "tfrg.h mirrors tfrg_ids.h");
+  static_assert(sizeof(tfrg_ids_spec) == 72, "tfrg.h states the size");
+  static_assert(kIdsNoLen == kElemsNoLen && kIdsOffStored == kElemsOffStored, "const_len_of / const_off_of serve tfrg_ids.h");
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_ids_spec& s = specs[i];
+    const std::string at = "spec " + std::to_string(i) + ": ";
+    if (s.slot >= c->n_slots) return bad(at + "slot " + std::to_string(s.slot) + " >= n_slots");
+    const uint32_t kind = c->slot_kind_h[s.slot] & 3u;
+    if (kind != TFRG_KIND_BYTES)
+      return bad(at + "slot " + std::to_string(s.slot) + " is not a bytes_list slot (kind " + std::to_string(kind) + ")");
+    if (!s.row_offsets) return bad(at + "row_offsets is NULL");
+    if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.ids & 7u)) return bad(at + "row_offsets and ids must be 8-byte aligned");
+    if (s.reserved0 || s.reserved1) return bad(at + "reserved words must be 0");
+    if (!s.vocab && !s.num_oov_buckets) return bad(at + "no vocabulary and no hash buckets");
+    if (s.vocab && !s.vocab->d_mem) return bad(at + "the vocabulary was built host-only (device -1)");
+    if (s.vocab && s.vocab->device != c->device)
+      return bad(at + "the vocabulary is on device " + std::to_string(s.vocab->device) + ", the context on " +
+                 std::to_string(c->device));
+  }
+  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
+  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
+  const uint32_t tile = c->ragged_tile;
+  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile;
+  if (tiles * n_specs > 0x7fffffffull) return bad("too many tiles for one launch: raise the ragged tile");
+  HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = confirm_pending(c)) return rc;
+  const bool run = m && c->res.req.n;
+  if (run) HIP_TRY(c->id_tsum.ensure((size_t)(tiles * n_specs) * 8));
+  hipStream_t st, cs;
+  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
+  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
+  if (run) {
+    IdsArgs a{};
+    fill_columns(c, a);
+    fill_bytes_source(c, a);
+    a.stats = d_stats;
+    a.totals = d_totals;
+    a.tsum = c->id_tsum.as<uint64_t>();
+    a.rows = d_rows;
+    a.rows64 = rows_dtype == TFRG_ROWS_I64;
+    a.row0 = row0;
+    a.m = m;
+    a.n_specs = n_specs;
+    a.tile = tile;
+    a.tiles = (uint32_t)tiles;
+    for (uint32_t i = 0; i < n_specs; ++i) {
+      const tfrg_ids_spec& s = specs[i];
+      IdsSpec& d = a.sp[i];
+      d.ids = s.ids;
+      d.row_offsets = s.row_offsets;
+      d.elem_cap = s.elem_cap;
+      if (const tfrg_vocab* v = s.vocab) {
+        d.table = v->d_table;
+        d.w_offs = v->d_offs;
+        d.blob = v->d_blob;
+        d.w_ids = v->d_ids;
+        d.mask = (uint32_t)v->table.size() - 1u;
+        d.max_probe = v->max_probe;
+        d.max_word = v->max_word;
+        d.blob_bound = v->d_blob_bound;
+      }
+      d.n_buckets = s.num_oov_buckets;
+      d.oov_base = s.oov_base;
+      d.default_id = s.default_id;
+      d.slot = s.slot;
+      d.max_elems = s.max_elems;
+      d.const_len = const_len_of(c, s.slot, true);
+      d.const_off = const_off_of(c, s.slot, true);
+    }
+    HIP_TRY(launch_ids(a, st));
+  } else {
+    // no row, or no record (every row is skipped): all offsets and totals are 0
+    for (uint32_t i = 0; i < n_specs; ++i) {
+      HIP_TRY(hipMemsetAsync(specs[i].row_offsets, 0, ((size_t)m + 1) * 8, st));
+      if (d_stats && m)
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
+    }
+    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 8, st));
   }
   return fence_close(c, st, cs);
 }

@@ -2,7 +2,8 @@
 // word primitives, the readfirstlane wrappers, the wave sums and the wave and workgroup scans, the nt
 // store, and the bookkeeping that ends an optimistic decode (all_placed_finish). Included by
 // tfrg_kernels.hip, tfrg_scan.hip, tfrg_tpl.hip, tfrg_bytes.hip, tfrg_frame.hip and, through
-// tfrg_rows.h, by the row-list passes (tfrg_dense.hip, tfrg_ragged.hip, tfrg_elems.hip, tfrg_select.hip).
+// tfrg_rows.h, by the row-list passes (tfrg_dense.hip, tfrg_ragged.hip, tfrg_elems.hip, tfrg_ids.hip,
+// tfrg_select.hip).
 #pragma once
 #include "tfrg_internal.h"
 #include "../../include/tfrg_status.h"

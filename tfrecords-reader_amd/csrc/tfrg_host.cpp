@@ -1,6 +1,7 @@
 // tfrg_host.cpp — host-side native pieces of libtfrg: the TFRecord framing index over an mmap'd
 // file image (replaces cython/indexer.pyx:212-252, bit-exact), the .idx cache format
-// (indexer.pyx:255-328), CRC-32C and the TFRecord writer framing.
+// (indexer.pyx:255-328), CRC-32C and the TFRecord writer framing; tfrg_hash64 and the host half of the
+// vocabulary object (tfrg_vocab: the open-addressing table, built and probed here).
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
@@ -10,6 +11,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <new>
 #include <string>
 #include <unordered_set>
 #include <vector>
@@ -18,6 +20,7 @@
 
 #include "../../include/tfrg.h"
 #include "crc32c.h"
+#include "tfrg_vocab.h"
 
 namespace tfrg {
 thread_local std::string g_last_error;
@@ -56,6 +59,8 @@ struct HostCrc {
     return c;
   }
 };
+VocabDeviceOps g_vocab_device = {nullptr, nullptr};
+
 static const HostCrc& host_crc() {
   static const HostCrc h;
   return h;
@@ -537,6 +542,108 @@ int64_t tfrg_frame_records(const uint8_t* payloads, const uint64_t* offsets, int
     p += 16 + len;
   }
   return total;
+}
+
+// ---- tfrg_hash64 and the vocabulary (include/tfrg.h)
+uint64_t tfrg_hash64(const uint8_t* p, uint64_t n) { return hash64(p, n); }
+
+// The table: capacity the smallest power of two >= max(16, 2 * n_words), words inserted in order at
+// hash & (capacity - 1), linear probing. A word met on the way that equals the new one is a duplicate.
+int tfrg_vocab_create(int device, const uint8_t* words, const uint64_t* offsets, uint64_t n_words, const int64_t* ids,
+                      tfrg_vocab** out) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_vocab_create: " + why);
+    return TFRG_E_ARG;
+  };
+  if (!out) return bad("out is NULL");
+  *out = nullptr;
+  if (device < -1) return bad("device must be -1 (host only) or a device ordinal");
+  if (n_words >= 0x80000000ull) return bad("n_words must be below 2^31");
+  if (n_words && !offsets) return bad("offsets is NULL");
+  for (uint64_t i = 0; i < n_words; ++i)
+    if (offsets[i + 1] < offsets[i]) return bad("offsets descend at word " + std::to_string(i));
+  const uint64_t first = n_words ? offsets[0] : 0, nblob = n_words ? offsets[n_words] - first : 0;
+  if (nblob >= 0x100000000ull) return bad("the words hold 2^32 bytes or more");
+  if (nblob && !words) return bad("words is NULL");
+  if (device >= 0 && !g_vocab_device.upload) return bad("this build has no device half: device must be -1");
+  tfrg_vocab* v = new (std::nothrow) tfrg_vocab;
+  if (!v) {
+    set_error("tfrg_vocab_create: out of memory");
+    return TFRG_E_NOMEM;
+  }
+  uint64_t cap = 16;
+  while (cap < 2 * n_words) cap <<= 1;
+  try {
+    v->table.assign(cap, kVocabEmpty);
+    v->offs.resize(n_words + 1);
+    v->blob.assign(words ? words + first : nullptr, words ? words + first + nblob : nullptr);
+    v->ids.resize(n_words);
+  } catch (const std::bad_alloc&) {
+    delete v;
+    set_error("tfrg_vocab_create: out of memory");
+    return TFRG_E_NOMEM;
+  }
+  v->offs[0] = 0;
+  for (uint64_t i = 0; i < n_words; ++i) {
+    v->offs[i + 1] = (uint32_t)(offsets[i + 1] - first);
+    v->ids[i] = ids ? ids[i] : (int64_t)i;
+  }
+  const uint8_t* const b = v->blob.data();
+  for (uint64_t i = 0; i < n_words; ++i) {
+    const uint32_t o = v->offs[i], len = v->offs[i + 1] - o;
+    uint64_t s = hash64(b + o, len) & (cap - 1), d = 0;
+    for (; v->table[s] != kVocabEmpty; s = (s + 1) & (cap - 1), ++d) {
+      const uint32_t w = v->table[s], wo = v->offs[w];
+      if (v->offs[w + 1] - wo == len && (len == 0 || memcmp(b + wo, b + o, len) == 0)) {
+        delete v;
+        return bad("word " + std::to_string(i) + " equals word " + std::to_string(w));
+      }
+    }
+    v->table[s] = (uint32_t)i;
+    if (d > v->max_probe) v->max_probe = (uint32_t)d;
+    if (len > v->max_word) v->max_word = len;
+  }
+  if (device >= 0) {
+    v->device = device;
+    if (const int rc = g_vocab_device.upload(v)) {
+      delete v;
+      return rc;
+    }
+  }
+  *out = v;
+  return 0;
+}
+
+int tfrg_vocab_destroy(tfrg_vocab* v) {
+  if (!v) return 0;
+  int rc = 0;
+  if (v->d_mem && g_vocab_device.release) rc = g_vocab_device.release(v);
+  delete v;
+  return rc;
+}
+
+int tfrg_vocab_info(const tfrg_vocab* v, uint64_t* n_words, uint64_t* capacity, uint32_t* max_probe,
+                    uint64_t* device_bytes) {
+  if (!v) {
+    set_error("tfrg_vocab_info: no vocabulary");
+    return TFRG_E_ARG;
+  }
+  if (n_words) *n_words = v->ids.size();
+  if (capacity) *capacity = v->table.size();
+  if (max_probe) *max_probe = v->max_probe;
+  if (device_bytes) *device_bytes = v->device_bytes;
+  return 0;
+}
+
+int64_t tfrg_vocab_lookup_host(const tfrg_vocab* v, const uint8_t* p, uint64_t n, int64_t missing) {
+  if (!v || n > v->max_word) return missing;
+  const uint64_t mask = v->table.size() - 1;
+  const uint8_t* const b = v->blob.data();
+  for (uint64_t s = hash64(p, n) & mask; v->table[s] != kVocabEmpty; s = (s + 1) & mask) {
+    const uint32_t w = v->table[s], wo = v->offs[w];
+    if (v->offs[w + 1] - wo == n && (n == 0 || memcmp(b + wo, p, (size_t)n) == 0)) return v->ids[w];
+  }
+  return missing;
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // tfrg_rows.h — what the row-list passes share: the device code of the passes that read a finished
-// decode through a list of rows (tfrg_dense.hip, tfrg_ragged.hip, tfrg_elems.hip, tfrg_select.hip),
-// each piece defined once. The functions that read a kernel argument are templates over the pass's own
-// pointer to it (DenseArgs, RaggedArgs, ElemsArgs, SelectArgs / SelectBytesArgs in the constant
+// decode through a list of rows (tfrg_dense.hip, tfrg_ragged.hip, tfrg_elems.hip, tfrg_ids.hip,
+// tfrg_select.hip), each piece defined once. The functions that read a kernel argument are templates over
+// the pass's own pointer to it (DenseArgs, RaggedArgs, ElemsArgs, IdsArgs, SelectArgs / SelectBytesArgs in the constant
 // address space), as fill_columns<Args> is on the host: the argument structs stay apart, and only
 // the names of their common fields (info, rs, n, rows, row0, rows64, in, in_bound) are assumed.
 #pragma once

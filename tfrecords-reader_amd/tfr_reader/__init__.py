@@ -6,6 +6,7 @@ spreads the readers' files over several GPUs.
 """
 
 from tfr_reader.example import Feature, set_decoder_type
+from tfr_reader.ids import ElementIds, Vocabulary
 from tfr_reader.ragged import Ragged, RaggedBatch
 from tfr_reader.reader import (
     TFRecordDatasetReader,
@@ -17,11 +18,13 @@ from tfr_reader.reader import (
 )
 
 __all__ = [
+    "ElementIds",
     "Feature",
     "Ragged",
     "RaggedBatch",
     "TFRecordDatasetReader",
     "TFRecordFileReader",
+    "Vocabulary",
     "inspect_dataset_example",
     "join_path",
     "load_from_directory",

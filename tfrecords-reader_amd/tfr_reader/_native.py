@@ -158,6 +158,28 @@ ELEMS_MAX_SPECS = 32
 ELEMS_SCAN_THREADS = 1024  # (csrc/tfrg_elems.h: the tile sums its scan kernel takes per pass)
 
 
+class TfrgIdsSpec(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("max_elems", C.c_uint32),
+        ("reserved0", C.c_uint32),
+        ("reserved1", C.c_uint32),
+        ("vocab", C.c_void_p),
+        ("num_oov_buckets", C.c_uint64),
+        ("oov_base", C.c_int64),
+        ("default_id", C.c_int64),
+        ("elem_cap", C.c_uint64),
+        ("ids", C.c_void_p),
+        ("row_offsets", C.c_void_p),
+    ]
+
+
+IDS_MAX_SPECS = 32
+IDS_SCAN_THREADS = 1024  # (csrc/tfrg_ids.h: the tile sums its scan kernel takes per pass)
+VOCAB_EMPTY = 0xFFFFFFFF  # a slot of a vocabulary's table without a word
+VOCAB_MIN_CAPACITY = 16
+
+
 class TfrgSelectTerm(C.Structure):
     _fields_ = [
         ("slot", C.c_uint32),
@@ -284,6 +306,13 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_ctx_set_ragged_tile": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tfrg_result_ragged_elems": (C.c_int, [C.c_void_p, C.POINTER(TfrgElemsSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                            C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tfrg_hash64": (C.c_uint64, [C.c_char_p, C.c_uint64]),
+    "tfrg_vocab_create": (C.c_int, [C.c_int, C.c_char_p, u64p, C.c_uint64, i64p, C.POINTER(C.c_void_p)]),
+    "tfrg_vocab_destroy": (C.c_int, [C.c_void_p]),
+    "tfrg_vocab_info": (C.c_int, [C.c_void_p, u64p, u64p, u32p, u64p]),
+    "tfrg_vocab_lookup_host": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int64]),
+    "tfrg_result_elem_ids": (C.c_int, [C.c_void_p, C.POINTER(TfrgIdsSpec), C.c_uint32, C.c_void_p, C.c_uint32,
+                                       C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_result_select_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgSelectTerm), C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_uint32, C.c_void_p]),

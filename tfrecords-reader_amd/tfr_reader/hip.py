@@ -533,6 +533,15 @@ class HipDecoder:
 
         return R.decoder_ragged_elements(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
 
+    def element_ids(self, specs, *, rows=None, capacity=None, out=None, stream: int | None = None):
+        """One int64 id per element of the ``bytes_list``s of the last decode (a vocabulary lookup, hash
+        buckets, or both) as ``(ids, row_offsets)`` torch tensors on this decoder's device, one pair per
+        ``tfr_reader.ids.ElementIds`` spec, for every record or for the list ``rows``
+        (tfrg_result_elem_ids); see ``tfr_reader.ids.decoder_element_ids``."""
+        from tfr_reader import ids as I  # noqa: PLC0415, N812
+
+        return I.decoder_element_ids(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
+
     def ragged_minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False, capacity=None,
                            where=None):
         """One epoch of shuffled ``batch_size``-row ``RaggedBatch``es over the last decode (``where``:
@@ -844,6 +853,14 @@ class BatchResult:
         from tfr_reader import ragged as R  # noqa: PLC0415
 
         return R.batch_ragged_elements(self, specs, rows)
+
+    def element_ids(self, specs, rows=None):
+        """``(ids, row_offsets)`` numpy arrays of ``tfr_reader.ids.ElementIds`` specs from the fetched
+        columns (the host counterpart of ``HipDecoder.element_ids``, with a pure-Python table): an
+        ``IdsBatch`` with ``.totals`` and ``.stats``. ``rows``: as for ``ragged``."""
+        from tfr_reader import ids as I  # noqa: PLC0415, N812
+
+        return I.batch_element_ids(self, specs, rows)
 
     def select(self, where, rows=None, row0: int = 0):
         """The candidates that pass ``where`` (``tfr_reader.select.Term``s), from the fetched columns
