@@ -562,3 +562,45 @@ def test_python_device_path_against_the_numpy_path(main):
     finally:
         for v in (vocab, tags, host_only):
             v.close()
+
+
+def test_python_absent_key_over_a_list_with_entries_out_of_range(main):
+    """An absent key beside a present one, over a device row list with -1 and n in it: the absent key's
+    rows are empty or skipped like the present one's, without a launch for it, and offsets the caller
+    provides for it are zeroed."""
+    import torch
+
+    d, _, items, t = main
+    vocab = I.Vocabulary(t.words, device=0)
+    try:
+        rows = [0, N_REC, -1, 5, I64_MAX, 3, 3]
+        specs = [I.ElementIds("zz", vocab, name="absent"), I.ElementIds("b", vocab, num_oov_buckets=7)]
+        want = IR.expect(items, IR.Rule("b", t.t_half, 7, len(t.words)), rows)
+        assert want.stats[3] == 3 and want.total > 0
+        got = d.element_ids(specs, rows=to_dev(rows))
+        assert got["absent"][0].numel() == 0 and got["absent"][1].cpu().tolist() == [0] * 8
+        assert got.stats["absent"].tolist() == [0, 0, 4, 3] and got.totals["absent"] == 0 and not got.overflowed["absent"]
+        assert np.array_equal(got["b"][0].cpu().numpy(), want.ids) and np.array_equal(got["b"][1].cpu().numpy(), want.row_offsets)
+        assert got.stats["b"].tolist() == want.stats and got.totals["b"] == want.total
+        out = {"absent": (torch.full((4,), -1, dtype=torch.int64, device=dev()), torch.full((8,), -1, dtype=torch.int64, device=dev()))}
+        got = d.element_ids(specs, rows=to_dev(rows), out=out)
+        assert out["absent"][1].cpu().tolist() == [0] * 8 and out["absent"][0].cpu().tolist() == [-1] * 4
+        assert got.capacity["absent"] == 4 and np.array_equal(got["b"][0].cpu().numpy(), want.ids)
+    finally:
+        vocab.close()
+
+
+def test_python_path_over_a_decode_of_no_records():
+    """No record: every row of a device list is skipped, nothing is launched, all offsets are 0."""
+    fresh = new_decoder()
+    vocab = I.Vocabulary([b"q"], device=0)
+    try:
+        buf, s0, e0 = payload_input(main_batch()[0])
+        assert len(fresh.decode(buf[: int(e0[4])], s0[:5], e0[:5], payload_only=True)) == 5  # (the keys get their slots)
+        assert len(fresh.decode(buf[:0], s0[:0], e0[:0], payload_only=True)) == 0
+        got = fresh.element_ids([I.ElementIds("b", vocab)], rows=to_dev([0, 5]))
+        assert got["b"][0].numel() == 0 and got["b"][1].cpu().tolist() == [0, 0, 0]
+        assert got.stats["b"].tolist() == [0, 0, 0, 2] and got.totals["b"] == 0 and not got.overflowed["b"]
+    finally:
+        vocab.close()
+        fresh.close()

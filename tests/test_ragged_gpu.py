@@ -464,6 +464,25 @@ def test_c_level_argument_errors_and_empty_cases(dec):
     assert got["label"][1].cpu().tolist() == [0, 0, 0] and got.stats["label"].tolist() == [0, 0, 0, 2]
 
 
+def test_python_out_is_checked(dec):
+    """``out=``: tensors of the right dtype and shape are written into; a wrong dtype, shape or device
+    is refused."""
+    import torch
+
+    dec.decode(*synth.framed(synth.c1_payloads(6)))
+    specs = [R.Ragged("label", "int64")]
+    rows = to_dev([0, 6, -1, 5, 2, 2, 3])
+    ok = (torch.full((8,), -1, dtype=torch.int64, device=dev()), torch.full((8,), -1, dtype=torch.int64, device=dev()))
+    got = dec.ragged(specs, rows=rows, out={"label": ok})
+    assert got["label"][0] is ok[0] and got["label"][1] is ok[1] and got.capacity["label"] == 8
+    assert ok[1].cpu().tolist() == [0, 1, 1, 1, 2, 3, 4, 5] and ok[0].cpu().tolist() == [0, 5, 2, 2, 3, -1, -1, -1]
+    assert got.totals["label"] == 5 and got.stats["label"].tolist() == [0, 0, 0, 2] and not got.overflowed["label"]
+    for i, wrong in ((0, ok[0].to(torch.int32)), (0, ok[0].cpu()), (0, ok[0].view(2, 4)), (0, ok[0][::2]),
+                     (1, ok[1].to(torch.int32)), (1, ok[1][:-1]), (1, ok[1].cpu())):
+        with pytest.raises(ValueError):
+            dec.ragged(specs, rows=rows, out={"label": tuple(wrong if j == i else t for j, t in enumerate(ok))})
+
+
 # ------------------------------------------------------------------------------------ 7. streams
 def test_rows_made_just_before_and_results_used_just_after(c3):
     """The row list is produced by kernels queued on the consumer stream immediately before the call

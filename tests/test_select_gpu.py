@@ -112,6 +112,9 @@ def run(d, where, want, wstats, rows=None, rdt=np.int64, row0: int = 0, odt: int
     elif m is None:
         m = d._last_n
     out_ptr = None if null_out else big.data_ptr() + GUARD
+    # (no consumer stream is given, so nothing orders the call's memsets on the decode's stream after the
+    # poison fills queued above on torch's: without a row list to upload, they have to be waited for here)
+    torch.cuda.synchronize()
     S.launch(d, terms, rw, m, row0, (out_ptr, odt), cap, count.data_ptr(), st.data_ptr() + GUARD,
              N.SEL_APPEND if base is not None else 0, None)
     torch.cuda.synchronize()

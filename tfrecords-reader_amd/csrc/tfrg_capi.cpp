@@ -1431,85 +1431,138 @@ int tfrg_result_dense_rows(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n
   return result_dense("tfrg_result_dense_rows", true, c, specs, n_specs, rows, d_stats, consumer_stream);
 }
 
+// ---- The frame of the entry points that pack per-spec outputs for a list of rows (tfrg_result_ragged_rows,
+// _ragged_elems, _elem_ids): the checks in the one order all three make them, the tiles and the split,
+// the scratch, the consumer fence and the counters, around what an entry point brings as its own.
+struct RowListCall {  // the arguments the three have in common
+  const void* d_rows;
+  uint32_t rows_dtype, m;
+  int64_t row0;
+  uint64_t* d_totals;
+  uint32_t* d_stats;
+  void* consumer_stream;
+};
+struct RowListKind {
+  const char* fn;
+  uint32_t max_specs;
+  DBuf Arena::*tsum;   // the scratch of the per-tile sums
+  uint32_t words;      // u64 words per (spec, tile) in it, and per spec in d_totals
+  uint32_t split0;     // workgroups per tile that share its bytes: where no spec has bytes to store,
+  uint32_t max_split;  // and at the most (while the launch is below 4 per CU)
+};
+extern "C++" {
+// check(spec, at, bad, any_values): the spec's own checks; any_values: it has bytes to store.
+// launch(a, split, st): the spec table of `a` (its other fields are filled) and the kernels.
+// empty(spec, st): the spec's offsets of a result without a row or a record, where all of them are 0.
+// Nothing is written on the device before every check has passed.
+template <class Args, class Spec, class Check, class Launch, class Empty>
+static int result_row_list(const RowListKind& k, tfrg_ctx* c, const Spec* specs, uint32_t n_specs, const RowListCall& q,
+                           const Check& check, const Launch& launch, const Empty& empty) {
+  auto bad = [&k](const std::string& why) {
+    set_error(std::string(k.fn) + ": " + why);
+    return TFRG_E_ARG;
+  };
+  if (const int rc = check_specs(c, specs, n_specs, k.max_specs, bad)) return rc;
+  bool any_values = false;
+  for (uint32_t i = 0; i < n_specs; ++i)
+    if (const int rc = check(specs[i], "spec " + std::to_string(i) + ": ", bad, any_values)) return rc;
+  if (const int rc = check_rows_dtype(q.d_rows, q.rows_dtype, false, bad)) return rc;
+  if (const int rc = check_rows_m(q.d_rows, q.m, false, bad)) return rc;
+  const uint32_t m = q.m, tile = c->ragged_tile;
+  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile;
+  uint64_t split = k.split0;
+  if (any_values && tiles) {
+    const uint64_t want = (uint64_t)std::max(c->num_cus, 1) * 4u, have = tiles * n_specs;
+    split = std::min<uint64_t>(k.max_split, std::max<uint64_t>(1, (want + have - 1) / have));
+  }
+  if (tiles * n_specs * std::max<uint64_t>(split, 1) > 0x7fffffffull)
+    return bad("too many tiles for one launch: raise the ragged tile");
+  HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = confirm_pending(c)) return rc;
+  const bool run = m && c->res.req.n;
+  DBuf& tsum = c->*k.tsum;
+  if (run) HIP_TRY(tsum.ensure((size_t)(tiles * n_specs) * k.words * 8));
+  hipStream_t st, cs;
+  if (const int rc = fence_open(c, q.consumer_stream, &st, &cs)) return rc;
+  if (q.d_stats) HIP_TRY(hipMemsetAsync(q.d_stats, 0, (size_t)n_specs * 16, st));
+  if (run) {
+    Args a{};
+    fill_columns(c, a);
+    fill_bytes_source(c, a);
+    a.stats = q.d_stats;
+    a.totals = q.d_totals;
+    a.tsum = tsum.as<uint64_t>();
+    a.rows = q.d_rows;
+    a.rows64 = q.rows_dtype == TFRG_ROWS_I64;
+    a.row0 = q.row0;
+    a.m = m;
+    a.n_specs = n_specs;
+    a.tile = tile;
+    a.tiles = (uint32_t)tiles;
+    if (const int rc = launch(a, (uint32_t)split, st)) return rc;
+  } else {
+    // no row, or no record (every row is skipped): all offsets and totals are 0
+    for (uint32_t i = 0; i < n_specs; ++i) {
+      if (const int rc = empty(specs[i], st)) return rc;
+      if (q.d_stats && m)
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(q.d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
+    }
+    if (q.d_totals) HIP_TRY(hipMemsetAsync(q.d_totals, 0, (size_t)n_specs * k.words * 8, st));
+  }
+  return fence_close(c, st, cs);
+}
+// (the spec's slot exists and is a bytes_list slot)
+template <class Bad>
+static int check_bytes_slot(const tfrg_ctx* c, const std::string& at, uint32_t slot, const Bad& bad) {
+  if (slot >= c->n_slots) return bad(at + "slot " + std::to_string(slot) + " >= n_slots");
+  const uint32_t kind = c->slot_kind_h[slot] & 3u;
+  if (kind != TFRG_KIND_BYTES)
+    return bad(at + "slot " + std::to_string(slot) + " is not a bytes_list slot (kind " + std::to_string(kind) + ")");
+  return 0;
+}
+}  // extern "C++"
+
 // Packed values + offsets for a list of rows (tfrg_ragged.h: lengths, tile scan, gather). Every grid
 // size comes from m, n_specs, the tile and the split: nothing is read back from the device.
 int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t n_specs, const void* d_rows,
                             uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
                             void* consumer_stream) {
-  auto bad = [](const std::string& why) {
-    set_error("tfrg_result_ragged_rows: " + why);
-    return TFRG_E_ARG;
-  };
-  if (const int rc = check_specs(c, specs, n_specs, TFRG_RAGGED_MAX_SPECS, bad)) return rc;
   static_assert(TFRG_RAGGED_MAX_SPECS == kRaggedMaxSpecs, "tfrg.h mirrors tfrg_ragged.h");
-  bool any_values = false;
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_ragged_spec& s = specs[i];
-    const std::string at = "spec " + std::to_string(i) + ": ";
-    if (const int rc = check_slot_dtype(c, at, s.slot, s.dtype, bad)) return rc;
-    if (!s.offsets) return bad(at + "offsets is NULL");
-    if (s.reserved) return bad(at + "reserved must be 0");
-    const uintptr_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
-    if (((uintptr_t)s.values & (isz - 1)) || ((uintptr_t)s.offsets & 7u))
-      return bad(at + "values and offsets must be aligned to their element size");
-    any_values |= s.values != nullptr && s.cap != 0;
-  }
-  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
-  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
-  const uint32_t tile = c->ragged_tile;
-  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile;
-  // workgroups per tile that share its span: up to kRaggedMaxSplit while the launch is below 4 per CU
-  uint64_t split = 1;
-  if (any_values && tiles) {
-    const uint64_t want = (uint64_t)std::max(c->num_cus, 1) * 4u, have = tiles * n_specs;
-    split = std::min<uint64_t>(kRaggedMaxSplit, std::max<uint64_t>(1, (want + have - 1) / have));
-  }
-  if (tiles * n_specs * split > 0x7fffffffull) return bad("too many tiles for one launch: raise the ragged tile");
-  HIP_TRY(hipSetDevice(c->device));
-  if (const int rc = confirm_pending(c)) return rc;
-  const bool run = m && c->res.req.n;
-  if (run) HIP_TRY(c->rg_tsum.ensure((size_t)(tiles * n_specs) * 8));
-  hipStream_t st, cs;
-  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
-  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
-  if (run) {
-    RaggedArgs a{};
-    fill_columns(c, a);
-    fill_bytes_source(c, a);
-    a.stats = d_stats;
-    a.totals = d_totals;
-    a.tsum = c->rg_tsum.as<uint64_t>();
-    a.rows = d_rows;
-    a.rows64 = rows_dtype == TFRG_ROWS_I64;
-    a.row0 = row0;
-    a.m = m;
-    a.n_specs = n_specs;
-    a.tile = tile;
-    a.tiles = (uint32_t)tiles;
-    a.split = (uint32_t)split;
-    for (uint32_t i = 0; i < n_specs; ++i) {
-      const tfrg_ragged_spec& s = specs[i];
-      RaggedSpec& d = a.sp[i];
-      d.values = s.values;
-      d.offsets = s.offsets;
-      d.cap = s.cap;
-      d.slot = s.slot;
-      d.dtype = s.dtype;
-      d.max_len = s.max_len;
-      d.const_len = const_len_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
-      d.const_off = const_off_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
-    }
-    HIP_TRY(launch_ragged(a, st));
-  } else {
-    // no row, or no record (every row is skipped): all offsets and totals are 0
-    for (uint32_t i = 0; i < n_specs; ++i) {
-      HIP_TRY(hipMemsetAsync(specs[i].offsets, 0, ((size_t)m + 1) * 8, st));
-      if (d_stats && m)
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
-    }
-    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 8, st));
-  }
-  return fence_close(c, st, cs);
+  // (the split: workgroups per tile that share its span, 1 where nothing is stored)
+  const RowListKind kind{"tfrg_result_ragged_rows", TFRG_RAGGED_MAX_SPECS, &Arena::rg_tsum, 1, 1, kRaggedMaxSplit};
+  return result_row_list<RaggedArgs>(
+      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
+      [c](const tfrg_ragged_spec& s, const std::string& at, const auto& bad, bool& any_values) -> int {
+        if (const int rc = check_slot_dtype(c, at, s.slot, s.dtype, bad)) return rc;
+        if (!s.offsets) return bad(at + "offsets is NULL");
+        if (s.reserved) return bad(at + "reserved must be 0");
+        const uintptr_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
+        if (((uintptr_t)s.values & (isz - 1)) || ((uintptr_t)s.offsets & 7u))
+          return bad(at + "values and offsets must be aligned to their element size");
+        any_values |= s.values != nullptr && s.cap != 0;
+        return 0;
+      },
+      [c, specs](RaggedArgs& a, uint32_t split, hipStream_t st) -> int {
+        a.split = split;
+        for (uint32_t i = 0; i < a.n_specs; ++i) {
+          const tfrg_ragged_spec& s = specs[i];
+          RaggedSpec& d = a.sp[i];
+          d.values = s.values;
+          d.offsets = s.offsets;
+          d.cap = s.cap;
+          d.slot = s.slot;
+          d.dtype = s.dtype;
+          d.max_len = s.max_len;
+          d.const_len = const_len_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
+          d.const_off = const_off_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
+        }
+        HIP_TRY(launch_ragged(a, st));
+        return 0;
+      },
+      [m](const tfrg_ragged_spec& s, hipStream_t st) -> int {
+        HIP_TRY(hipMemsetAsync(s.offsets, 0, ((size_t)m + 1) * 8, st));
+        return 0;
+      });
 }
 
 // Every element of a bytes_list slot for a list of rows: bytes + element offsets + row offsets
@@ -1518,89 +1571,47 @@ int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t
 int tfrg_result_ragged_elems(tfrg_ctx* c, const tfrg_elems_spec* specs, uint32_t n_specs, const void* d_rows,
                              uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
                              void* consumer_stream) {
-  auto bad = [](const std::string& why) {
-    set_error("tfrg_result_ragged_elems: " + why);
-    return TFRG_E_ARG;
-  };
-  if (const int rc = check_specs(c, specs, n_specs, TFRG_ELEMS_MAX_SPECS, bad)) return rc;
   static_assert(TFRG_ELEMS_MAX_SPECS == kElemsMaxSpecs, "tfrg.h mirrors tfrg_elems.h");
   static_assert(sizeof(tfrg_elems_spec) == 56, "tfrg.h states the size");
-  bool any_values = false;
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_elems_spec& s = specs[i];
-    const std::string at = "spec " + std::to_string(i) + ": ";
-    if (s.slot >= c->n_slots) return bad(at + "slot " + std::to_string(s.slot) + " >= n_slots");
-    const uint32_t kind = c->slot_kind_h[s.slot] & 3u;
-    if (kind != TFRG_KIND_BYTES)
-      return bad(at + "slot " + std::to_string(s.slot) + " is not a bytes_list slot (kind " + std::to_string(kind) + ")");
-    if (!s.row_offsets) return bad(at + "row_offsets is NULL");
-    if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.elem_offsets & 7u))
-      return bad(at + "row_offsets and elem_offsets must be 8-byte aligned");
-    if (s.values && !s.elem_offsets) return bad(at + "values without elem_offsets");
-    if (s.reserved) return bad(at + "reserved must be 0");
-    any_values |= s.values != nullptr && s.cap != 0 && s.elem_cap != 0;
-  }
-  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
-  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
-  const uint32_t tile = c->ragged_tile;
-  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile;
-  // workgroups per tile that share its bytes: up to kElemsMaxSplit while the launch is below 4 per CU
-  // (0: no spec has bytes to store, and the copy is not launched)
-  uint64_t split = 0;
-  if (any_values && tiles) {
-    const uint64_t want = (uint64_t)std::max(c->num_cus, 1) * 4u, have = tiles * n_specs;
-    split = std::min<uint64_t>(kElemsMaxSplit, std::max<uint64_t>(1, (want + have - 1) / have));
-  }
-  if (tiles * n_specs * std::max<uint64_t>(split, 1) > 0x7fffffffull)
-    return bad("too many tiles for one launch: raise the ragged tile");
-  HIP_TRY(hipSetDevice(c->device));
-  if (const int rc = confirm_pending(c)) return rc;
-  const bool run = m && c->res.req.n;
-  if (run) HIP_TRY(c->el_tsum.ensure((size_t)(tiles * n_specs) * 16));
-  hipStream_t st, cs;
-  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
-  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
-  if (run) {
-    ElemsArgs a{};
-    fill_columns(c, a);
-    fill_bytes_source(c, a);
-    a.stats = d_stats;
-    a.totals = d_totals;
-    a.tsum = c->el_tsum.as<uint64_t>();
-    a.rows = d_rows;
-    a.rows64 = rows_dtype == TFRG_ROWS_I64;
-    a.row0 = row0;
-    a.m = m;
-    a.n_specs = n_specs;
-    a.tile = tile;
-    a.tiles = (uint32_t)tiles;
-    a.split = (uint32_t)split;
-    for (uint32_t i = 0; i < n_specs; ++i) {
-      const tfrg_elems_spec& s = specs[i];
-      ElemsSpec& d = a.sp[i];
-      d.values = s.values;
-      d.elem_offsets = s.elem_offsets;
-      d.row_offsets = s.row_offsets;
-      d.elem_cap = s.elem_cap;
-      d.cap = s.cap;
-      d.slot = s.slot;
-      d.max_elems = s.max_elems;
-      d.max_len = s.max_len;
-      d.const_len = const_len_of(c, s.slot, true);
-      d.const_off = const_off_of(c, s.slot, true);
-    }
-    HIP_TRY(launch_elems(a, st));
-  } else {
-    // no row, or no record (every row is skipped): all offsets and totals are 0
-    for (uint32_t i = 0; i < n_specs; ++i) {
-      HIP_TRY(hipMemsetAsync(specs[i].row_offsets, 0, ((size_t)m + 1) * 8, st));
-      if (specs[i].elem_offsets) HIP_TRY(hipMemsetAsync(specs[i].elem_offsets, 0, 8, st));
-      if (d_stats && m)
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
-    }
-    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 16, st));
-  }
-  return fence_close(c, st, cs);
+  // (the split: workgroups per tile that share its bytes; 0: no spec has bytes to store, and the copy
+  // is not launched)
+  const RowListKind kind{"tfrg_result_ragged_elems", TFRG_ELEMS_MAX_SPECS, &Arena::el_tsum, 2, 0, kElemsMaxSplit};
+  return result_row_list<ElemsArgs>(
+      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
+      [c](const tfrg_elems_spec& s, const std::string& at, const auto& bad, bool& any_values) -> int {
+        if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
+        if (!s.row_offsets) return bad(at + "row_offsets is NULL");
+        if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.elem_offsets & 7u))
+          return bad(at + "row_offsets and elem_offsets must be 8-byte aligned");
+        if (s.values && !s.elem_offsets) return bad(at + "values without elem_offsets");
+        if (s.reserved) return bad(at + "reserved must be 0");
+        any_values |= s.values != nullptr && s.cap != 0 && s.elem_cap != 0;
+        return 0;
+      },
+      [c, specs](ElemsArgs& a, uint32_t split, hipStream_t st) -> int {
+        a.split = split;
+        for (uint32_t i = 0; i < a.n_specs; ++i) {
+          const tfrg_elems_spec& s = specs[i];
+          ElemsSpec& d = a.sp[i];
+          d.values = s.values;
+          d.elem_offsets = s.elem_offsets;
+          d.row_offsets = s.row_offsets;
+          d.elem_cap = s.elem_cap;
+          d.cap = s.cap;
+          d.slot = s.slot;
+          d.max_elems = s.max_elems;
+          d.max_len = s.max_len;
+          d.const_len = const_len_of(c, s.slot, true);
+          d.const_off = const_off_of(c, s.slot, true);
+        }
+        HIP_TRY(launch_elems(a, st));
+        return 0;
+      },
+      [m](const tfrg_elems_spec& s, hipStream_t st) -> int {
+        HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
+        if (s.elem_offsets) HIP_TRY(hipMemsetAsync(s.elem_offsets, 0, 8, st));
+        return 0;
+      });
 }
 
 // ---- The device half of a vocabulary (tfrg_vocab.h; the host half, tfrg_host.cpp, calls it through
@@ -1653,91 +1664,56 @@ static const bool g_vocab_device_registered = (tfrg::g_vocab_device = {vocab_upl
 int tfrg_result_elem_ids(tfrg_ctx* c, const tfrg_ids_spec* specs, uint32_t n_specs, const void* d_rows,
                          uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
                          void* consumer_stream) {
-  auto bad = [](const std::string& why) {
-    set_error("tfrg_result_elem_ids: " + why);
-    return TFRG_E_ARG;
-  };
-  if (const int rc = check_specs(c, specs, n_specs, TFRG_IDS_MAX_SPECS, bad)) return rc;
   static_assert(TFRG_IDS_MAX_SPECS == kIdsMaxSpecs, "tfrg.h mirrors tfrg_ids.h");
   static_assert(sizeof(tfrg_ids_spec) == 72, "tfrg.h states the size");
   static_assert(kIdsNoLen == kElemsNoLen && kIdsOffStored == kElemsOffStored, "const_len_of / const_off_of serve tfrg_ids.h");
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_ids_spec& s = specs[i];
-    const std::string at = "spec " + std::to_string(i) + ": ";
-    if (s.slot >= c->n_slots) return bad(at + "slot " + std::to_string(s.slot) + " >= n_slots");
-    const uint32_t kind = c->slot_kind_h[s.slot] & 3u;
-    if (kind != TFRG_KIND_BYTES)
-      return bad(at + "slot " + std::to_string(s.slot) + " is not a bytes_list slot (kind " + std::to_string(kind) + ")");
-    if (!s.row_offsets) return bad(at + "row_offsets is NULL");
-    if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.ids & 7u)) return bad(at + "row_offsets and ids must be 8-byte aligned");
-    if (s.reserved0 || s.reserved1) return bad(at + "reserved words must be 0");
-    if (!s.vocab && !s.num_oov_buckets) return bad(at + "no vocabulary and no hash buckets");
-    if (s.vocab && !s.vocab->d_mem) return bad(at + "the vocabulary was built host-only (device -1)");
-    if (s.vocab && s.vocab->device != c->device)
-      return bad(at + "the vocabulary is on device " + std::to_string(s.vocab->device) + ", the context on " +
-                 std::to_string(c->device));
-  }
-  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
-  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
-  const uint32_t tile = c->ragged_tile;
-  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile;
-  if (tiles * n_specs > 0x7fffffffull) return bad("too many tiles for one launch: raise the ragged tile");
-  HIP_TRY(hipSetDevice(c->device));
-  if (const int rc = confirm_pending(c)) return rc;
-  const bool run = m && c->res.req.n;
-  if (run) HIP_TRY(c->id_tsum.ensure((size_t)(tiles * n_specs) * 8));
-  hipStream_t st, cs;
-  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
-  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
-  if (run) {
-    IdsArgs a{};
-    fill_columns(c, a);
-    fill_bytes_source(c, a);
-    a.stats = d_stats;
-    a.totals = d_totals;
-    a.tsum = c->id_tsum.as<uint64_t>();
-    a.rows = d_rows;
-    a.rows64 = rows_dtype == TFRG_ROWS_I64;
-    a.row0 = row0;
-    a.m = m;
-    a.n_specs = n_specs;
-    a.tile = tile;
-    a.tiles = (uint32_t)tiles;
-    for (uint32_t i = 0; i < n_specs; ++i) {
-      const tfrg_ids_spec& s = specs[i];
-      IdsSpec& d = a.sp[i];
-      d.ids = s.ids;
-      d.row_offsets = s.row_offsets;
-      d.elem_cap = s.elem_cap;
-      if (const tfrg_vocab* v = s.vocab) {
-        d.table = v->d_table;
-        d.w_offs = v->d_offs;
-        d.blob = v->d_blob;
-        d.w_ids = v->d_ids;
-        d.mask = (uint32_t)v->table.size() - 1u;
-        d.max_probe = v->max_probe;
-        d.max_word = v->max_word;
-        d.blob_bound = v->d_blob_bound;
-      }
-      d.n_buckets = s.num_oov_buckets;
-      d.oov_base = s.oov_base;
-      d.default_id = s.default_id;
-      d.slot = s.slot;
-      d.max_elems = s.max_elems;
-      d.const_len = const_len_of(c, s.slot, true);
-      d.const_off = const_off_of(c, s.slot, true);
-    }
-    HIP_TRY(launch_ids(a, st));
-  } else {
-    // no row, or no record (every row is skipped): all offsets and totals are 0
-    for (uint32_t i = 0; i < n_specs; ++i) {
-      HIP_TRY(hipMemsetAsync(specs[i].row_offsets, 0, ((size_t)m + 1) * 8, st));
-      if (d_stats && m)
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
-    }
-    if (d_totals) HIP_TRY(hipMemsetAsync(d_totals, 0, (size_t)n_specs * 8, st));
-  }
-  return fence_close(c, st, cs);
+  const RowListKind kind{"tfrg_result_elem_ids", TFRG_IDS_MAX_SPECS, &Arena::id_tsum, 1, 0, 0};  // (no split)
+  return result_row_list<IdsArgs>(
+      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
+      [c](const tfrg_ids_spec& s, const std::string& at, const auto& bad, bool&) -> int {
+        if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
+        if (!s.row_offsets) return bad(at + "row_offsets is NULL");
+        if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.ids & 7u)) return bad(at + "row_offsets and ids must be 8-byte aligned");
+        if (s.reserved0 || s.reserved1) return bad(at + "reserved words must be 0");
+        if (!s.vocab && !s.num_oov_buckets) return bad(at + "no vocabulary and no hash buckets");
+        if (s.vocab && !s.vocab->d_mem) return bad(at + "the vocabulary was built host-only (device -1)");
+        if (s.vocab && s.vocab->device != c->device)
+          return bad(at + "the vocabulary is on device " + std::to_string(s.vocab->device) + ", the context on " +
+                     std::to_string(c->device));
+        return 0;
+      },
+      [c, specs](IdsArgs& a, uint32_t, hipStream_t st) -> int {
+        for (uint32_t i = 0; i < a.n_specs; ++i) {
+          const tfrg_ids_spec& s = specs[i];
+          IdsSpec& d = a.sp[i];
+          d.ids = s.ids;
+          d.row_offsets = s.row_offsets;
+          d.elem_cap = s.elem_cap;
+          if (const tfrg_vocab* v = s.vocab) {
+            d.table = v->d_table;
+            d.w_offs = v->d_offs;
+            d.blob = v->d_blob;
+            d.w_ids = v->d_ids;
+            d.mask = (uint32_t)v->table.size() - 1u;
+            d.max_probe = v->max_probe;
+            d.max_word = v->max_word;
+            d.blob_bound = v->d_blob_bound;
+          }
+          d.n_buckets = s.num_oov_buckets;
+          d.oov_base = s.oov_base;
+          d.default_id = s.default_id;
+          d.slot = s.slot;
+          d.max_elems = s.max_elems;
+          d.const_len = const_len_of(c, s.slot, true);
+          d.const_off = const_off_of(c, s.slot, true);
+        }
+        HIP_TRY(launch_ids(a, st));
+        return 0;
+      },
+      [m](const tfrg_ids_spec& s, hipStream_t st) -> int {
+        HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
+        return 0;
+      });
 }
 
 // The WHERE clause over the last result (tfrg_select.h: verdicts, tile scan, write). Every grid size

@@ -3,7 +3,8 @@
 // elements' bytes back to back (values), the E + 1 offsets of the elements in them (elem_offsets) and
 // the m + 1 offsets of the rows in elements (row_offsets). Four launches on the decode's stream, no
 // workgroup ever waiting on another (the shape of k_rg_len / k_rg_scan / k_rg_gather in tfrg_ragged.hip;
-// the row rule, the scans and the row table in LDS are those of tfrg_rows.h):
+// the row rule, the scans and the row table in LDS are those of tfrg_rows.h, the rows of elements those of
+// tfrg_elem_rows.h, shared with tfrg_ids.hip):
 //
 //   k_el_len   per (spec, tile of `tile` rows): the rows' element counts scanned into LDS, then the
 //              tile's elements shared by the lanes (lane t takes tile-local elements t, t + 256, ...
@@ -40,23 +41,24 @@
 // record 0 and drops it), and it counts in the fourth counter alone.
 #include <hip/hip_runtime.h>
 
+#include "tfrg_elem_rows.h"
 #include "tfrg_elems.h"
 #include "tfrg_internal.h"
-#include "tfrg_rows.h"
 
 namespace tfrg {
 namespace {
 
 typedef uint32_t el_u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t kBlk = 256;
+constexpr uint32_t kBlk = kElemBlk;
 
 // The kernel argument is read in place, in the constant address space (scalar loads)
 typedef const __attribute__((address_space(4))) ElemsArgs* KArgs;
 typedef const __attribute__((address_space(4))) ElemsSpec* KSpec;
 
-// the spec a workgroup works in (uniform)
+// the spec a workgroup works in (uniform), with the fields tfrg_elem_rows.h reads
 struct Sp {
+  static constexpr uint32_t kNoLen = kElemsNoLen;
   KArgs a;
   KSpec s;
   const uint32_t* rs;  // the slot's row splits; null: placed (record g holds one element, at index g)
@@ -83,108 +85,7 @@ __device__ __forceinline__ Sp make_sp(KArgs a, uint32_t si) {
   return x;
 }
 
-// One row of the output: its first `cnt` elements, element j being number src + j of the slot's column
-// (by_end: src is the record, whose one element lies at its end plus a constant)
-struct Row {
-  uint32_t cnt;  // after max_elems; 0 for a skipped row
-  uint32_t C;    // the record's element count
-  uint32_t src;
-  uint32_t ok;
-};
-
-__device__ __forceinline__ Row row_of(const Sp& x, uint32_t k) {
-  const Rec q = rec_of(x.a, x.rl.row0, x.rl.rows ? row_entry(x.rl, k) : (int64_t)k);
-  uint32_t lo = q.g, c = 1u;
-  if (x.rs) {
-    lo = x.rs[q.g];
-    c = x.rs[q.g + 1u] - lo;
-  }
-  c = q.ok ? c : 0u;  // (a skipped row is a record without an element to everything that loads)
-  Row r;
-  r.ok = q.ok;
-  r.C = c;
-  r.cnt = (x.max_elems && c > x.max_elems) ? x.max_elems : c;
-  r.src = x.by_end ? q.g : lo;
-  return r;
-}
-
-// the byte length of element j of the row whose elements start at src
-__device__ __forceinline__ uint32_t elem_L(const Sp& x, uint32_t src, uint32_t j) {
-  const uint64_t es = x.base + src + j;
-  if (x.a->b_off64) {
-    const uint64_t l = x.a->b_off64[es + 1] - x.a->b_off64[es];
-    return l < 0xffffffffull ? (uint32_t)l : 0xffffffffu;
-  }
-  return x.s->const_len != kElemsNoLen ? x.s->const_len : x.a->b_len[es];
-}
-
 __device__ __forceinline__ uint32_t clamp_len(const Sp& x, uint32_t L) { return (x.max_len && L > x.max_len) ? x.max_len : L; }
-
-// the position of its first byte in the bytes' source
-__device__ __forceinline__ uint32_t elem_off(const Sp& x, uint32_t src, uint32_t j) {
-  const uint64_t es = x.base + src + j;
-  if (x.a->b_off64) {
-    const uint64_t o0 = x.a->b_off64[es];
-    return o0 < 0xffffffffull ? (uint32_t)o0 : 0xffffffffu;
-  }
-  return x.by_end ? x.a->end32[src] + (uint32_t)x.s->const_off : x.a->b_off[es];
-}
-
-// The tile in LDS: eo[r] for r <= nrows are the absolute element offsets of its rows (eo[nrows]: of the
-// row after the tile), src[r] the row's source.
-struct Tile {
-  const uint64_t* eo;
-  const uint32_t* src;
-  uint32_t nrows;
-};
-
-// Elements per lane and pass in k_el_len and k_el_offs: the lane's kPer elements (t, t + 256, ... of the
-// pass) are searched in lockstep and their lengths loaded together, so a pass waits for one LDS chain
-// and one memory latency, not kPer of each
-constexpr uint32_t kPer = 4;
-
-// row_at for kPer elements at once: the same number of steps for each (nrows alone decides it)
-__device__ __forceinline__ void rows_at(const Tile& T, const uint64_t (&e)[kPer], uint32_t (&r)[kPer]) {
-#pragma unroll
-  for (uint32_t i = 0; i < kPer; ++i) r[i] = 0u;
-  for (uint32_t s = 1u << (31 - __builtin_clz(T.nrows)); s; s >>= 1) {
-#pragma unroll
-    for (uint32_t i = 0; i < kPer; ++i) {
-      const uint32_t mid = r[i] + s;
-      if (mid < T.nrows && T.eo[mid] <= e[i]) r[i] = mid;
-    }
-  }
-}
-
-// the tile's rows into LDS: element counts scanned from the tile's base, sources. TALLY: the three
-// per-row counters into the lane's tallies.
-template <bool TALLY>
-__device__ __forceinline__ void scan_rows(const Sp& x, uint32_t t0, uint32_t nrows, uint64_t base, const RowTable& l,
-                                          uint32_t& rtrunc, uint32_t& empty, uint32_t& skip) {
-  uint64_t carry = base;
-  for (uint32_t r0 = 0; r0 < nrows; r0 += kBlk) {
-    const uint32_t r = r0 + threadIdx.x;
-    Row w{};
-    if (r < nrows) {
-      w = row_of(x, t0 + r);
-      if constexpr (TALLY) {
-        // (branch-free: a skipped row counts in `skip` alone; its C is 0)
-        rtrunc += w.C > w.cnt;
-        empty += w.ok & (uint32_t)(w.C == 0u);
-        skip += w.ok ^ 1u;
-      }
-    }
-    uint64_t total;
-    const uint64_t ex = block_excl_scan<kBlk / 64>((uint64_t)w.cnt, l.part, &total);
-    if (r < nrows) {
-      l.offs[r] = carry + ex;
-      l.src[r] = w.src;
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) l.offs[nrows] = carry;
-  __syncthreads();
-}
 
 // ------------------------------------------------------------------ 1. counts and byte sums
 // dynamic LDS: the row table of tfrg_rows.h with part [16] u64 (elems_lds_bytes sizes it)
@@ -198,7 +99,7 @@ __global__ __launch_bounds__(kBlk) void k_el_len(const ElemsArgs) {
   const uint32_t t0 = ti * tile;
   const uint32_t nrows = a->m - t0 < tile ? a->m - t0 : tile;
   uint32_t rtrunc = 0, etrunc = 0, empty = 0, skip = 0;
-  scan_rows<true>(x, t0, nrows, 0ull, l, rtrunc, empty, skip);
+  scan_rows<true, true>(x, t0, nrows, 0ull, l, rtrunc, empty, skip);
   const Tile T{l.offs, l.src, nrows};
   const uint64_t et = l.offs[nrows];
   uint64_t sum = 0;
@@ -277,7 +178,7 @@ __global__ __launch_bounds__(kBlk) void k_el_offs(const ElemsArgs) {
   const uint64_t eb = a->tsum[blockIdx.x];
   const uint64_t bb = a->tsum[(uint64_t)a->n_specs * tiles + blockIdx.x];
   uint32_t u0 = 0, u1 = 0, u2 = 0;
-  scan_rows<false>(x, t0, nrows, eb, l, u0, u1, u2);
+  scan_rows<true, false>(x, t0, nrows, eb, l, u0, u1, u2);
   int64_t* const ro = x.s->row_offsets + t0;  // (row_offsets[m] is k_el_scan's)
   for (uint32_t r = threadIdx.x; r < nrows; r += kBlk) ro[r] = (int64_t)l.offs[r];
   int64_t* const eoffs = x.s->elem_offsets;
@@ -437,7 +338,7 @@ __global__ __launch_bounds__(kBlk) void k_el_copy(const ElemsArgs) {
   const uint32_t t0 = ti * tile;
   const uint32_t nrows = a->m - t0 < tile ? a->m - t0 : tile;
   uint32_t u0 = 0, u1 = 0, u2 = 0;
-  scan_rows<false>(x, t0, nrows, eb, l, u0, u1, u2);
+  scan_rows<true, false>(x, t0, nrows, eb, l, u0, u1, u2);
   const Tile T{l.offs, l.src, nrows};
   const uint64_t ee = l.offs[nrows];
   const Span sp{ks->elem_offsets, eb, ee < ecap ? ee : ecap};

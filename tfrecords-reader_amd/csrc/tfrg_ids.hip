@@ -1,9 +1,9 @@
 // tfrg_ids.hip — the kernels behind tfrg_result_elem_ids: for a list of m rows (row k is record
 // g = entry(k) - row0) and every requested bytes_list slot, one int64 id per element of the rows' lists
 // (the vocabulary word equal to the element's bytes, else a hash bucket, else a default) and the m + 1
-// offsets of the rows in elements. Rows, element order and row_offsets are tfrg_elems.hip's. Three
-// launches on the decode's stream, no workgroup ever waiting on another (the row rule, the scans and the
-// row table in LDS are those of tfrg_rows.h):
+// offsets of the rows in elements. Rows, element order and row_offsets are those of tfrg_elems.hip: both
+// files take them from tfrg_elem_rows.h. Three launches on the decode's stream, no workgroup ever waiting
+// on another (the row rule, the scans and the row table in LDS are those of tfrg_rows.h):
 //
 //   k_id_len    per (spec, tile of `tile` rows): the rows' element counts summed (k_el_len without the
 //               byte sums: no element is touched), the tile's sum into the scratch, and the three
@@ -32,22 +32,23 @@
 // record 0 and drops it), and it counts in the fourth counter alone.
 #include <hip/hip_runtime.h>
 
+#include "tfrg_elem_rows.h"
 #include "tfrg_ids.h"
 #include "tfrg_internal.h"
-#include "tfrg_rows.h"
 #include "tfrg_vocab.h"
 
 namespace tfrg {
 namespace {
 
-constexpr uint32_t kBlk = 256;
+constexpr uint32_t kBlk = kElemBlk;
 
 // The kernel argument is read in place, in the constant address space (scalar loads)
 typedef const __attribute__((address_space(4))) IdsArgs* KArgs;
 typedef const __attribute__((address_space(4))) IdsSpec* KSpec;
 
-// the spec a workgroup works in (uniform): tfrg_elems.hip's Sp without max_len
+// the spec a workgroup works in (uniform), with the fields tfrg_elem_rows.h reads
 struct Sp {
+  static constexpr uint32_t kNoLen = kIdsNoLen;
   KArgs a;
   KSpec s;
   const uint32_t* rs;  // the slot's row splits; null: placed (record g holds one element, at index g)
@@ -69,106 +70,6 @@ __device__ __forceinline__ Sp make_sp(KArgs a, uint32_t si) {
   x.by_end = !a->b_off64 && s->const_off != kIdsOffStored;
   x.rl = make_row_list(a);
   return x;
-}
-
-// One row of the output: its first `cnt` elements, element j being number src + j of the slot's column
-// (by_end: src is the record, whose one element lies at its end plus a constant)
-struct Row {
-  uint32_t cnt;  // after max_elems; 0 for a skipped row
-  uint32_t C;    // the record's element count
-  uint32_t src;
-  uint32_t ok;
-};
-
-__device__ __forceinline__ Row row_of(const Sp& x, uint32_t k) {
-  const Rec q = rec_of(x.a, x.rl.row0, x.rl.rows ? row_entry(x.rl, k) : (int64_t)k);
-  uint32_t lo = q.g, c = 1u;
-  if (x.rs) {
-    lo = x.rs[q.g];
-    c = x.rs[q.g + 1u] - lo;
-  }
-  c = q.ok ? c : 0u;  // (a skipped row is a record without an element to everything that loads)
-  Row r;
-  r.ok = q.ok;
-  r.C = c;
-  r.cnt = (x.max_elems && c > x.max_elems) ? x.max_elems : c;
-  r.src = x.by_end ? q.g : lo;
-  return r;
-}
-
-// the byte length of element j of the row whose elements start at src
-__device__ __forceinline__ uint32_t elem_L(const Sp& x, uint32_t src, uint32_t j) {
-  const uint64_t es = x.base + src + j;
-  if (x.a->b_off64) {
-    const uint64_t l = x.a->b_off64[es + 1] - x.a->b_off64[es];
-    return l < 0xffffffffull ? (uint32_t)l : 0xffffffffu;
-  }
-  return x.s->const_len != kIdsNoLen ? x.s->const_len : x.a->b_len[es];
-}
-
-// the position of its first byte in the bytes' source
-__device__ __forceinline__ uint32_t elem_off(const Sp& x, uint32_t src, uint32_t j) {
-  const uint64_t es = x.base + src + j;
-  if (x.a->b_off64) {
-    const uint64_t o0 = x.a->b_off64[es];
-    return o0 < 0xffffffffull ? (uint32_t)o0 : 0xffffffffu;
-  }
-  return x.by_end ? x.a->end32[src] + (uint32_t)x.s->const_off : x.a->b_off[es];
-}
-
-// Elements per lane and pass in k_id_write: the lane's kPer elements (t, t + 256, ... of the pass) are
-// searched in lockstep, their lengths and offsets loaded together and their bytes hashed in lockstep, so a
-// step waits for one memory latency, not kPer of them
-constexpr uint32_t kPer = 4;
-
-// the rows of kPer elements at once in the tile's table (eo[r] for r <= nrows: the absolute element
-// offsets of its rows): the same number of steps for each (nrows alone decides it)
-__device__ __forceinline__ void rows_at(const uint64_t* eo, uint32_t nrows, const uint64_t (&e)[kPer], uint32_t (&r)[kPer]) {
-#pragma unroll
-  for (uint32_t i = 0; i < kPer; ++i) r[i] = 0u;
-  for (uint32_t s = 1u << (31 - __builtin_clz(nrows)); s; s >>= 1) {
-#pragma unroll
-    for (uint32_t i = 0; i < kPer; ++i) {
-      const uint32_t mid = r[i] + s;
-      if (mid < nrows && eo[mid] <= e[i]) r[i] = mid;
-    }
-  }
-}
-
-// The tile's rows: element counts scanned from `base`. TABLE: into the row table in LDS, with the
-// rows' sources; TALLY: the three per-row counters into the lane's tallies. Returns base + the tile's
-// sum (to every thread).
-template <bool TABLE, bool TALLY>
-__device__ __forceinline__ uint64_t scan_rows(const Sp& x, uint32_t t0, uint32_t nrows, uint64_t base, const RowTable& l,
-                                              uint32_t& rtrunc, uint32_t& empty, uint32_t& skip) {
-  uint64_t carry = base;
-  for (uint32_t r0 = 0; r0 < nrows; r0 += kBlk) {
-    const uint32_t r = r0 + threadIdx.x;
-    Row w{};
-    if (r < nrows) {
-      w = row_of(x, t0 + r);
-      if constexpr (TALLY) {
-        // (branch-free: a skipped row counts in `skip` alone; its C is 0)
-        rtrunc += w.C > w.cnt;
-        empty += w.ok & (uint32_t)(w.C == 0u);
-        skip += w.ok ^ 1u;
-      }
-    }
-    uint64_t total;
-    const uint64_t ex = block_excl_scan<kBlk / 64>((uint64_t)w.cnt, l.part, &total);
-    if constexpr (TABLE) {
-      if (r < nrows) {
-        l.offs[r] = carry + ex;
-        l.src[r] = w.src;
-      }
-    }
-    carry += total;
-  }
-  if constexpr (TABLE) {
-    if (threadIdx.x == 0) l.offs[nrows] = carry;
-    __syncthreads();
-  }
-  return carry;
 }
 
 // ------------------------------------------------------------------ 1. counts
@@ -286,6 +187,7 @@ __global__ __launch_bounds__(kBlk) void k_id_write(const IdsArgs) {
   const uint64_t nb = ks->n_buckets;
   const bool pow2 = (nb & (nb - 1ull)) == 0ull;
   const uint32_t max_word = has_vocab ? ks->max_word : 0u;
+  const Tile T{l.offs, l.src, nrows};
   uint32_t unmatched = 0;
   for (uint64_t p0 = eb; p0 < lim; p0 += kPer * kBlk) {
     uint64_t e[kPer], h[kPer];
@@ -297,7 +199,7 @@ __global__ __launch_bounds__(kBlk) void k_id_write(const IdsArgs) {
       on[i] = e[i] < lim;
       e[i] = on[i] ? e[i] : p0;  // (an element past the tile's reads the pass's first one and drops it)
     }
-    rows_at(l.offs, nrows, e, r);
+    rows_at(T, e, r);
     uint32_t steps = 0;
 #pragma unroll
     for (uint32_t i = 0; i < kPer; ++i) {

@@ -3,7 +3,8 @@
 // tfrg_select.hip), each piece defined once. The functions that read a kernel argument are templates over
 // the pass's own pointer to it (DenseArgs, RaggedArgs, ElemsArgs, IdsArgs, SelectArgs / SelectBytesArgs in the constant
 // address space), as fill_columns<Args> is on the host: the argument structs stay apart, and only
-// the names of their common fields (info, rs, n, rows, row0, rows64, in, in_bound) are assumed.
+// the names of their common fields (info, rs, n, rows, row0, rows64, in, in_bound) are assumed. What
+// tfrg_elems.hip and tfrg_ids.hip share beyond that (a row as a run of elements) is in tfrg_elem_rows.h.
 #pragma once
 #include "tfrg_dev.h"
 

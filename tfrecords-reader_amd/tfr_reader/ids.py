@@ -22,6 +22,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from tfr_reader import _native as N
+from tfr_reader import _rowlist as RL
 from tfr_reader import dense as D
 
 IDS_STAT_NAMES = ("rows_truncated", "unmatched", "empty", "skipped")
@@ -116,7 +117,7 @@ class Vocabulary:
 
 
 @dataclass(frozen=True, eq=False)
-class ElementIds:
+class ElementIds(RL.NamedSpec):
     """One id output: every element of ``key``'s ``bytes_list`` as an int64. An element equal to a word
     of ``vocab`` gets the word's id; else, with ``num_oov_buckets``, ``oov_base + hash64(element) %
     num_oov_buckets`` (``oov_base`` default: ``len(vocab)``, or 0 without a vocabulary); else
@@ -151,20 +152,11 @@ class ElementIds:
                 raise ValueError(f"ElementIds({self.key!r}): {what} must be an int64, not {v!r}")
 
     @property
-    def out_name(self) -> str:
-        return self.name if self.name is not None else self.key
-
-    @property
     def base(self) -> int:
         """``tfrg_ids_spec.oov_base``."""
         if self.oov_base is not None:
             return int(self.oov_base)
         return len(self.vocab) if self.vocab is not None else 0
-
-    @property
-    def elems_limit(self) -> int:
-        """``tfrg_ids_spec.max_elems`` (0: every element)."""
-        return int(self.max_elems) if self.max_elems is not None else 0
 
     def id_of(self, b: bytes) -> tuple[int, bool]:
         """(the id of an element with bytes ``b``, whether a word matched it), in pure Python."""
@@ -179,47 +171,15 @@ class ElementIds:
 
 
 def check_specs(specs: Sequence[ElementIds]) -> list[ElementIds]:
-    specs = list(specs)
-    if not 1 <= len(specs) <= N.IDS_MAX_SPECS:
-        raise ValueError(f"between 1 and {N.IDS_MAX_SPECS} ElementIds specs per call, not {len(specs)}")
-    seen = set()
-    for s in specs:
-        if not isinstance(s, ElementIds):
-            raise TypeError(f"specs must be ElementIds objects, not {type(s).__name__}")
-        if s.out_name in seen:
-            raise ValueError(f"two ElementIds specs are named {s.out_name!r}: give one of them name=")
-        seen.add(s.out_name)
-    return specs
+    return RL.check_named_specs(specs, ElementIds, N.IDS_MAX_SPECS)
 
 
-class IdsBatch(dict):
+class IdsBatch(RL.RowListBatch):
     """name -> ``(ids, row_offsets)`` (torch tensors on the decoder's device, numpy arrays on the host
     path). ``capacity[name]``: the elements ``ids`` can hold; ``totals[name]``: E, the elements of the
     rows; ``stats[name]``: the four counters ``IDS_STAT_NAMES`` as a uint32 array; ``overflowed[name]``:
     E is above the capacity (the stored prefix is still right, the row offsets complete). The last
     three are read back from the device on first access."""
-
-    def __init__(self, outputs: Mapping, capacity: Mapping, totals, stats) -> None:
-        super().__init__(outputs)
-        self.capacity = dict(capacity)
-        self._totals = totals  # a dict, or a function returning it
-        self._stats = stats
-
-    @property
-    def totals(self) -> dict[str, int]:
-        if callable(self._totals):
-            self._totals = self._totals()
-        return self._totals
-
-    @property
-    def stats(self) -> dict[str, np.ndarray]:
-        if callable(self._stats):
-            self._stats = self._stats()
-        return self._stats
-
-    @property
-    def overflowed(self) -> dict[str, bool]:
-        return {k: t > self.capacity[k] for k, t in self.totals.items()}
 
 
 # ---------------------------------------------------------------------- host path (numpy)
@@ -232,6 +192,7 @@ def idsify(specs: Sequence[ElementIds], *, n: int, slot_key: Sequence[str | None
     without a slot gives all-empty rows. ``rows``: output row k is record ``rows[k]`` (any order,
     repeats allowed; IndexError for one outside [0, n))."""
     specs = check_specs(specs)
+    cols = RL.BytesColumns(slot_key, slot_kind, row_splits, slot_base, bytes_off, bytes_len, buf, bytes_data, bytes_offsets)
     picked = list(range(n)) if rows is None else D.host_rows(rows, n).tolist()
     m = len(picked)
     outputs, totals, stats = {}, {}, {}
@@ -239,30 +200,14 @@ def idsify(specs: Sequence[ElementIds], *, n: int, slot_key: Sequence[str | None
         ids: list[int] = []
         row_offsets = np.zeros(m + 1, np.int64)
         st = np.zeros(4, np.uint32)
-        s = D.find_slot(slot_key, slot_kind, sp.key, 1)
-        if s is None:
-            st[2] = m
-        else:
-            base = int(slot_base[s])
-            rs = np.asarray(row_splits[s]).astype(np.int64)
-            for k, g in enumerate(picked):
-                lo, c = base + int(rs[g]), int(rs[g + 1] - rs[g])
-                st[2] += c == 0
-                cnt = c
-                if sp.max_elems is not None and c > sp.max_elems:
-                    cnt = int(sp.max_elems)
-                    st[0] += 1
-                for e in range(lo, lo + cnt):
-                    if bytes_data is not None:
-                        elem = bytes(np.asarray(bytes_data[int(bytes_offsets[e]) : int(bytes_offsets[e + 1])], np.uint8))
-                    else:
-                        o, ln = int(bytes_off[e]), int(bytes_len[e])
-                        elem = bytes(np.asarray(buf[o : o + ln], np.uint8))
-                        elem += bytes(ln - len(elem))  # (a view past the input reads zeros)
-                    i, hit = sp.id_of(elem)
-                    st[1] += not hit
-                    ids.append(i)
-                row_offsets[k + 1] = row_offsets[k] + cnt
+        for k, c, elems in cols.rows(sp.key, sp.max_elems, picked):
+            st[0] += c > len(elems)
+            st[2] += c == 0
+            for elem in elems:
+                i, hit = sp.id_of(elem.tobytes())
+                st[1] += not hit
+                ids.append(i)
+            row_offsets[k + 1] = row_offsets[k] + len(elems)
         k = sp.out_name
         outputs[k] = (np.asarray(ids, np.int64).reshape(-1), row_offsets)
         totals[k] = len(ids)
@@ -322,108 +267,11 @@ def decoder_element_ids(dec, specs: Sequence[ElementIds], *, rows=None, capacity
         if sp.vocab is not None and sp.vocab.device != dec.device:
             raise ValueError(f"ElementIds({sp.key!r}): its vocabulary was made with device={sp.vocab.device}, "
                              f"the decoder is on device {dec.device}")
-    n = D.last_n(dec)
-    dev = torch.device("cuda", dec.device)
-    consumer = D.ConsumerStream.wrapping(stream, dev)
-    with torch.cuda.device(dev), torch.cuda.stream(consumer.cur):
-        d_rows, m = (None, n) if rows is None else D.device_rows(rows, n, dec.device)
-        rw = D.rows_arg(d_rows) if d_rows is not None else None
-
-        def call(items, totals_t, stats_t) -> None:  # (the consumer is ordered around each call)
-            consumer.begin()
-            launch_ids(dec, items, rw, m, 0, totals_t.data_ptr(), stats_t.data_ptr() if stats_t is not None else None,
-                       consumer.handle)
-            consumer.end()
-
-        def i64_ok(t, shape0: int | None) -> bool:
-            return (t.dim() == 1 and t.dtype == torch.int64 and t.device == dev and t.is_contiguous()
-                    and (shape0 is None or t.numel() == shape0))
-
-        caps: dict[str, int | None] = {}
-        idt: dict = {}
-        roffs: dict = {}
-        present: list[tuple[ElementIds, int]] = []
-        absent: list[ElementIds] = []  # key not in the key table, or no record: all-empty rows, no launch
-        for sp in specs:
-            k = sp.out_name
-            given = (out or {}).get(k)
-            v = r = None
-            if given is not None:
-                v, r = given
-                if not i64_ok(v, None):
-                    raise ValueError(f"out[{k!r}] ids must be a contiguous 1-D int64 tensor on {dev}")
-                if not i64_ok(r, m + 1):
-                    raise ValueError(f"out[{k!r}] row_offsets must be a contiguous int64 tensor of shape ({m + 1},) on {dev}")
-                caps[k] = int(v.numel())
-            else:
-                caps[k] = _capacity(capacity.get(k) if isinstance(capacity, Mapping) else capacity, "capacity")
-            slot = D.resolve_slot(dec, sp) if n else None
-            if slot is None:
-                absent.append(sp)
-                caps[k] = caps[k] or 0
-                if v is None:
-                    v = torch.empty(caps[k], dtype=torch.int64, device=dev)
-                if r is None:
-                    r = torch.zeros(m + 1, dtype=torch.int64, device=dev)
-                else:
-                    r.zero_()
-            else:
-                present.append((sp, slot))
-                if r is None:
-                    r = torch.empty(m + 1, dtype=torch.int64, device=dev)
-            idt[k], roffs[k] = v, r
-        # the skipped rows of a spec without a launch (as decoder_ragged)
-        absent_skipped = m if not n else 0
-        if absent and n and isinstance(rows, torch.Tensor):
-            absent_skipped = ((d_rows < 0) | (d_rows >= n)).sum()
-
-        kp = len(present)
-        host_totals = None
-        totals_t = stats_t = None
-        if kp:
-            totals_t = torch.empty(kp, dtype=torch.int64, device=dev)
-            stats_t = torch.empty((kp, 4), dtype=torch.int32, device=dev)
-
-            def items(with_ids: bool) -> list:
-                got = []
-                for sp, slot in present:
-                    k = sp.out_name
-                    v = idt[k] if with_ids else None
-                    got.append((slot, sp.elems_limit, sp.vocab._handle().value if sp.vocab is not None else None,
-                                int(sp.num_oov_buckets), sp.base, int(sp.default_id), int(v.numel()) if v is not None else 0,
-                                v.data_ptr() if v is not None and v.numel() else None, roffs[k].data_ptr()))
-                return got
-
-            if any(caps[sp.out_name] is None for sp, _ in present):
-                call(items(False), totals_t, None)
-                host_totals = [int(t) for t in totals_t.cpu().tolist()]  # the step's one synchronisation
-                for (sp, _), t in zip(present, host_totals):
-                    if caps[sp.out_name] is None:
-                        caps[sp.out_name] = t
-            for sp, _ in present:
-                k = sp.out_name
-                if idt[k] is None:
-                    idt[k] = torch.empty(caps[k], dtype=torch.int64, device=dev)
-            call(items(True), totals_t, stats_t)
-
-    names = [sp.out_name for sp, _ in present]
-
-    def totals() -> dict:
-        got = {sp.out_name: 0 for sp in absent}
-        if kp:
-            host = host_totals if host_totals is not None else totals_t.cpu().tolist()
-            got.update({k: int(t) for k, t in zip(names, host)})
-        return {sp.out_name: got[sp.out_name] for sp in specs}
-
-    def stats() -> dict:
-        got = {}
-        if absent:
-            bad = int(absent_skipped)
-            for sp in absent:
-                got[sp.out_name] = np.array([0, 0, m - bad, bad], np.uint32)
-        if kp:
-            host = stats_t.cpu().numpy().view(np.uint32)
-            got.update({k: host[i].copy() for i, k in enumerate(names)})
-        return {sp.out_name: got[sp.out_name] for sp in specs}
-
-    return IdsBatch({sp.out_name: (idt[sp.out_name], roffs[sp.out_name]) for sp in specs}, caps, totals, stats)
+    kind = RL.OutputKind(
+        parts=lambda sp: (RL.Part("ids", torch.int64, lambda cap: cap, "1-D int64 tensor"),),
+        offsets="row_offsets", capacity=_capacity, cap_of=lambda v: int(v.numel()), no_cap=0,
+        item=lambda sp, slot, ts, r: (slot, sp.elems_limit, sp.vocab._handle().value if sp.vocab is not None else None,
+                                      int(sp.num_oov_buckets), sp.base, int(sp.default_id), RL.numel(ts[0]), RL.ptr(ts[0]),
+                                      r.data_ptr()),
+        launch=launch_ids, width=1, empty_stat=2, batch=IdsBatch)
+    return RL.run(dec, specs, kind, rows=rows, capacity=capacity, out=out, stream=stream)
