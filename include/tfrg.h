@@ -421,6 +421,71 @@ int tfrg_result_dense_rows(tfrg_ctx* ctx, const tfrg_dense_spec* specs, uint32_t
                            uint32_t rows_dtype, uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped,
                            void* consumer_stream);
 
+/* Raw tensors from bytes features: a tensor stored as bytes (image.tobytes(), int16 PCM, a float16
+ * feature map) decoded, cast, normalised and laid out for a list of rows in one launch -- what
+ * tf.io.decode_raw + tf.cast + a per-channel normalise + an HWC -> CHW transpose compute. Outputs are
+ * [m][count] of the output type, lengths [m]. Rows (d_rows, rows_dtype, m, row0, skipped rows left
+ * unwritten and counted in d_skipped[spec]) are tfrg_result_dense_rows's; a NULL d_rows is the identity
+ * list (entry k is k; rows_dtype is then ignored), as in tfrg_result_ragged_rows. Per spec and output
+ * row k whose record g is not skipped:
+ *   the element is element 0 of record g's list, L its byte length (0: the list is empty or absent),
+ *     esz the size of the source type (src: little-endian, as tf.io.decode_raw's default). Source
+ *     element j exists iff (j + 1) * esz <= L: a trailing partial element does not. The element's bytes
+ *     are those tfrg_result_dense (TFRG_DENSE_U8) reads for it: bytes past the readable input are zero;
+ *   for j < count: where element j does not exist the value is `fill` (raw low bits in the OUTPUT type,
+ *     not transformed). With TFRG_RAW_OUT_SAME the source bytes are copied unchanged (NaN payloads
+ *     included; scale and bias are ignored). Otherwise, with c = j % channels, v = (float)x (round to
+ *     nearest even; exact for every source type but I32) and y = fmaf(v, scale[c], bias[c]) (one
+ *     rounding), the value is y as float32, or y rounded to nearest even to float16 / bfloat16. A NaN
+ *     source gives a NaN;
+ *   it is stored at out[k][j] (planar 0), or at out[k][c][j / channels] with planes of count / channels
+ *     elements (planar 1: HWC -> CHW);
+ *   lengths[k] = L, in bytes.
+ * d_stats (device, [n_specs][4] u32, or NULL; zeroed by the call on the stream): as tfrg_result_dense's
+ * for bytes slots with count * esz in the place of width: rows with L > count * esz (truncated),
+ * L < count * esz (padded), without an element (empty), with more than one (multi).
+ * One launch for all specs. m == 0 launches nothing; with n == 0 every row is skipped. Stream order,
+ * confirmation of an optimistic or hinted decode (the only host synchronisation, once per decode), the
+ * columns that are neither written nor read, any number of calls per decode and the full view afterwards
+ * are as for tfrg_result_dense.
+ * TFRG_E_ARG (text in tfrg_last_error): no result, n_specs outside 1..TFRG_RAW_MAX_SPECS, a slot >=
+ * n_slots or not a bytes_list slot, an unknown src or out, count outside 1..TFRG_RAW_MAX_COUNT, channels
+ * outside 1..TFRG_RAW_MAX_CHANNELS, count not a multiple of channels, planar above 1, a NULL out_ptr, an
+ * out_ptr not aligned to the output element size, a nonzero reserved, an unknown rows_dtype with a
+ * non-NULL d_rows, m >= 2^31. */
+#define TFRG_RAW_U8 0
+#define TFRG_RAW_I8 1
+#define TFRG_RAW_U16 2
+#define TFRG_RAW_I16 3
+#define TFRG_RAW_I32 4
+#define TFRG_RAW_F16 5
+#define TFRG_RAW_BF16 6
+#define TFRG_RAW_F32 7
+#define TFRG_RAW_OUT_F32 0
+#define TFRG_RAW_OUT_F16 1
+#define TFRG_RAW_OUT_BF16 2
+#define TFRG_RAW_OUT_SAME 3 /* the source type, bit for bit */
+#define TFRG_RAW_MAX_SPECS 16
+#define TFRG_RAW_MAX_COUNT 16777216 /* 2^24 */
+#define TFRG_RAW_MAX_CHANNELS 16
+typedef struct tfrg_raw_spec {
+  uint32_t slot;      /* column, as in tfrg_set_schema: a bytes_list slot */
+  uint32_t src;       /* TFRG_RAW_U8 .. TFRG_RAW_F32 */
+  uint32_t out;       /* TFRG_RAW_OUT_* */
+  uint32_t count;     /* elements per output row, 1..TFRG_RAW_MAX_COUNT, a multiple of channels */
+  uint32_t channels;  /* 1..TFRG_RAW_MAX_CHANNELS */
+  uint32_t planar;    /* 0: out[k][j]; 1: out[k][j % channels][j / channels] */
+  uint32_t fill;      /* raw low bits of the pad value, in the output type */
+  uint32_t reserved;  /* 0 */
+  float scale[16];    /* per channel */
+  float bias[16];
+  void* out_ptr;      /* device, [m][count] of the output type, caller-owned */
+  int32_t* lengths;   /* device [m], or NULL */
+} tfrg_raw_spec;      /* 176 bytes */
+int tfrg_result_raw_rows(tfrg_ctx* ctx, const tfrg_raw_spec* specs, uint32_t n_specs, const void* d_rows,
+                         uint32_t rows_dtype, uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped,
+                         void* consumer_stream);
+
 /* Ragged minibatches: packed values and offsets for a list of rows (the tf.io.parse_example
  * VarLenFeature / RaggedTensor side, next to the FixedLenFeature side above; the packed form varlen
  * attention, jagged tensors and EmbeddingBag take). Per spec and output row k < m, with

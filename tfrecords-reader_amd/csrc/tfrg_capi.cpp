@@ -15,6 +15,7 @@
 #include "../../include/tfrg.h"
 #include "crc32c.h"
 #include "tfrg_dense.h"
+#include "tfrg_raw.h"
 #include "tfrg_elems.h"
 #include "tfrg_ids.h"
 #include "tfrg_ragged.h"
@@ -1521,6 +1522,94 @@ static int check_bytes_slot(const tfrg_ctx* c, const std::string& at, uint32_t s
   return 0;
 }
 }  // extern "C++"
+
+// Raw tensors from bytes features for a list of rows (tfrg_raw.h): one launch, all specs. The checks,
+// the column view, the confirmation and the consumer fence are the ones above; what is its own is the
+// spec table and the split into work items.
+int tfrg_result_raw_rows(tfrg_ctx* c, const tfrg_raw_spec* specs, uint32_t n_specs, const void* d_rows,
+                         uint32_t rows_dtype, uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped,
+                         void* consumer_stream) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_result_raw_rows: " + why);
+    return TFRG_E_ARG;
+  };
+  static_assert(TFRG_RAW_MAX_SPECS == kRawMaxSpecs && TFRG_RAW_MAX_COUNT == kRawMaxCount &&
+                    TFRG_RAW_MAX_CHANNELS == kRawMaxChannels && TFRG_RAW_U8 == kRawU8 && TFRG_RAW_I8 == kRawI8 &&
+                    TFRG_RAW_U16 == kRawU16 && TFRG_RAW_I16 == kRawI16 && TFRG_RAW_I32 == kRawI32 &&
+                    TFRG_RAW_F16 == kRawF16 && TFRG_RAW_BF16 == kRawBF16 && TFRG_RAW_F32 == kRawF32 &&
+                    TFRG_RAW_OUT_F32 == kRawOutF32 && TFRG_RAW_OUT_F16 == kRawOutF16 &&
+                    TFRG_RAW_OUT_BF16 == kRawOutBF16 && TFRG_RAW_OUT_SAME == kRawOutSame,
+                "tfrg.h mirrors tfrg_raw.h");
+  static_assert(sizeof(tfrg_raw_spec) == 176, "tfrg.h states the size");
+  static_assert(kRawNoLen == kDenseNoLen && kRawOffStored == kDenseOffStored, "const_len_of / const_off_of serve k_raw");
+  if (const int rc = check_specs(c, specs, n_specs, TFRG_RAW_MAX_SPECS, bad)) return rc;
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_raw_spec& s = specs[i];
+    const std::string at = "spec " + std::to_string(i) + ": ";
+    if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
+    if (s.src >= kRawSrcs) return bad(at + "unknown src " + std::to_string(s.src));
+    if (s.out >= kRawOuts) return bad(at + "unknown out " + std::to_string(s.out));
+    if (s.count == 0 || s.count > TFRG_RAW_MAX_COUNT) return bad(at + "count must be 1.." + std::to_string(TFRG_RAW_MAX_COUNT));
+    if (s.channels == 0 || s.channels > TFRG_RAW_MAX_CHANNELS)
+      return bad(at + "channels must be 1.." + std::to_string(TFRG_RAW_MAX_CHANNELS));
+    if (s.count % s.channels) return bad(at + "count must be a multiple of channels");
+    if (s.planar > 1) return bad(at + "planar must be 0 or 1");
+    if (!s.out_ptr) return bad(at + "out_ptr is NULL");
+    if ((uintptr_t)s.out_ptr & (raw_out_size(s.src, s.out) - 1u)) return bad(at + "out_ptr must be aligned to the output element size");
+    if (s.reserved) return bad(at + "reserved must be 0");
+  }
+  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
+  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = confirm_pending(c)) return rc;
+  RawArgs a{};
+  a.rows = d_rows;
+  a.rows64 = d_rows && rows_dtype == TFRG_ROWS_I64;
+  a.m = m;
+  a.row0 = row0;
+  a.skipped = d_skipped;
+  fill_columns(c, a);
+  fill_bytes_source(c, a);
+  a.stats = d_stats;
+  a.n_specs = n_specs;
+  a.nt = (uint32_t)c->sw.dense_nt;
+  // workgroups per spec: one per work item (wide rows: kRawSpan tiles; narrow rows: four rows, a wave
+  // each), within an even share of 32 per CU; they stride over what is left
+  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 32u / n_specs);
+  uint32_t blocks = 0;
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_raw_spec& s = specs[i];
+    RawSpec& d = a.sp[i];
+    const uint32_t osz = raw_out_size(s.src, s.out);
+    d.out = s.out_ptr;
+    d.lengths = s.lengths;
+    d.fill = osz == 4 ? s.fill : s.fill & ((1u << (8 * osz)) - 1u);
+    d.slot = s.slot;
+    d.src = s.src;
+    d.outt = s.out;
+    d.count = s.count;
+    d.channels = s.channels;
+    d.planar = s.planar;
+    d.const_len = const_len_of(c, s.slot, true);
+    d.const_off = const_off_of(c, s.slot, true);
+    const uint32_t tp = raw_tile_pixels(s.channels), tiles = (s.count / s.channels + tp - 1) / tp;
+    d.spans = (tiles + kRawSpan - 1) / kRawSpan;
+    const uint64_t work = s.count > kRawNarrow ? (uint64_t)m * d.spans : ((uint64_t)m + 3) / 4;
+    d.blk0 = blocks;
+    d.nblk = (uint32_t)std::min<uint64_t>(cap, work);
+    blocks += d.nblk;
+    memcpy(d.scale, s.scale, sizeof d.scale);
+    memcpy(d.bias, s.bias, sizeof d.bias);
+  }
+  hipStream_t st, cs;
+  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
+  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
+  // (a row list over an empty result: no record to read, every row is skipped)
+  if (d_skipped)
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_skipped), c->res.req.n ? 0 : (int)m, n_specs, st));
+  if (m && c->res.req.n) HIP_TRY(launch_raw(a, blocks, st));
+  return fence_close(c, st, cs);
+}
 
 // Packed values + offsets for a list of rows (tfrg_ragged.h: lengths, tile scan, gather). Every grid
 // size comes from m, n_specs, the tile and the split: nothing is read back from the device.

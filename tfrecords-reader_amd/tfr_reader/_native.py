@@ -119,6 +119,32 @@ ROWS_I32 = 0  # tfrg_result_dense_rows: the row list's element type (TFRG_ROWS_*
 ROWS_I64 = 1
 
 
+class TfrgRawSpec(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("src", C.c_uint32),
+        ("out", C.c_uint32),
+        ("count", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("planar", C.c_uint32),
+        ("fill", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("scale", C.c_float * 16),
+        ("bias", C.c_float * 16),
+        ("out_ptr", C.c_void_p),
+        ("lengths", C.c_void_p),
+    ]
+
+
+RAW_U8, RAW_I8, RAW_U16, RAW_I16, RAW_I32, RAW_F16, RAW_BF16, RAW_F32 = range(8)  # tfrg_raw_spec.src (TFRG_RAW_*)
+RAW_OUT_F32, RAW_OUT_F16, RAW_OUT_BF16, RAW_OUT_SAME = range(4)  # tfrg_raw_spec.out
+RAW_MAX_SPECS = 16
+RAW_MAX_COUNT = 1 << 24
+RAW_MAX_CHANNELS = 16
+RAW_TILE = 4096  # (csrc/tfrg_raw.h: a tile's elements at the most, and the rows a single wave takes)
+RAW_NARROW = 1024
+
+
 class TfrgRaggedSpec(C.Structure):
     _fields_ = [
         ("slot", C.c_uint32),
@@ -301,6 +327,8 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_result_dense": (C.c_int, [C.c_void_p, C.POINTER(TfrgDenseSpec), C.c_uint32, C.c_void_p, C.c_void_p]),
     "tfrg_result_dense_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgDenseSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tfrg_result_raw_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgRawSpec), C.c_uint32, C.c_void_p, C.c_uint32,
+                                       C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_result_ragged_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgRaggedSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_ctx_set_ragged_tile": (C.c_int, [C.c_void_p, C.c_uint32]),

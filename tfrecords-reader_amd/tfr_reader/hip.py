@@ -542,6 +542,16 @@ class HipDecoder:
 
         return I.decoder_element_ids(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
 
+    def raw(self, specs, rows=None, out=None, stream: int | None = None, strict: bool = False):
+        """Tensors stored as bytes (``image.tobytes()``, PCM, a float16 feature map) of the last decode,
+        decoded, cast, scaled per channel and laid out -- ``[m, *shape]``, or planar ``[m, channels,
+        *shape[:-1]]`` -- as torch tensors on this decoder's device, one per ``tfr_reader.raw.Raw`` spec, for
+        every record or for the list ``rows``, in one launch (tfrg_result_raw_rows); see
+        ``tfr_reader.raw.decoder_raw``."""
+        from tfr_reader import raw as W  # noqa: PLC0415
+
+        return W.decoder_raw(self, specs, rows=rows, out=out, stream=stream, strict=strict)
+
     def ragged_minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False, capacity=None,
                            where=None):
         """One epoch of shuffled ``batch_size``-row ``RaggedBatch``es over the last decode (``where``:
@@ -861,6 +871,14 @@ class BatchResult:
         from tfr_reader import ids as I  # noqa: PLC0415, N812
 
         return I.batch_element_ids(self, specs, rows)
+
+    def raw(self, specs, rows=None):
+        """The outputs of ``tfr_reader.raw.Raw`` specs as numpy arrays from the fetched columns (the host
+        counterpart of ``HipDecoder.raw``): a ``DenseBatch`` with ``.lengths`` and ``.stats``; bfloat16
+        outputs as their uint16 bits. ``rows``: as for ``dense``."""
+        from tfr_reader import raw as W  # noqa: PLC0415
+
+        return W.batch_raw(self, specs, rows)
 
     def select(self, where, rows=None, row0: int = 0):
         """The candidates that pass ``where`` (``tfr_reader.select.Term``s), from the fetched columns

@@ -385,6 +385,14 @@ class ShardDecoder:
 
         return D.shard_dense(self, plan, specs, strict=strict, out=out, stream=stream, rows=rows)
 
+    def raw(self, plan: np.ndarray, specs, rows=None, out=None, stream: int | None = None, strict: bool = False):
+        """The last ``decode_device`` / ``decode_device32`` as raw-tensor outputs over the whole plan
+        (``tfr_reader.raw.Raw`` specs): every batch's context takes the row list (None: the plan's rows in
+        order) with its ``row0`` and writes the rows whose record it holds; see ``tfr_reader.raw.shard_raw``."""
+        from tfr_reader import raw as W  # noqa: PLC0415
+
+        return W.shard_raw(self, plan, specs, rows=rows, out=out, stream=stream, strict=strict)
+
     def minibatches(self, plan: np.ndarray, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False,
                     where=None):
         """One epoch of shuffled ``batch_size``-row ``DenseBatch``es over the plan's last decode
