@@ -486,6 +486,73 @@ int tfrg_result_raw_rows(tfrg_ctx* ctx, const tfrg_raw_spec* specs, uint32_t n_s
                          uint32_t rows_dtype, uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped,
                          void* consumer_stream);
 
+/* Resized raw images: per-record H x W, crop, flip, resample to a fixed size, normalise. Element 0 of a
+ * bytes_list slot is an image of H x W x channels elements of the source type, interleaved (HWC),
+ * little-endian; H and W are value 0 of two int64_list slots of the same record (or constants). Per spec
+ * and list entry k whose record g is not skipped, the crop window d_boxes[k] (top, left, height, width;
+ * NULL: the whole image), mirrored left-right where d_flip[k] is nonzero, is resampled to out_h x out_w
+ * and written as out[k][oy][ox][c] (planar 0) or out[k][c][oy][ox] (planar 1) -- what tf.image.resize /
+ * crop_and_resize / RandomResizedCrop + RandomHorizontalFlip and a per-channel normalise compute, in one
+ * launch for all specs. d_boxes and d_flip belong to the list entry, not to the record (a record drawn
+ * twice may get two crops), and are shared by all specs of the call (an image and its mask get the same
+ * geometry). Rows (d_rows, rows_dtype, m, row0, NULL = identity, skipped rows left unwritten and counted in
+ * d_skipped[spec]), stream order, confirmation of an optimistic or hinted decode and any number of calls
+ * per decode are as for tfrg_result_raw_rows.
+ * With H, W the declared shape, L the element's byte length (0 without an element) and esz the size of
+ * the source type:
+ *   bad shape (the row is all `fill`; d_stats[spec][0]): the height or width list is empty, H or W is
+ *     outside 1..TFRG_RESIZE_MAX_SRC, or H * W * channels * esz > L;
+ *   bad box (all `fill`; d_stats[spec][1]): a non-positive extent, a box not inside the image, or
+ *     width * channels * esz > TFRG_RESIZE_MAX_ROW_BYTES. A box is never clipped;
+ *   d_stats[spec][2]: rows without an element (they are bad-shape rows too); d_stats[spec][3]: rows with
+ *     H and W in range and L > H * W * channels * esz (they decode).
+ *   shapes[k] = (H, W) as read (clamped to int32; 0 for an empty list), bad rows included.
+ * Coordinates, in integers: for an axis with source extent n (the box's), output extent N and output
+ * index o (a flipped row's x axis: o' = out_w - 1 - o): num = (2 * o + 1) * n - N, den = 2 * N; num < 0:
+ * i0 = 0, f = 0; else i0 = num / den, f = (float)(num % den) / (float)den; then i0 >= n - 1: i0 = i1 =
+ * n - 1, f = 0; else i1 = i0 + 1. (Half-pixel centres without antialiasing: tf.image.resize "bilinear",
+ * F.interpolate(mode="bilinear", align_corners=False).) Nearest: i = min(((2 * o + 1) * n) / (2 * N), n - 1).
+ * Arithmetic, v the source element as float32 (as tfrg_result_raw_rows converts it): h = fmaf(fx, v[i1] -
+ * v[i0], v[i0]) along x, r = fmaf(fy, h1 - h0, h0) along y, y = fmaf(r, scale[c], bias[c]), then one
+ * round-to-nearest-even to float16 / bfloat16 where asked. Nearest takes v[i] for r; with
+ * TFRG_RAW_OUT_SAME it copies the element's bits.
+ * TFRG_E_ARG (text in tfrg_last_error): what tfrg_result_raw_rows refuses of the arguments both have, an
+ * h_slot / w_slot that is neither TFRG_RESIZE_CONST nor an int64_list slot, a constant extent outside
+ * 1..TFRG_RESIZE_MAX_SRC, out_h or out_w outside 1..TFRG_RESIZE_MAX_OUT, out_w * channels above
+ * TFRG_RESIZE_MAX_OUT, channels outside 1..TFRG_RESIZE_MAX_CHANNELS, an unknown interp,
+ * TFRG_RAW_OUT_SAME with bilinear, a shapes pointer that is not 4-byte aligned. */
+#define TFRG_RESIZE_BILINEAR 0
+#define TFRG_RESIZE_NEAREST 1
+#define TFRG_RESIZE_CONST 0xffffffffu /* h_slot / w_slot: the extent is src_h / src_w */
+#define TFRG_RESIZE_MAX_SPECS 16
+#define TFRG_RESIZE_MAX_CHANNELS 4
+#define TFRG_RESIZE_MAX_OUT 4096
+#define TFRG_RESIZE_MAX_SRC 16384
+#define TFRG_RESIZE_MAX_ROW_BYTES 16384
+typedef struct tfrg_resize_spec {
+  uint32_t slot;      /* a bytes_list slot: the image is element 0 */
+  uint32_t src;       /* TFRG_RAW_U8 .. TFRG_RAW_F32 */
+  uint32_t out;       /* TFRG_RAW_OUT_*; TFRG_RAW_OUT_SAME with TFRG_RESIZE_NEAREST only */
+  uint32_t channels;  /* 1..TFRG_RESIZE_MAX_CHANNELS */
+  uint32_t h_slot;    /* int64_list slots whose value 0 is the record's height / width, */
+  uint32_t w_slot;    /*   or TFRG_RESIZE_CONST */
+  uint32_t src_h;     /* the height / width of every record, for TFRG_RESIZE_CONST */
+  uint32_t src_w;
+  uint32_t out_h;     /* 1..TFRG_RESIZE_MAX_OUT */
+  uint32_t out_w;     /* 1..TFRG_RESIZE_MAX_OUT, out_w * channels <= TFRG_RESIZE_MAX_OUT */
+  uint32_t interp;    /* TFRG_RESIZE_BILINEAR / TFRG_RESIZE_NEAREST */
+  uint32_t planar;    /* 0: out[k][oy][ox][c]; 1: out[k][c][oy][ox] */
+  uint32_t fill;      /* raw low bits of a bad row's value, in the output type */
+  uint32_t reserved;  /* 0 */
+  float scale[4];     /* per channel */
+  float bias[4];
+  void* out_ptr;      /* device, [m][out_h * out_w * channels] of the output type, caller-owned */
+  int32_t* shapes;    /* device [m][2] (H, W), or NULL */
+} tfrg_resize_spec;   /* 104 bytes */
+int tfrg_result_raw_resize(tfrg_ctx* ctx, const tfrg_resize_spec* specs, uint32_t n_specs, const void* d_rows,
+                           uint32_t rows_dtype, uint32_t m, int64_t row0, const int32_t* d_boxes,
+                           const uint8_t* d_flip, uint32_t* d_stats, uint32_t* d_skipped, void* consumer_stream);
+
 /* Ragged minibatches: packed values and offsets for a list of rows (the tf.io.parse_example
  * VarLenFeature / RaggedTensor side, next to the FixedLenFeature side above; the packed form varlen
  * attention, jagged tensors and EmbeddingBag take). Per spec and output row k < m, with

@@ -16,6 +16,7 @@
 #include "crc32c.h"
 #include "tfrg_dense.h"
 #include "tfrg_raw.h"
+#include "tfrg_resize.h"
 #include "tfrg_elems.h"
 #include "tfrg_ids.h"
 #include "tfrg_ragged.h"
@@ -1608,6 +1609,117 @@ int tfrg_result_raw_rows(tfrg_ctx* c, const tfrg_raw_spec* specs, uint32_t n_spe
   if (d_skipped)
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_skipped), c->res.req.n ? 0 : (int)m, n_specs, st));
   if (m && c->res.req.n) HIP_TRY(launch_raw(a, blocks, st));
+  return fence_close(c, st, cs);
+}
+
+// Resized raw images for a list of rows (tfrg_resize.h): one launch, all specs. The frame is
+// tfrg_result_raw_rows's; its own are the int64 slots of the shape, the geometry of the outputs, the
+// split into bands and the launch's LDS.
+int tfrg_result_raw_resize(tfrg_ctx* c, const tfrg_resize_spec* specs, uint32_t n_specs, const void* d_rows,
+                           uint32_t rows_dtype, uint32_t m, int64_t row0, const int32_t* d_boxes,
+                           const uint8_t* d_flip, uint32_t* d_stats, uint32_t* d_skipped, void* consumer_stream) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_result_raw_resize: " + why);
+    return TFRG_E_ARG;
+  };
+  static_assert(TFRG_RESIZE_MAX_SPECS == kResizeMaxSpecs && TFRG_RESIZE_MAX_CHANNELS == kResizeMaxChannels &&
+                    TFRG_RESIZE_MAX_OUT == kResizeMaxOut && TFRG_RESIZE_MAX_SRC == kResizeMaxSrc &&
+                    TFRG_RESIZE_MAX_ROW_BYTES == kResizeMaxRowBytes && TFRG_RESIZE_CONST == kResizeConst &&
+                    TFRG_RESIZE_BILINEAR == kResizeBilinear && TFRG_RESIZE_NEAREST == kResizeNearest,
+                "tfrg.h mirrors tfrg_resize.h");
+  static_assert(sizeof(tfrg_resize_spec) == 104, "tfrg.h states the size");
+  if (const int rc = check_specs(c, specs, n_specs, TFRG_RESIZE_MAX_SPECS, bad)) return rc;
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_resize_spec& s = specs[i];
+    const std::string at = "spec " + std::to_string(i) + ": ";
+    if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
+    if (s.src >= kRawSrcs) return bad(at + "unknown src " + std::to_string(s.src));
+    if (s.out >= kRawOuts) return bad(at + "unknown out " + std::to_string(s.out));
+    if (s.interp >= kResizeInterps) return bad(at + "unknown interp " + std::to_string(s.interp));
+    if (s.out == TFRG_RAW_OUT_SAME && s.interp != TFRG_RESIZE_NEAREST)
+      return bad(at + "TFRG_RAW_OUT_SAME copies bits: it goes with TFRG_RESIZE_NEAREST only");
+    if (s.channels == 0 || s.channels > TFRG_RESIZE_MAX_CHANNELS)
+      return bad(at + "channels must be 1.." + std::to_string(TFRG_RESIZE_MAX_CHANNELS));
+    if (s.out_h == 0 || s.out_h > TFRG_RESIZE_MAX_OUT || s.out_w == 0 || s.out_w > TFRG_RESIZE_MAX_OUT)
+      return bad(at + "out_h and out_w must be 1.." + std::to_string(TFRG_RESIZE_MAX_OUT));
+    if (s.out_w * s.channels > TFRG_RESIZE_MAX_OUT)
+      return bad(at + "out_w * channels must be at most " + std::to_string(TFRG_RESIZE_MAX_OUT));
+    const struct {
+      const char* what;
+      uint32_t slot, konst;
+    } ext[2] = {{"h_slot", s.h_slot, s.src_h}, {"w_slot", s.w_slot, s.src_w}};
+    for (const auto& e : ext) {
+      if (e.slot == TFRG_RESIZE_CONST) {
+        if (e.konst == 0 || e.konst > TFRG_RESIZE_MAX_SRC)
+          return bad(at + "a constant extent must be 1.." + std::to_string(TFRG_RESIZE_MAX_SRC));
+      } else if (e.slot >= c->n_slots || (c->slot_kind_h[e.slot] & 3u) != TFRG_KIND_INT64) {
+        return bad(at + e.what + " " + std::to_string(e.slot) + " is not an int64_list slot");
+      }
+    }
+    if (s.planar > 1) return bad(at + "planar must be 0 or 1");
+    if (!s.out_ptr) return bad(at + "out_ptr is NULL");
+    if ((uintptr_t)s.out_ptr & (raw_out_size(s.src, s.out) - 1u)) return bad(at + "out_ptr must be aligned to the output element size");
+    if ((uintptr_t)s.shapes & 3u) return bad(at + "shapes must be 4-byte aligned");
+    if (s.reserved) return bad(at + "reserved must be 0");
+  }
+  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
+  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
+  if ((uintptr_t)d_boxes & 3u) return bad("d_boxes must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = confirm_pending(c)) return rc;
+  ResizeArgs a{};
+  a.rows = d_rows;
+  a.rows64 = d_rows && rows_dtype == TFRG_ROWS_I64;
+  a.m = m;
+  a.row0 = row0;
+  a.skipped = d_skipped;
+  a.boxes = d_boxes;
+  a.flips = d_flip;
+  fill_columns(c, a);
+  fill_bytes_source(c, a);
+  a.stats = d_stats;
+  a.n_specs = n_specs;
+  a.nt = (uint32_t)c->sw.dense_nt;
+  // workgroups per spec: one per band of a row, within an even share of 8 per CU (what the LDS of the
+  // common sizes lets a CU hold); they stride over what is left
+  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 8u / n_specs);
+  uint32_t blocks = 0, lds_words = 0;
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_resize_spec& s = specs[i];
+    ResizeSpec& d = a.sp[i];
+    const uint32_t osz = raw_out_size(s.src, s.out);
+    d.out = s.out_ptr;
+    d.shapes = s.shapes;
+    d.fill = osz == 4 ? s.fill : s.fill & ((1u << (8 * osz)) - 1u);
+    d.slot = s.slot;
+    d.src = s.src;
+    d.outt = s.out;
+    d.channels = s.channels;
+    d.planar = s.planar;
+    d.interp = s.interp;
+    d.out_h = s.out_h;
+    d.out_w = s.out_w;
+    d.h_slot = s.h_slot;
+    d.w_slot = s.w_slot;
+    d.src_h = s.src_h;
+    d.src_w = s.src_w;
+    d.const_len = const_len_of(c, s.slot, true);
+    d.const_off = const_off_of(c, s.slot, true);
+    d.bands = (s.out_h + kResizeBand - 1) / kResizeBand;
+    d.blk0 = blocks;
+    d.nblk = (uint32_t)std::min<uint64_t>(cap, (uint64_t)m * d.bands);
+    blocks += d.nblk;
+    lds_words = std::max(lds_words, resize_lds_words(s.out_w, s.channels));
+    memcpy(d.scale, s.scale, sizeof d.scale);
+    memcpy(d.bias, s.bias, sizeof d.bias);
+  }
+  hipStream_t st, cs;
+  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
+  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
+  // (a row list over an empty result: no record to read, every row is skipped)
+  if (d_skipped)
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_skipped), c->res.req.n ? 0 : (int)m, n_specs, st));
+  if (m && c->res.req.n) HIP_TRY(launch_resize(a, blocks, lds_words * 4u, st));
   return fence_close(c, st, cs);
 }
 

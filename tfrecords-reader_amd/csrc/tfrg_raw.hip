@@ -40,40 +40,23 @@
 #include <hip/hip_runtime.h>
 
 #include "tfrg_raw.h"
+#include "tfrg_raw_dev.h"
 #include "tfrg_internal.h"
 #include "tfrg_rows.h"
 
 namespace tfrg {
 namespace {
 
-typedef uint32_t rw_u32x4 __attribute__((ext_vector_type(4)));
-typedef float rw_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 rw_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 rw_f16x2 __attribute__((ext_vector_type(2)));
-
 typedef const __attribute__((address_space(4))) RawArgs* KArgs;
 typedef const __attribute__((address_space(4))) RawSpec* KSpec;
 
-// LDS of a workgroup in words: kData words of slack (the realigned write of unit 0 starts up to three
-// words early), a tile's 4096 words, one unit of overrun, and the padding of one word per 32. A wave of
-// the narrow shape has a quarter of it (its tile is at most 1024 words).
-constexpr uint32_t kData = 4;
+// LDS of a workgroup in words: kData words of slack (tfrg_raw_dev.h), a tile's 4096 words, one unit of
+// overrun, and the padding of one word per 32. A wave of the narrow shape has a quarter of it (its tile is
+// at most 1024 words).
 constexpr uint32_t kLdsWords = 4352;
 constexpr uint32_t kWaveWords = kLdsWords / 4;
 static_assert(kData + kRawTile + 4 + (kData + kRawTile + 4) / 32 < kLdsWords, "a workgroup's tile fits");
 static_assert(kData + kRawNarrow + 4 + (kData + kRawNarrow + 4) / 32 < kWaveWords, "a wave's tile fits");
-
-__device__ __forceinline__ uint32_t swz(uint32_t w) { return w + (w >> 5); }
-
-// element at byte b of the staged tile (b a multiple of ESZ), zero-extended
-template <uint32_t ESZ>
-__device__ __forceinline__ uint32_t ld_elem(const uint32_t* L, uint32_t b) {
-  b += kData * 4u;
-  const uint32_t a = b + ((b >> 7) << 2);  // (swz on a byte address)
-  if constexpr (ESZ == 1) return reinterpret_cast<const uint8_t*>(L)[a];
-  else if constexpr (ESZ == 2) return reinterpret_cast<const uint16_t*>(L)[a >> 1];
-  else return L[a >> 2];
-}
 
 // the spec a workgroup works in (uniform)
 struct Sp {
@@ -102,36 +85,6 @@ __device__ __forceinline__ void grp_sync(const Grp& g) {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
   }
-}
-
-// ------------------------------------------------------------------ the row of a work item
-struct RowSrc {
-  uint32_t off, len, cnt, ok;  // element 0's first byte and length, the record's element count
-};
-
-// (every value uniform over the group: held in scalar registers)
-__device__ __forceinline__ RowSrc resolve(const Sp& x, uint32_t k) {
-  const Rec q = rec_of(x.a, x.rl.row0, x.rl.rows ? row_entry(x.rl, k) : (int64_t)k);
-  const uint32_t g = rfl32(q.g), ok = rfl32(q.ok);
-  uint32_t lo = g, c = 1u;
-  if (x.rs) {
-    lo = rfl32(x.rs[g]);
-    c = rfl32(x.rs[g + 1u]) - lo;
-  }
-  c = ok ? c : 0u;
-  const uint64_t es = c ? x.base + lo : 0ull;
-  RowSrc r{0u, 0u, c, ok};
-  if (x.a->b_off64) {
-    const uint64_t o0 = rfl64(x.a->b_off64[es]), o1 = rfl64(x.a->b_off64[es + 1]);
-    const uint64_t l = o1 - o0;
-    r.off = o0 < 0xffffffffull ? (uint32_t)o0 : 0xffffffffu;
-    r.len = l < 0xffffffffull ? (uint32_t)l : 0xffffffffu;
-  } else {
-    r.off = x.s->const_off != kRawOffStored ? rfl32(x.a->end32[g]) + (uint32_t)x.s->const_off : rfl32(x.a->b_off[es]);
-    r.len = x.s->const_len != kRawNoLen ? x.s->const_len : rfl32(x.a->b_len[es]);
-  }
-  if (!c) r.len = 0u;
-  return r;
 }
 
 // ------------------------------------------------------------------ source side
@@ -168,25 +121,6 @@ __device__ __forceinline__ void stage(const Sp& x, const Grp& g, uint64_t s0, ui
 }
 
 // ------------------------------------------------------------------ convert
-template <uint32_t SRC>
-__device__ __forceinline__ float to_f32(uint32_t raw) {
-  if constexpr (SRC == kRawU8 || SRC == kRawU16) return (float)raw;
-  else if constexpr (SRC == kRawI8) return (float)(int8_t)raw;
-  else if constexpr (SRC == kRawI16) return (float)(int16_t)raw;
-  else if constexpr (SRC == kRawI32) return (float)(int32_t)raw;
-  else if constexpr (SRC == kRawF16) return (float)__builtin_bit_cast(_Float16, (uint16_t)raw);
-  else if constexpr (SRC == kRawBF16) return __builtin_bit_cast(float, raw << 16);
-  else return __builtin_bit_cast(float, raw);
-}
-
-// two float32 to a pair of float16 / bfloat16, RNE
-template <uint32_t OUT>
-__device__ __forceinline__ uint32_t cvt2(float a, float b) {
-  const rw_f32x2 v = {a, b};
-  if constexpr (OUT == kRawOutF16) return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, rw_f16x2));
-  else return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, rw_bf16x2));
-}
-
 // where a lane's elements come from and what they are (per lane)
 struct Run {
   uint32_t b0, bstr;  // LDS byte of its first element, bytes between consecutive ones
@@ -244,14 +178,6 @@ __device__ __forceinline__ void elems(const Sp& x, const uint32_t* L, const rw_f
       }
     }
   }
-}
-
-// a store to global memory at address p (global_store, not flat), with the streaming policy under NT
-template <bool NT, class T>
-__device__ __forceinline__ void st(uint64_t p, T v) {
-  typedef __attribute__((address_space(1))) T* G;
-  if constexpr (NT) __builtin_nontemporal_store(v, (G)p);
-  else *(G)p = v;
 }
 
 // ------------------------------------------------------------------ one tile

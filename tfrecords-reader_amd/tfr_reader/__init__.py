@@ -8,7 +8,7 @@ spreads the readers' files over several GPUs.
 from tfr_reader.example import Feature, set_decoder_type
 from tfr_reader.ids import ElementIds, Vocabulary
 from tfr_reader.ragged import Ragged, RaggedBatch
-from tfr_reader.raw import Raw
+from tfr_reader.raw import Raw, Resize
 from tfr_reader.reader import (
     TFRecordDatasetReader,
     TFRecordFileReader,
@@ -24,6 +24,7 @@ __all__ = [
     "Ragged",
     "RaggedBatch",
     "Raw",
+    "Resize",
     "TFRecordDatasetReader",
     "TFRecordFileReader",
     "Vocabulary",

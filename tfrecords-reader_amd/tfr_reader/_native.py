@@ -145,6 +145,39 @@ RAW_TILE = 4096  # (csrc/tfrg_raw.h: a tile's elements at the most, and the rows
 RAW_NARROW = 1024
 
 
+class TfrgResizeSpec(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("src", C.c_uint32),
+        ("out", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("h_slot", C.c_uint32),
+        ("w_slot", C.c_uint32),
+        ("src_h", C.c_uint32),
+        ("src_w", C.c_uint32),
+        ("out_h", C.c_uint32),
+        ("out_w", C.c_uint32),
+        ("interp", C.c_uint32),
+        ("planar", C.c_uint32),
+        ("fill", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("scale", C.c_float * 4),
+        ("bias", C.c_float * 4),
+        ("out_ptr", C.c_void_p),
+        ("shapes", C.c_void_p),
+    ]
+
+
+RESIZE_BILINEAR, RESIZE_NEAREST = range(2)  # tfrg_resize_spec.interp (TFRG_RESIZE_*)
+RESIZE_CONST = 0xFFFFFFFF  # h_slot / w_slot: the extent is src_h / src_w
+RESIZE_MAX_SPECS = 16
+RESIZE_MAX_CHANNELS = 4
+RESIZE_MAX_OUT = 4096
+RESIZE_MAX_SRC = 16384
+RESIZE_MAX_ROW_BYTES = 16384
+RESIZE_BAND = 16  # (csrc/tfrg_resize.h: the output rows of one work item)
+
+
 class TfrgRaggedSpec(C.Structure):
     _fields_ = [
         ("slot", C.c_uint32),
@@ -329,6 +362,9 @@ SIGNATURES: dict[str, tuple] = {
                                          C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_result_raw_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgRawSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                        C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tfrg_result_raw_resize": (C.c_int, [C.c_void_p, C.POINTER(TfrgResizeSpec), C.c_uint32, C.c_void_p, C.c_uint32,
+                                         C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "tfrg_result_ragged_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgRaggedSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_ctx_set_ragged_tile": (C.c_int, [C.c_void_p, C.c_uint32]),

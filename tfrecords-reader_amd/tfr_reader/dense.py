@@ -111,11 +111,13 @@ class DenseBatch(dict):
     path); ``lengths[name]`` for the specs that asked for them; ``stats[name]`` the four counters
     ``STAT_NAMES`` as a uint32 array (read back from the device on first access); ``skipped``: how
     many entries of a device row list were out of range, their output rows left unwritten (read back
-    on first access too)."""
+    on first access too); ``shapes[name]``: the ``[m, 2]`` (H, W) of the records behind the rows, for the
+    ``tfr_reader.raw.Resize`` specs that asked for them."""
 
-    def __init__(self, values: Mapping, lengths: Mapping, stats, skipped=0) -> None:
+    def __init__(self, values: Mapping, lengths: Mapping, stats, skipped=0, shapes: Mapping | None = None) -> None:
         super().__init__(values)
         self.lengths = dict(lengths)
+        self.shapes = dict(shapes or {})
         self._stats = stats  # a dict, or a function returning it
         self._skipped = skipped  # an int, or a function returning it
 

@@ -552,6 +552,16 @@ class HipDecoder:
 
         return W.decoder_raw(self, specs, rows=rows, out=out, stream=stream, strict=strict)
 
+    def resize(self, specs, rows=None, boxes=None, flip=None, out=None, stream: int | None = None, strict: bool = False):
+        """Raw images whose height and width are int64 features of their record, cropped (``boxes``: an
+        int32 ``[m, 4]`` device tensor of top, left, height, width per output row), mirrored (``flip``: a
+        uint8 / bool ``[m]`` device tensor), resampled to a fixed size and normalised -- ``[m, OH, OW, C]`` or
+        planar ``[m, C, OH, OW]`` -- one torch tensor per ``tfr_reader.raw.Resize`` spec, in one launch
+        (tfrg_result_raw_resize); see ``tfr_reader.raw.decoder_resize``."""
+        from tfr_reader import raw as W  # noqa: PLC0415
+
+        return W.decoder_resize(self, specs, rows=rows, boxes=boxes, flip=flip, out=out, stream=stream, strict=strict)
+
     def ragged_minibatches(self, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False, capacity=None,
                            where=None):
         """One epoch of shuffled ``batch_size``-row ``RaggedBatch``es over the last decode (``where``:
@@ -879,6 +889,14 @@ class BatchResult:
         from tfr_reader import raw as W  # noqa: PLC0415
 
         return W.batch_raw(self, specs, rows)
+
+    def resize(self, specs, rows=None, boxes=None, flip=None):
+        """The outputs of ``tfr_reader.raw.Resize`` specs as numpy arrays from the fetched columns (the host
+        counterpart of ``HipDecoder.resize``, in the same integer coordinates and float32 arithmetic): a
+        ``DenseBatch`` with ``.stats`` and ``.shapes``; bfloat16 outputs as their uint16 bits."""
+        from tfr_reader import raw as W  # noqa: PLC0415
+
+        return W.batch_resize(self, specs, rows, boxes, flip)
 
     def select(self, where, rows=None, row0: int = 0):
         """The candidates that pass ``where`` (``tfr_reader.select.Term``s), from the fetched columns

@@ -393,6 +393,15 @@ class ShardDecoder:
 
         return W.shard_raw(self, plan, specs, rows=rows, out=out, stream=stream, strict=strict)
 
+    def resize(self, plan: np.ndarray, specs, rows=None, boxes=None, flip=None, out=None, stream: int | None = None,
+               strict: bool = False):
+        """The last ``decode_device`` / ``decode_device32`` as resized-image outputs over the whole plan
+        (``tfr_reader.raw.Resize`` specs; ``boxes`` and ``flip`` per entry of the row list), as ``raw``; see
+        ``tfr_reader.raw.shard_resize``."""
+        from tfr_reader import raw as W  # noqa: PLC0415
+
+        return W.shard_resize(self, plan, specs, rows=rows, boxes=boxes, flip=flip, out=out, stream=stream, strict=strict)
+
     def minibatches(self, plan: np.ndarray, specs, batch_size: int, *, seed: int = 0, drop_last: bool = False,
                     where=None):
         """One epoch of shuffled ``batch_size``-row ``DenseBatch``es over the plan's last decode
