@@ -516,13 +516,27 @@ int tfrg_result_raw_rows(tfrg_ctx* ctx, const tfrg_raw_spec* specs, uint32_t n_s
  * v[i0], v[i0]) along x, r = fmaf(fy, h1 - h0, h0) along y, y = fmaf(r, scale[c], bias[c]), then one
  * round-to-nearest-even to float16 / bfloat16 where asked. Nearest takes v[i] for r; with
  * TFRG_RAW_OUT_SAME it copies the element's bits.
+ * Antialiasing: interp = TFRG_RESIZE_BILINEAR | TFRG_RESIZE_ANTIALIAS filters a downscale instead of
+ * skipping samples (F.interpolate(mode="bilinear", antialias=True, align_corners=False), torchvision's
+ * Resize on tensors, PIL's BILINEAR, tf.image.resize(antialias=True)). Every row of such a spec uses, on
+ * both axes, the triangle filter centred at (o + 0.5) n / N with half-width max(n / N, 1), renormalised at
+ * the edges, in integers: with M = max(n, N), t_j = |(2j + 1) N - (2o + 1) n| (below 2^28), w_j =
+ * max(0, 2M - t_j) for j in 0..n-1 and S = the sum of the w_j (at most 2^30, never 0), out = (sum of
+ * w_j * v_j) / S. Arithmetic: w_j converted to float32 (exactly); along x, then along y, a float32
+ * accumulation of fmaf(w, v, acc) over the window, in any order, times 1.0f / (float)S; then y =
+ * fmaf(r, scale[c], bias[c]) and the rounding as above. For n <= N this is mathematically the bilinear rule
+ * above, so an upscaled axis agrees with plain bilinear within rounding, but not bit for bit. Bad shapes,
+ * bad boxes, fill, shapes, counters, rows, boxes, flips and every limit are as without the flag; there is
+ * no limit on the taps of a window. Specs with and without the flag may share a call.
  * TFRG_E_ARG (text in tfrg_last_error): what tfrg_result_raw_rows refuses of the arguments both have, an
  * h_slot / w_slot that is neither TFRG_RESIZE_CONST nor an int64_list slot, a constant extent outside
  * 1..TFRG_RESIZE_MAX_SRC, out_h or out_w outside 1..TFRG_RESIZE_MAX_OUT, out_w * channels above
  * TFRG_RESIZE_MAX_OUT, channels outside 1..TFRG_RESIZE_MAX_CHANNELS, an unknown interp,
- * TFRG_RAW_OUT_SAME with bilinear, a shapes pointer that is not 4-byte aligned. */
+ * TFRG_RESIZE_ANTIALIAS with TFRG_RESIZE_NEAREST, TFRG_RAW_OUT_SAME with bilinear (antialiased or not), a
+ * shapes pointer that is not 4-byte aligned. */
 #define TFRG_RESIZE_BILINEAR 0
 #define TFRG_RESIZE_NEAREST 1
+#define TFRG_RESIZE_ANTIALIAS 0x100u /* OR-ed into interp, with TFRG_RESIZE_BILINEAR only */
 #define TFRG_RESIZE_CONST 0xffffffffu /* h_slot / w_slot: the extent is src_h / src_w */
 #define TFRG_RESIZE_MAX_SPECS 16
 #define TFRG_RESIZE_MAX_CHANNELS 4
@@ -540,7 +554,7 @@ typedef struct tfrg_resize_spec {
   uint32_t src_w;
   uint32_t out_h;     /* 1..TFRG_RESIZE_MAX_OUT */
   uint32_t out_w;     /* 1..TFRG_RESIZE_MAX_OUT, out_w * channels <= TFRG_RESIZE_MAX_OUT */
-  uint32_t interp;    /* TFRG_RESIZE_BILINEAR / TFRG_RESIZE_NEAREST */
+  uint32_t interp;    /* TFRG_RESIZE_BILINEAR (| TFRG_RESIZE_ANTIALIAS) / TFRG_RESIZE_NEAREST */
   uint32_t planar;    /* 0: out[k][oy][ox][c]; 1: out[k][c][oy][ox] */
   uint32_t fill;      /* raw low bits of a bad row's value, in the output type */
   uint32_t reserved;  /* 0 */

@@ -1612,9 +1612,9 @@ int tfrg_result_raw_rows(tfrg_ctx* c, const tfrg_raw_spec* specs, uint32_t n_spe
   return fence_close(c, st, cs);
 }
 
-// Resized raw images for a list of rows (tfrg_resize.h): one launch, all specs. The frame is
-// tfrg_result_raw_rows's; its own are the int64 slots of the shape, the geometry of the outputs, the
-// split into bands and the launch's LDS.
+// Resized raw images for a list of rows (tfrg_resize.h): one launch of k_resize for all plain specs and
+// one of k_resize_aa for all antialiased ones. The frame is tfrg_result_raw_rows's; its own are the int64
+// slots of the shape, the geometry of the outputs, the split into bands and each launch's LDS.
 int tfrg_result_raw_resize(tfrg_ctx* c, const tfrg_resize_spec* specs, uint32_t n_specs, const void* d_rows,
                            uint32_t rows_dtype, uint32_t m, int64_t row0, const int32_t* d_boxes,
                            const uint8_t* d_flip, uint32_t* d_stats, uint32_t* d_skipped, void* consumer_stream) {
@@ -1625,7 +1625,8 @@ int tfrg_result_raw_resize(tfrg_ctx* c, const tfrg_resize_spec* specs, uint32_t 
   static_assert(TFRG_RESIZE_MAX_SPECS == kResizeMaxSpecs && TFRG_RESIZE_MAX_CHANNELS == kResizeMaxChannels &&
                     TFRG_RESIZE_MAX_OUT == kResizeMaxOut && TFRG_RESIZE_MAX_SRC == kResizeMaxSrc &&
                     TFRG_RESIZE_MAX_ROW_BYTES == kResizeMaxRowBytes && TFRG_RESIZE_CONST == kResizeConst &&
-                    TFRG_RESIZE_BILINEAR == kResizeBilinear && TFRG_RESIZE_NEAREST == kResizeNearest,
+                    TFRG_RESIZE_BILINEAR == kResizeBilinear && TFRG_RESIZE_NEAREST == kResizeNearest &&
+                    TFRG_RESIZE_ANTIALIAS == kResizeAntialias,
                 "tfrg.h mirrors tfrg_resize.h");
   static_assert(sizeof(tfrg_resize_spec) == 104, "tfrg.h states the size");
   if (const int rc = check_specs(c, specs, n_specs, TFRG_RESIZE_MAX_SPECS, bad)) return rc;
@@ -1635,7 +1636,10 @@ int tfrg_result_raw_resize(tfrg_ctx* c, const tfrg_resize_spec* specs, uint32_t 
     if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
     if (s.src >= kRawSrcs) return bad(at + "unknown src " + std::to_string(s.src));
     if (s.out >= kRawOuts) return bad(at + "unknown out " + std::to_string(s.out));
-    if (s.interp >= kResizeInterps) return bad(at + "unknown interp " + std::to_string(s.interp));
+    if (s.interp == (TFRG_RESIZE_NEAREST | TFRG_RESIZE_ANTIALIAS))
+      return bad(at + "TFRG_RESIZE_ANTIALIAS filters: it goes with TFRG_RESIZE_BILINEAR only");
+    if (s.interp >= kResizeInterps && s.interp != (TFRG_RESIZE_BILINEAR | TFRG_RESIZE_ANTIALIAS))
+      return bad(at + "unknown interp " + std::to_string(s.interp));
     if (s.out == TFRG_RAW_OUT_SAME && s.interp != TFRG_RESIZE_NEAREST)
       return bad(at + "TFRG_RAW_OUT_SAME copies bits: it goes with TFRG_RESIZE_NEAREST only");
     if (s.channels == 0 || s.channels > TFRG_RESIZE_MAX_CHANNELS)
@@ -1680,10 +1684,6 @@ int tfrg_result_raw_resize(tfrg_ctx* c, const tfrg_resize_spec* specs, uint32_t 
   a.stats = d_stats;
   a.n_specs = n_specs;
   a.nt = (uint32_t)c->sw.dense_nt;
-  // workgroups per spec: one per band of a row, within an even share of 8 per CU (what the LDS of the
-  // common sizes lets a CU hold); they stride over what is left
-  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 8u / n_specs);
-  uint32_t blocks = 0, lds_words = 0;
   for (uint32_t i = 0; i < n_specs; ++i) {
     const tfrg_resize_spec& s = specs[i];
     ResizeSpec& d = a.sp[i];
@@ -1705,11 +1705,6 @@ int tfrg_result_raw_resize(tfrg_ctx* c, const tfrg_resize_spec* specs, uint32_t 
     d.src_w = s.src_w;
     d.const_len = const_len_of(c, s.slot, true);
     d.const_off = const_off_of(c, s.slot, true);
-    d.bands = (s.out_h + kResizeBand - 1) / kResizeBand;
-    d.blk0 = blocks;
-    d.nblk = (uint32_t)std::min<uint64_t>(cap, (uint64_t)m * d.bands);
-    blocks += d.nblk;
-    lds_words = std::max(lds_words, resize_lds_words(s.out_w, s.channels));
     memcpy(d.scale, s.scale, sizeof d.scale);
     memcpy(d.bias, s.bias, sizeof d.bias);
   }
@@ -1719,7 +1714,25 @@ int tfrg_result_raw_resize(tfrg_ctx* c, const tfrg_resize_spec* specs, uint32_t 
   // (a row list over an empty result: no record to read, every row is skipped)
   if (d_skipped)
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_skipped), c->res.req.n ? 0 : (int)m, n_specs, st));
-  if (m && c->res.req.n) HIP_TRY(launch_resize(a, blocks, lds_words * 4u, st));
+  // Per kernel, the blk0 table of its launch: workgroups per spec of its kind, one per band of a row, within
+  // an even share of 8 per CU (what the LDS of the common sizes lets a CU hold, and more); they stride over
+  // what is left. A spec of the other kind has no workgroup, so no block index selects it; the spec index,
+  // and with it the counters, are the call's in both launches.
+  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 8u / n_specs);
+  for (const bool aa : {false, true}) {
+    uint32_t blocks = 0, lds_words = 0;
+    for (uint32_t i = 0; i < n_specs; ++i) {
+      ResizeSpec& d = a.sp[i];
+      const bool mine = ((d.interp & kResizeAntialias) != 0) == aa;
+      const uint32_t band = aa ? resize_aa_band(d.out_w * d.channels) : kResizeBand;
+      d.bands = (d.out_h + band - 1) / band;
+      d.blk0 = blocks;
+      d.nblk = mine ? (uint32_t)std::min<uint64_t>(cap, (uint64_t)m * d.bands) : 0u;
+      blocks += d.nblk;
+      if (mine) lds_words = std::max(lds_words, (aa ? resize_aa_lds_words : resize_lds_words)(d.out_w, d.channels));
+    }
+    if (m && c->res.req.n) HIP_TRY((aa ? launch_resize_aa : launch_resize)(a, blocks, lds_words * 4u, st));
+  }
   return fence_close(c, st, cs);
 }
 

@@ -1,4 +1,5 @@
-// tfrg_resize.h — arguments of k_resize (tfrg_resize.hip), the kernel behind tfrg_result_raw_resize:
+// tfrg_resize.h — arguments of k_resize (tfrg_resize.hip) and k_resize_aa (tfrg_resize_aa.hip, the
+// antialiased specs), the kernels behind tfrg_result_raw_resize:
 // element 0 of a bytes_list slot read as an H x W x channels image whose H and W are int64 features of the
 // same record, a per-row crop window resampled (bilinear or nearest, optionally mirrored) to a fixed
 // out_h x out_w, normalised per channel and written interleaved or planar, for a list of rows.
@@ -18,6 +19,7 @@ constexpr uint32_t kResizeMaxSrc = 16384;       // (tfrg.h TFRG_RESIZE_MAX_SRC):
 constexpr uint32_t kResizeMaxRowBytes = 16384;  // (tfrg.h TFRG_RESIZE_MAX_ROW_BYTES): a crop row
 constexpr uint32_t kResizeConst = 0xffffffffu;  // (tfrg.h TFRG_RESIZE_CONST)
 enum ResizeInterp : uint32_t { kResizeBilinear = 0, kResizeNearest, kResizeInterps };
+constexpr uint32_t kResizeAntialias = 0x100u;   // (tfrg.h TFRG_RESIZE_ANTIALIAS): OR-ed into interp; k_resize_aa
 
 // A work item is a band of kResizeBand consecutive output rows of one list entry.
 constexpr uint32_t kResizeBand = 16;
@@ -28,6 +30,27 @@ constexpr uint32_t kResizeBand = 16;
 constexpr uint32_t kResizeStageWords = 4352;
 __host__ __device__ constexpr uint32_t resize_lds_words(uint32_t out_w, uint32_t channels) {
   return kResizeStageWords + 2u * out_w * channels + 2u * out_w;
+}
+
+// k_resize_aa (tfrg_resize_aa.hip). A work item is a band of resize_aa_band() output rows; its source rows
+// are staged and resampled horizontally in groups of up to resize_aa_group() rows (fewer where fewer crop
+// rows fit the stage). Both follow from the output row's length rn = out_w * channels alone, so the
+// launcher and the kernel agree without a field: about 24 KiB for the band's accumulators and 12 KiB for
+// the group's horizontal results, at most 8 and 4 rows (224 x 3: 8 and 4), at least 2 and 1 (rn = 4096).
+constexpr uint32_t kResizeAaMaxBand = 8, kResizeAaMaxGroup = 4;
+__host__ __device__ constexpr uint32_t resize_aa_band(uint32_t rn) {
+  const uint32_t b = 6144u / rn;
+  return b > kResizeAaMaxBand ? kResizeAaMaxBand : b < 2u ? 2u : b;
+}
+__host__ __device__ constexpr uint32_t resize_aa_group(uint32_t rn) {
+  const uint32_t g = 3072u / rn;
+  return g > kResizeAaMaxGroup ? kResizeAaMaxGroup : g < 1u ? 1u : g;
+}
+// LDS of a workgroup, in words: the stage, the group's horizontal results, the band's accumulators, the
+// column table (three words per output column) and the band's row table (four words per output row).
+__host__ __device__ constexpr uint32_t resize_aa_lds_words(uint32_t out_w, uint32_t channels) {
+  const uint32_t rn = out_w * channels;
+  return kResizeStageWords + (resize_aa_group(rn) + resize_aa_band(rn)) * rn + 3u * out_w + 4u * kResizeAaMaxBand;
 }
 
 // One requested output. Workgroups [blk0, blk0 + nblk) of the launch work inside it and stride over its
@@ -84,5 +107,7 @@ static_assert(sizeof(ResizeArgs) <= 4096, "k_resize's spec table travels as the 
 
 // lds_bytes: resize_lds_words of the launch's largest spec, in bytes
 hipError_t launch_resize(const ResizeArgs& a, uint32_t blocks, uint32_t lds_bytes, hipStream_t st);
+// the same for k_resize_aa over the antialiased specs of a call (lds_bytes: resize_aa_lds_words)
+hipError_t launch_resize_aa(const ResizeArgs& a, uint32_t blocks, uint32_t lds_bytes, hipStream_t st);
 
 }  // namespace tfrg

@@ -169,6 +169,7 @@ class TfrgResizeSpec(C.Structure):
 
 
 RESIZE_BILINEAR, RESIZE_NEAREST = range(2)  # tfrg_resize_spec.interp (TFRG_RESIZE_*)
+RESIZE_ANTIALIAS = 0x100  # OR-ed into interp, with RESIZE_BILINEAR only (TFRG_RESIZE_ANTIALIAS)
 RESIZE_CONST = 0xFFFFFFFF  # h_slot / w_slot: the extent is src_h / src_w
 RESIZE_MAX_SPECS = 16
 RESIZE_MAX_CHANNELS = 4
@@ -176,6 +177,9 @@ RESIZE_MAX_OUT = 4096
 RESIZE_MAX_SRC = 16384
 RESIZE_MAX_ROW_BYTES = 16384
 RESIZE_BAND = 16  # (csrc/tfrg_resize.h: the output rows of one work item)
+# (csrc/tfrg_resize.h, k_resize_aa: the output rows of one work item and the crop rows of one group, for
+# outputs of up to 768 elements per row and crop rows of which four fit the stage; fewer beyond)
+RESIZE_AA_BAND, RESIZE_AA_GROUP = 8, 4
 
 
 class TfrgRaggedSpec(C.Structure):

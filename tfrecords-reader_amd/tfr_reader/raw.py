@@ -262,7 +262,10 @@ class Resize:
     "nearest"), then ``x * scale[c] + bias[c]`` and one rounding to ``out``, as ``Raw``. The result is
     ``[m, OH, OW, channels]``, or ``[m, channels, OH, OW]`` with ``planar``. A record whose shape or box
     is unusable gives a row of ``fill``. ``shapes``: also return ``[m, 2]`` int32, each record's (H, W).
-    ``out="same"`` (the source bits) goes with "nearest" only."""
+    ``out="same"`` (the source bits) goes with "nearest" only. ``antialias`` (with "bilinear" only): the
+    triangle filter of include/tfrg.h on both axes, which filters a downscale instead of skipping samples
+    (``F.interpolate(antialias=True)``, torchvision's ``Resize``, PIL's ``BILINEAR``); an upscaled axis then
+    agrees with plain bilinear within rounding, not bit for bit."""
 
     key: str
     size: tuple = (1, 1)
@@ -278,6 +281,7 @@ class Resize:
     fill: float | int = 0
     shapes: bool = False
     name: str | None = None
+    antialias: bool = False
 
     dtype = "uint8"  # (the slot kind, as ``Dense.dtype`` selects it)
 
@@ -293,6 +297,9 @@ class Resize:
             raise ValueError(f"{who}: interp must be one of {sorted(INTERP)}, not {self.interp!r}")
         if self.out == "same" and self.interp != "nearest":
             raise ValueError(f"{who}: out='same' copies bits and goes with interp='nearest' only")
+        if self.antialias and self.interp != "bilinear":
+            raise ValueError(f"{who}: antialias filters and goes with interp='bilinear' only")
+        object.__setattr__(self, "antialias", bool(self.antialias))
         c = self.channels
         if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= int(c) <= N.RESIZE_MAX_CHANNELS:
             raise ValueError(f"{who}: channels must be in 1..{N.RESIZE_MAX_CHANNELS}, not {c!r}")
@@ -366,6 +373,36 @@ def _fma32(a: np.ndarray, b: np.ndarray, c: np.ndarray) -> np.ndarray:
     return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
 
 
+def axis_windows(n: int, size: int, flip: bool = False) -> tuple:
+    """(j0, cnt, d0, inv) of the ``size`` antialiased output positions along a source axis of ``n`` samples,
+    in the integers of include/tfrg.h: the window's first tap and tap count, d = (2 j0 + 1) N - (2 o + 1) n
+    of the first tap (the next tap's is 2N more; a tap's weight is 2M - |d|) and float32 1 / (float32)S."""
+    o = np.arange(size, dtype=np.int64)
+    if flip:
+        o = size - 1 - o
+    big, c = max(n, size), (2 * o + 1) * n
+    j0 = np.maximum((c - 2 * big - size) // (2 * size) + 1, 0)
+    j1 = np.minimum((c + 2 * big - size - 1) // (2 * size), n - 1)
+    d0 = (2 * j0 + 1) * size - c
+    tot = [int((2 * big - np.abs(d + 2 * size * np.arange(k))).sum()) for d, k in zip(d0, j1 - j0 + 1)]
+    return j0, j1 - j0 + 1, d0, np.float32(1) / np.array(tot, np.int64).astype(np.float32)
+
+
+def _filter_axis(v: np.ndarray, n: int, size: int, flip: bool) -> np.ndarray:
+    """float32 ``v`` ``[n, ...]`` filtered along axis 0 to ``[size, ...]``: per output a sequential float32
+    accumulation of fmaf(w, v, acc) over the window, times 1 / S."""
+    j0, cnt, d0, inv = axis_windows(n, size, flip)
+    out = np.zeros((size, *v.shape[1:]), np.float32)
+    big = 2 * max(n, size)
+    for o in range(size):
+        acc = np.zeros(v.shape[1:], np.float32)
+        for j in range(int(cnt[o])):
+            w = np.float32(big - abs(int(d0[o]) + 2 * size * j))
+            acc = _fma32(np.broadcast_to(w, acc.shape), v[int(j0[o]) + j], acc)
+        out[o] = acc * inv[o]
+    return out
+
+
 def resample(sp: Resize, img: np.ndarray, box: tuple, flip: bool) -> np.ndarray:
     """The output bits ``[OH, OW, channels]`` of the crop ``box`` = (top, left, height, width) of ``img``
     (``[H, W, channels]`` of the source type; bfloat16 as uint16 bits), in the kernel's arithmetic."""
@@ -378,7 +415,10 @@ def resample(sp: Resize, img: np.ndarray, box: tuple, flip: bool) -> np.ndarray:
         return crop[y0][:, x0].view(ubits)
     v = (crop.astype(np.uint32) << 16).view(np.float32) if sp.src == "bfloat16" else crop.astype(np.float32)
     with np.errstate(all="ignore"):
-        if sp.interp == "nearest":
+        if sp.antialias:
+            h = _filter_axis(np.ascontiguousarray(v.transpose(1, 0, 2)), cw, ow, flip)  # ([OW, ch, C])
+            r = _filter_axis(np.ascontiguousarray(h.transpose(1, 0, 2)), ch, oh, False)
+        elif sp.interp == "nearest":
             r = v[y0][:, x0]
         else:
             a, b = v[:, x0], v[:, x1]
@@ -486,6 +526,7 @@ def launch_resize(dec, items: Sequence[tuple], rows: tuple | None, m: int, row0:
     arr = (N.TfrgResizeSpec * len(items))()
     for a, (sp, (slot, hs, ws), out, shapes) in zip(arr, items):
         a.slot, a.src, a.out, a.channels, a.interp = slot, SRC[sp.src][0], OUT[sp.out], sp.channels, INTERP[sp.interp]
+        a.interp |= N.RESIZE_ANTIALIAS if sp.antialias else 0
         a.h_slot, a.src_h = (N.RESIZE_CONST, sp.height) if hs is None else (hs, 0)
         a.w_slot, a.src_w = (N.RESIZE_CONST, sp.width) if ws is None else (ws, 0)
         (a.out_h, a.out_w), a.planar, a.fill, a.reserved = sp.size, int(bool(sp.planar)), sp.fill_bits, 0

@@ -9,6 +9,8 @@ bfloat16 planar. Alternating in one process, timed by device events over windows
   torch:   per record, a view of the packed image bytes (what ragged() hands back) -> crop -> float ->
            F.interpolate(bilinear) -> flip -> normalise -> bfloat16 into the same output.
 Algorithmic bytes: the source crop rows that some output row taps, once each, plus the output.
+`--antialias`: the same records, boxes and flips with `antialias=True` on both sides (k_resize_aa;
+F.interpolate(..., antialias=True)); every crop row of a box is tapped, so the bytes are all of them once.
 Prints one JSON line."""
 
 import argparse
@@ -34,6 +36,7 @@ def main() -> None:
     ap.add_argument("--iters", type=int, default=1000, help="resize calls per timed window")
     ap.add_argument("--torch-iters", type=int, default=30, help="passes of the torch composition per timed window")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--antialias", action="store_true", help="the triangle filter on both sides")
     ap.add_argument("--hbm-gbs", type=float, default=8000.0, help="the HBM rate the fraction is taken of")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
@@ -52,7 +55,7 @@ def main() -> None:
         boxes[k] = [rng.integers(0, h - ch + 1), rng.integers(0, w - cw + 1), ch, cw]
     flips = rng.integers(0, 2, m).astype(np.uint8)
     mean, std = np.array([0.485, 0.456, 0.406]) * 255, np.array([0.229, 0.224, 0.225]) * 255
-    sp = W.Resize.normalize("image", mean, std, size=(224, 224), channels=3, out="bfloat16", planar=True)
+    sp = W.Resize.normalize("image", mean, std, size=(224, 224), channels=3, out="bfloat16", planar=True, antialias=a.antialias)
     d_rows, d_boxes, d_flips = (torch.from_numpy(x).to(dev) for x in (rows.astype(np.int64), boxes, flips))
     out = torch.empty((m, 3, 224, 224), dtype=torch.bfloat16, device=dev)
 
@@ -68,7 +71,7 @@ def main() -> None:
             h, w = shapes[g]
             t, l, ch, cw = boxes[k].tolist()
             x = packed[offs[g] : offs[g + 1]].view(h, w, 3)[t : t + ch, l : l + cw].permute(2, 0, 1)[None].float()
-            y = F.interpolate(x, size=(224, 224), mode="bilinear", align_corners=False)
+            y = F.interpolate(x, size=(224, 224), mode="bilinear", align_corners=False, antialias=a.antialias)
             out[k] = ((y.flip(-1) if flips[k] else y) * sc + bi)[0].to(torch.bfloat16)
 
     def timed(fn, iters):
@@ -90,10 +93,10 @@ def main() -> None:
     for k in range(m):
         _, _, ch, cw = boxes[k].tolist()
         y0, y1, _ = W.axis_coords(ch, 224, "bilinear")
-        tapped += len(set(y0.tolist()) | set(y1.tolist())) * cw * 3
+        tapped += (ch if a.antialias else len(set(y0.tolist()) | set(y1.tolist()))) * cw * 3
     nbytes = tapped + out.numel() * 2
     best = min(t_ours)
-    print(json.dumps({"m": m, "resize_ms": sorted(round(t, 4) for t in t_ours), "torch_ms": sorted(round(t, 3) for t in t_theirs),
+    print(json.dumps({"m": m, "antialias": a.antialias, "resize_ms": sorted(round(t, 4) for t in t_ours), "torch_ms": sorted(round(t, 3) for t in t_theirs),
                       "algorithmic_bytes": int(nbytes), "resize_gbs_best": round(nbytes / best / 1e6, 1),
                       "hbm_fraction_best": round(nbytes / best / 1e6 / a.hbm_gbs, 4), "device": torch.cuda.get_device_name(0)}))
     dec.close()
