@@ -759,6 +759,78 @@ int tfrg_result_elem_ids(tfrg_ctx* ctx, const tfrg_ids_spec* specs, uint32_t n_s
                          const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
                          uint64_t* d_totals, uint32_t* d_stats, void* consumer_stream);
 
+/* Token ids: a TEXT feature (a title, a query, a caption: one sentence per element) as one int64 per
+ * WORD, split on the device -- tf.strings.split + StringLookup / Hashing, or Keras
+ * TextVectorization(split="whitespace", standardize="lower") -- with the rows ragged in the form
+ * tfrg_result_elem_ids gives. Rows (d_rows, rows_dtype, m, row0, a NULL d_rows as the identity list,
+ * the rule for entries outside [0, n)) are word for word tfrg_result_ragged_elems's; a skipped row is an
+ * empty row. Per spec and output row k < m:
+ *   the taken elements are those tfrg_result_ragged_elems describes for the row with the same max_elems,
+ *     and an element's bytes are the bytes that call gives (the views into d_bytes, the materialized
+ *     column, or the end-relative view of an implicit_off_slots slot; zero past the readable input).
+ *     Columns an optimistic decode left implicit are neither read nor written;
+ *   a token is a maximal run of bytes that are no delimiter inside ONE element: an element boundary
+ *     always ends a token, and there are no empty tokens. The delimiters are the ASCII bytes b < 128
+ *     with bit b of delims set (delims[0] bit b for b < 64, delims[1] bit b - 64 above); both words 0
+ *     select the six bytes Python's bytes.split() splits on (09 0a 0b 0c 0d 20). A byte >= 128 is never
+ *     a delimiter, so a UTF-8 sequence is never cut inside a code point. The tokens of a row are the
+ *     tokens of its taken elements, in element order and then byte order;
+ *   with TFRG_TOK_LOWER_ASCII the bytes 'A'..'Z' of a token become 'a'..'z' before it is hashed or
+ *     compared, and no other byte changes (Python's bytes.lower()); the vocabulary's words are compared
+ *     as given;
+ *   a token's id is tfrg_result_elem_ids's rule applied to the (lowered) token bytes s: the id of the
+ *     vocabulary's word equal to s; else, with num_oov_buckets != 0, oov_base +
+ *     (int64_t)(tfrg_hash64(s) % num_oov_buckets); else default_id;
+ *   cnt(k) = the row's tokens, or min(that, max_tokens) with max_tokens != 0: the row's FIRST tokens;
+ *     row_offsets[0] = 0, row_offsets[k + 1] = row_offsets[k] + cnt(k): all m + 1 are always written.
+ *     T = row_offsets[m]. Only ids[t] for t < tok_cap are stored and nothing else in ids is written.
+ * d_totals (device, [n_specs] u64, or NULL): T. d_stats (device, [n_specs][4] u32, or NULL; zeroed by
+ * the call on the stream), counted over all T taken tokens and not only the stored ones: rows with more
+ * than max_tokens != 0 tokens; taken tokens that matched no word (every token, with vocab NULL); rows
+ * that are not skipped and have no token; skipped rows. A record drawn twice counts twice.
+ * m == 0: row_offsets[0] = 0, totals 0, no kernel. n == 0: every row is skipped. Two equal calls write
+ * equal bytes.
+ * Three launches on the decode's stream (token counts per tile of rows, kept in row_offsets; the scan of
+ * the tile sums; then row offsets and ids); no device value is read back. Stream order with
+ * consumer_stream, the single confirmation of an optimistic or hinted decode, any number of calls per
+ * decode, the rows per tile (tfrg_ctx_set_ragged_tile) and scratch from the context's arena are as for
+ * tfrg_result_elem_ids.
+ * Cost: the bytes are read twice, once to count and once to emit. A row of at most
+ * tfrg_ctx_set_token_split bytes is swept by ONE lane, 8 bytes a step; a longer row by ONE wave, 512
+ * bytes a round, so one very long row holds its wave for its length. A token is hashed, probed and
+ * compared by ONE lane, 8 bytes a step. A row of very many tiny elements walks them one per round.
+ * A row that has reached max_tokens is not read further. Without d_stats, rows whose first token lies
+ * at or past tok_cap (all of them with ids NULL) are not read a second time: a first call with ids NULL
+ * and d_stats NULL that sizes ids costs one sweep.
+ * TFRG_E_ARG (text in tfrg_last_error prefixed "tfrg_result_token_ids: ", nothing launched or
+ * written): everything tfrg_result_elem_ids refuses about the context, the rows, m, the slot,
+ * row_offsets and the vocabulary; n_specs outside 1..TFRG_TOK_MAX_SPECS; a misaligned ids; unknown
+ * flag bits; vocab NULL with num_oov_buckets == 0.
+ * TFRG_TOK_MAX_SPECS is 16 because the spec table travels as the kernel argument (4096 bytes). */
+#define TFRG_TOK_MAX_SPECS 16
+#define TFRG_TOK_LOWER_ASCII 1u
+typedef struct tfrg_tok_spec {
+  uint32_t slot;            /* a bytes_list slot, as in tfrg_set_schema */
+  uint32_t max_elems;       /* 0: every element of a row; else its first max_elems */
+  uint32_t max_tokens;      /* 0: every token of a row; else its first max_tokens */
+  uint32_t flags;           /* TFRG_TOK_LOWER_ASCII or 0; other bits refused */
+  uint64_t delims[2];       /* bit b of the 128: ASCII byte b separates tokens; both words 0: the six
+                               bytes bytes.split() splits on (09 0a 0b 0c 0d 20) */
+  const tfrg_vocab* vocab;  /* NULL: hash buckets only */
+  uint64_t num_oov_buckets; /* 0: an unmatched token gets default_id */
+  int64_t oov_base;
+  int64_t default_id;
+  uint64_t tok_cap;         /* ids that `ids` can hold */
+  int64_t* ids;             /* device [tok_cap], caller-owned; NULL: offsets and counters only */
+  int64_t* row_offsets;     /* device [m + 1], caller-owned, not NULL */
+} tfrg_tok_spec;            /* 88 bytes */
+int tfrg_result_token_ids(tfrg_ctx* ctx, const tfrg_tok_spec* specs, uint32_t n_specs,
+                          const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
+                          uint64_t* d_totals, uint32_t* d_stats, void* consumer_stream);
+/* bytes of a row up to which tfrg_result_token_ids sweeps it by one lane (longer rows: by one wave):
+ * 8..65536, 0 = the default (256). A tuning/testing knob: the result never depends on it. */
+int tfrg_ctx_set_token_split(tfrg_ctx* ctx, uint32_t bytes);
+
 /* Filtered row lists: the WHERE clause over the last result, on the device. Predicates over the
  * decoded columns in, the compacted list of the passing rows in device memory out -- usable as it is
  * as d_rows of tfrg_result_dense_rows / tfrg_result_ragged_rows of the same context(s), with the same

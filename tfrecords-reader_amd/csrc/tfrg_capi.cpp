@@ -19,6 +19,7 @@
 #include "tfrg_resize.h"
 #include "tfrg_elems.h"
 #include "tfrg_ids.h"
+#include "tfrg_tokens.h"
 #include "tfrg_ragged.h"
 #include "tfrg_select.h"
 #include "tfrg_frame.h"
@@ -140,6 +141,7 @@ struct Arena {
   DBuf rg_tsum;  // tfrg_result_ragged_rows: the per-tile sums
   DBuf el_tsum;  // tfrg_result_ragged_elems: the per-tile element counts and byte sums
   DBuf id_tsum;  // tfrg_result_elem_ids: the per-tile element counts
+  DBuf tk_tsum;  // tfrg_result_token_ids: the per-tile token counts
   DBuf sel_buf;  // tfrg_result_select_rows: the candidates' ballot words, then the per-tile sums
   template <class F>
   void each(F f) {
@@ -148,7 +150,7 @@ struct Arena {
                          &totals, &kind_totals, &ident, &i64, &f32, &b_off, &b_len, &big_list, &slow_list, &miss, &info,
                          &tsum, &crc_rec, &crc_base, &crc_part, &dq, &dq_cnt, &lmask, &rlist, &bdata, &boff64, &blb,
                          &bbig, &tpl, &spec, &fr_tab, &fr_dev, &rg_tsum, &el_tsum,
-                         &id_tsum, &sel_buf};
+                         &id_tsum, &tk_tsum, &sel_buf};
     static_assert(sizeof(all) / sizeof(*all) * sizeof(DBuf) == sizeof(Arena), "a buffer is missing from the list");
     for (DBuf* b : all) f(*b);
   }
@@ -226,6 +228,7 @@ struct tfrg_ctx : Arena {
   uint32_t index_chunk = kIndexChunkDefault;  // tfrg_ctx_set_index_chunk
   uint32_t ragged_tile = kRaggedTileDefault;  // tfrg_ctx_set_ragged_tile: rows per tile
   uint32_t select_tile = kSelTileDefault;     // tfrg_ctx_set_select_tile: candidates per tile
+  uint32_t token_split = kTokSplitDefault;   // tfrg_ctx_set_token_split: rows above it go by wave
   uint32_t select_scan = kSelScanDefault;     // tfrg_ctx_set_select_scan: CONTAINS elements above it go by wave
   void* fr_pin = nullptr;  // tfrg_index_device: pinned host staging
   size_t fr_pin_cap = 0;
@@ -389,6 +392,16 @@ int tfrg_ctx_set_ragged_tile(tfrg_ctx* c, uint32_t rows) {
     return TFRG_E_ARG;
   }
   c->ragged_tile = rows ? rows : kRaggedTileDefault;
+  return 0;
+}
+
+int tfrg_ctx_set_token_split(tfrg_ctx* c, uint32_t bytes) {
+  if (!c) return TFRG_E_ARG;
+  if (bytes && (bytes < kTokSplitMin || bytes > kTokSplitMax)) {
+    set_error("token split must be from 8 to 65536 bytes (0: the default)");
+    return TFRG_E_ARG;
+  }
+  c->token_split = bytes ? bytes : kTokSplitDefault;
   return 0;
 }
 
@@ -1925,6 +1938,70 @@ int tfrg_result_elem_ids(tfrg_ctx* c, const tfrg_ids_spec* specs, uint32_t n_spe
         return 0;
       },
       [m](const tfrg_ids_spec& s, hipStream_t st) -> int {
+        HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
+        return 0;
+      });
+}
+
+// One id per token of the elements of a bytes_list slot for a list of rows (tfrg_tokens.h: token counts,
+// tile scan, row offsets and ids). Every grid size comes from m, n_specs and the tile: nothing is read back.
+int tfrg_result_token_ids(tfrg_ctx* c, const tfrg_tok_spec* specs, uint32_t n_specs, const void* d_rows,
+                          uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
+                          void* consumer_stream) {
+  static_assert(TFRG_TOK_MAX_SPECS == kTokMaxSpecs && TFRG_TOK_LOWER_ASCII == kTokLowerAscii, "tfrg.h mirrors tfrg_tokens.h");
+  static_assert(sizeof(tfrg_tok_spec) == 88, "tfrg.h states the size");
+  static_assert(sizeof(TokArgs) < 4096, "the kernel argument");
+  static_assert(kTokNoLen == kElemsNoLen && kTokOffStored == kElemsOffStored, "const_len_of / const_off_of serve tfrg_tokens.h");
+  const RowListKind kind{"tfrg_result_token_ids", TFRG_TOK_MAX_SPECS, &Arena::tk_tsum, 1, 0, 0};  // (no split)
+  return result_row_list<TokArgs>(
+      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
+      [c](const tfrg_tok_spec& s, const std::string& at, const auto& bad, bool&) -> int {
+        if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
+        if (!s.row_offsets) return bad(at + "row_offsets is NULL");
+        if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.ids & 7u)) return bad(at + "row_offsets and ids must be 8-byte aligned");
+        if (s.flags & ~TFRG_TOK_LOWER_ASCII) return bad(at + "unknown flag bits " + std::to_string(s.flags));
+        if (!s.vocab && !s.num_oov_buckets) return bad(at + "no vocabulary and no hash buckets");
+        if (s.vocab && !s.vocab->d_mem) return bad(at + "the vocabulary was built host-only (device -1)");
+        if (s.vocab && s.vocab->device != c->device)
+          return bad(at + "the vocabulary is on device " + std::to_string(s.vocab->device) + ", the context on " +
+                     std::to_string(c->device));
+        return 0;
+      },
+      [c, specs](TokArgs& a, uint32_t, hipStream_t st) -> int {
+        a.split = c->token_split;
+        for (uint32_t i = 0; i < a.n_specs; ++i) {
+          const tfrg_tok_spec& s = specs[i];
+          TokSpec& d = a.sp[i];
+          d.ids = s.ids;
+          d.row_offsets = s.row_offsets;
+          d.tok_cap = s.tok_cap;
+          if (const tfrg_vocab* v = s.vocab) {
+            d.table = v->d_table;
+            d.w_offs = v->d_offs;
+            d.blob = v->d_blob;
+            d.w_ids = v->d_ids;
+            d.mask = (uint32_t)v->table.size() - 1u;
+            d.max_probe = v->max_probe;
+            d.max_word = v->max_word;
+            d.blob_bound = v->d_blob_bound;
+          }
+          d.n_buckets = s.num_oov_buckets;
+          d.oov_base = s.oov_base;
+          d.default_id = s.default_id;
+          const bool dflt = !s.delims[0] && !s.delims[1];  // (bytes.split()'s: 09 0a 0b 0c 0d 20)
+          d.delims[0] = dflt ? 0x100003e00ull : s.delims[0];
+          d.delims[1] = s.delims[1];
+          d.slot = s.slot;
+          d.max_elems = s.max_elems;
+          d.max_tokens = s.max_tokens;
+          d.lower = (s.flags & TFRG_TOK_LOWER_ASCII) ? 1u : 0u;
+          d.const_len = const_len_of(c, s.slot, true);
+          d.const_off = const_off_of(c, s.slot, true);
+        }
+        HIP_TRY(launch_tokens(a, st));
+        return 0;
+      },
+      [m](const tfrg_tok_spec& s, hipStream_t st) -> int {
         HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
         return 0;
       });

@@ -34,6 +34,7 @@
 
 #include "tfrg_elem_rows.h"
 #include "tfrg_ids.h"
+#include "tfrg_ids_dev.h"
 #include "tfrg_internal.h"
 #include "tfrg_vocab.h"
 
@@ -107,57 +108,7 @@ __global__ __launch_bounds__(kIdsScanThreads) void k_id_scan(const IdsArgs) {
 }
 
 // ------------------------------------------------------------------ 3. row offsets and ids
-// A byte string behind a buffer resource: the batch or the materialized column (an element), or the
-// vocabulary's blob (a word). Loads at or past `bound` give zeros without a memory access.
-struct Src {
-  __amdgpu_buffer_rsrc_t rsrc;
-  uint32_t bound;
-};
-
-// The k-th 8-byte word of the string of L bytes at byte `off` of the source, k < ceil(L / 8), zero-padded
-// after the string's end and reading zeros past the bound: three aligned dwords shifted into place
-// (bound <= 0xfffffff0, so p0 + 8 does not wrap)
-__device__ __forceinline__ uint64_t word8(const Src& s, uint32_t off, uint32_t L, uint32_t k) {
-  const uint64_t p = (uint64_t)off + ((uint64_t)k << 3);
-  uint32_t lo = 0u, hi = 0u;
-  if (p < s.bound) {
-    const uint32_t p0 = (uint32_t)p & ~3u, sh = (uint32_t)p & 3u;
-    const uint32_t d0 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(s.rsrc, p0, 0, 0);
-    const uint32_t d1 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(s.rsrc, p0 + 4u, 0, 0);
-    const uint32_t d2 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(s.rsrc, p0 + 8u, 0, 0);
-    lo = __builtin_amdgcn_alignbyte(d1, d0, sh);
-    hi = __builtin_amdgcn_alignbyte(d2, d1, sh);
-  }
-  const uint32_t rem = L - (k << 3);  // >= 1 bytes of the string from this word on
-  if (rem < 8u) {
-    lo &= bytes_mask(rem);
-    hi &= bytes_mask(rem > 4u ? rem - 4u : 0u);
-  }
-  return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint32_t words_of(uint32_t L) { return (L >> 3) + ((L & 7u) != 0u); }
-
-// The word of the vocabulary equal to the element (off, L) whose hash is h: its index, or kVocabEmpty.
-// From the home slot over at most max_probe + 1 slots, ending at an empty one; a candidate's length is
-// compared first, then its bytes.
-__device__ __forceinline__ uint32_t probe(KSpec s, const Src& in, const Src& blob, uint32_t off, uint32_t L, uint64_t h) {
-  const uint32_t mask = s->mask, nw = words_of(L);
-  uint32_t slot = (uint32_t)h & mask;
-#pragma unroll 1
-  for (uint32_t d = 0; d <= s->max_probe; ++d, slot = (slot + 1u) & mask) {
-    const uint32_t w = s->table[slot];
-    if (w == kVocabEmpty) break;
-    const uint32_t o0 = s->w_offs[w];
-    if (s->w_offs[w + 1u] - o0 != L) continue;
-    bool eq = true;
-#pragma unroll 1
-    for (uint32_t k = 0; k < nw && eq; ++k) eq = word8(in, off, L, k) == word8(blob, o0, L, k);
-    if (eq) return w;
-  }
-  return kVocabEmpty;
-}
-
+// (the strings behind buffer resources, the probe and the id rule: tfrg_ids_dev.h)
 // dynamic LDS as k_id_len
 __global__ __launch_bounds__(kBlk) void k_id_write(const IdsArgs) {
   extern __shared__ __attribute__((aligned(16))) uint8_t id_lds[];
@@ -229,16 +180,8 @@ __global__ __launch_bounds__(kBlk) void k_id_write(const IdsArgs) {
       if (!on[i]) continue;
       const uint64_t hv = hash_finish(h[i], (uint64_t)L[i]);
       uint32_t w = kVocabEmpty;
-      if (has_vocab && L[i] <= max_word) w = probe(ks, in, blob, off[i], L[i], hv);
-      int64_t id;
-      if (w != kVocabEmpty) {
-        id = ks->w_ids[w];
-      } else {
-        ++unmatched;
-        id = ks->default_id;
-        // (the sum wraps as two's complement: added as unsigned)
-        if (nb) id = (int64_t)((uint64_t)ks->oov_base + (pow2 ? hv & (nb - 1ull) : hv % nb));
-      }
+      if (has_vocab && L[i] <= max_word) w = probe<false>(ks, in, blob, off[i], L[i], hv);
+      const int64_t id = id_rule(ks, w, hv, nb, pow2, unmatched);
       if (e[i] < ecap) out[e[i]] = id;
     }
   }

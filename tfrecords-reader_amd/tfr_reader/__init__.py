@@ -17,6 +17,7 @@ from tfr_reader.reader import (
     load_from_directory,
     set_devices,
 )
+from tfr_reader.tokens import TokenIds
 
 __all__ = [
     "ElementIds",
@@ -27,6 +28,7 @@ __all__ = [
     "Resize",
     "TFRecordDatasetReader",
     "TFRecordFileReader",
+    "TokenIds",
     "Vocabulary",
     "inspect_dataset_example",
     "join_path",

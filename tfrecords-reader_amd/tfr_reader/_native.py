@@ -239,6 +239,28 @@ class TfrgIdsSpec(C.Structure):
 
 IDS_MAX_SPECS = 32
 IDS_SCAN_THREADS = 1024  # (csrc/tfrg_ids.h: the tile sums its scan kernel takes per pass)
+
+
+class TfrgTokSpec(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("max_elems", C.c_uint32),
+        ("max_tokens", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("delims", C.c_uint64 * 2),
+        ("vocab", C.c_void_p),
+        ("num_oov_buckets", C.c_uint64),
+        ("oov_base", C.c_int64),
+        ("default_id", C.c_int64),
+        ("tok_cap", C.c_uint64),
+        ("ids", C.c_void_p),
+        ("row_offsets", C.c_void_p),
+    ]
+
+
+TOK_MAX_SPECS = 16
+TOK_LOWER_ASCII = 1
+TOK_SCAN_THREADS = 1024  # (csrc/tfrg_tokens.h: the tile sums its scan kernel takes per pass)
 VOCAB_EMPTY = 0xFFFFFFFF  # a slot of a vocabulary's table without a word
 VOCAB_MIN_CAPACITY = 16
 
@@ -381,6 +403,9 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_vocab_lookup_host": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int64]),
     "tfrg_result_elem_ids": (C.c_int, [C.c_void_p, C.POINTER(TfrgIdsSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                        C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tfrg_result_token_ids": (C.c_int, [C.c_void_p, C.POINTER(TfrgTokSpec), C.c_uint32, C.c_void_p, C.c_uint32,
+                                        C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tfrg_ctx_set_token_split": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tfrg_result_select_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgSelectTerm), C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -542,6 +542,21 @@ class HipDecoder:
 
         return I.decoder_element_ids(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
 
+    def set_token_split(self, nbytes: int) -> None:
+        """Bytes of a row up to which ``token_ids`` sweeps it by one lane, longer rows by one wave (8 to
+        65536; 0: the default 256). The result never depends on it."""
+        N.check(self._lib.tfrg_ctx_set_token_split(self._ctx, int(nbytes)), "tfrg_ctx_set_token_split")
+
+    def token_ids(self, specs, *, rows=None, capacity=None, out=None, stream: int | None = None):
+        """One int64 id per TOKEN of the ``bytes_list`` elements of the last decode (split at ASCII
+        delimiters, optionally lower-cased; then a vocabulary lookup, hash buckets, or both) as ``(ids,
+        row_offsets)`` torch tensors on this decoder's device, one pair per ``tfr_reader.tokens.TokenIds``
+        spec, for every record or for the list ``rows`` (tfrg_result_token_ids); see
+        ``tfr_reader.tokens.decoder_token_ids``."""
+        from tfr_reader import tokens as T  # noqa: PLC0415, N812
+
+        return T.decoder_token_ids(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
+
     def raw(self, specs, rows=None, out=None, stream: int | None = None, strict: bool = False):
         """Tensors stored as bytes (``image.tobytes()``, PCM, a float16 feature map) of the last decode,
         decoded, cast, scaled per channel and laid out -- ``[m, *shape]``, or planar ``[m, channels,
@@ -881,6 +896,14 @@ class BatchResult:
         from tfr_reader import ids as I  # noqa: PLC0415, N812
 
         return I.batch_element_ids(self, specs, rows)
+
+    def token_ids(self, specs, rows=None):
+        """``(ids, row_offsets)`` numpy arrays of ``tfr_reader.tokens.TokenIds`` specs from the fetched
+        columns (the host counterpart of ``HipDecoder.token_ids``, with a pure-Python split and table): a
+        ``TokensBatch`` with ``.totals`` and ``.stats``. ``rows``: as for ``ragged``."""
+        from tfr_reader import tokens as T  # noqa: PLC0415, N812
+
+        return T.batch_token_ids(self, specs, rows)
 
     def raw(self, specs, rows=None):
         """The outputs of ``tfr_reader.raw.Raw`` specs as numpy arrays from the fetched columns (the host
