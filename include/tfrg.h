@@ -831,6 +831,80 @@ int tfrg_result_token_ids(tfrg_ctx* ctx, const tfrg_tok_spec* specs, uint32_t n_
  * 8..65536, 0 = the default (256). A tuning/testing knob: the result never depends on it. */
 int tfrg_ctx_set_token_split(tfrg_ctx* ctx, uint32_t bytes);
 
+/* WordPiece ids: a text feature as the subword ids that BERT-family encoders take -- punctuation split
+ * off, every word cut greedily into the longest pieces of a vocabulary, [UNK] for a word that cannot be
+ * covered, [CLS] ... [SEP] around a row -- on the device. Rows, skipped rows, the taken elements
+ * (max_elems), the bytes of an element, stream order with consumer_stream, the single confirmation of an
+ * optimistic or hinted decode, the rows per tile (tfrg_ctx_set_ragged_tile), scratch from the context's
+ * arena and "two equal calls write equal bytes" are word for word tfrg_result_token_ids's. Per spec:
+ *   words: delims is tfrg_tok_spec's set (both words 0: the six bytes bytes.split() splits on). isolate is
+ *     a second set of ASCII bytes, each of which is a one-byte word of its own and ends any word next to
+ *     it (BERT's punctuation split); a byte in both sets is a delimiter. A word is otherwise a maximal
+ *     run of bytes that are in neither set; bytes >= 128 are word bytes, and an element boundary ends a
+ *     word. Both sets are tested on the bytes as stored. With TFRG_WP_LOWER_ASCII the bytes 'A'..'Z' of a
+ *     word become 'a'..'z' before any compare or hash; no other byte changes;
+ *   two vocabularies, ordinary tfrg_vocab objects on the context's device: vocab holds the pieces that
+ *     may begin a word, vocab_cont the continuation pieces WITHOUT their prefix ("##ing" is stored as
+ *     "ing": the device never concatenates a prefix). vocab_cont NULL: only whole words and nothing after
+ *     a first piece can match;
+ *   the pieces of a word s of L bytes, after lowering: if L > max_word_bytes (0 selects 100), the one
+ *     piece unk_id. Else from pos = 0: the largest end in (pos, L] with s[pos:end] in vocab (pos == 0) or
+ *     in vocab_cont (pos > 0) gives that word's id and pos = end. If no end matches at some pos, the
+ *     WHOLE word is the single piece unk_id and the pieces found before are discarded. Ends are byte
+ *     positions: with UTF-8 vocabularies this equals the character-level algorithm, because a cut inside
+ *     a code point leaves a string that is no valid UTF-8 and so is no word of the vocabulary. Bytes are
+ *     not normalised;
+ *   the pieces of a row are the pieces of the words of its taken elements, in order. Without
+ *     TFRG_WP_SPECIAL cnt(k) = min(pieces, max_pieces), all of them with max_pieces == 0: the row's FIRST
+ *     pieces, and the cut may fall inside a word. With TFRG_WP_SPECIAL every row that is not skipped is
+ *     cls_id, its first min(pieces, max_pieces - 2) pieces, sep_id (max_pieces == 0: all of them); a
+ *     skipped row stays empty;
+ *   row_offsets[0 .. m], T = row_offsets[m], tok_cap, a NULL ids for sizing and "nothing else in ids is
+ *     written" are as for tfrg_result_token_ids.
+ * d_totals: T. d_stats ([n_specs][4] u32, or NULL), counted over all taken pieces, stored or not: rows
+ * cut by max_pieces; words that became unk_id (too long, or uncovered); rows that are not skipped and
+ * have no word; skipped rows.
+ * Three launches (piece counts per tile of rows, kept in row_offsets; the scan of the tile sums; then row
+ * offsets and ids); no device value is read back. Cost: the bytes are read and the words matched twice,
+ * once to count and once to emit. A row of at most tfrg_ctx_set_token_split bytes is swept by one lane,
+ * a longer row by one wave; the words go through a queue in LDS to groups of 8 lanes, which probe 8
+ * candidate ends of a piece at once: a word of the vocabulary costs one probe latency, an uncovered word
+ * of L bytes ceil(L / 8). A row that has reached max_pieces is not read further. Without d_stats, rows
+ * whose first piece lies at or past tok_cap (all of them with ids NULL) are not matched a second time.
+ * TFRG_E_ARG (text in tfrg_last_error prefixed "tfrg_result_wordpiece_ids: ", nothing launched or
+ * written): everything tfrg_result_token_ids refuses about the context, the rows, m, the slot,
+ * row_offsets and ids; n_specs outside 1..TFRG_WP_MAX_SPECS; unknown flag bits; a nonzero reserved; vocab
+ * NULL; a vocabulary built host-only or on another device; max_word_bytes > TFRG_WP_MAX_WORD_BYTES;
+ * TFRG_WP_SPECIAL with max_pieces == 1.
+ * TFRG_WP_MAX_SPECS is 16 because the spec table travels as the kernel argument (4096 bytes).
+ * Out of scope: Unicode normalisation, accent stripping, CJK splitting, non-ASCII punctuation and
+ * whitespace; a piece-to-word map; BPE; a padded [m, max_pieces] output. */
+#define TFRG_WP_MAX_SPECS 16
+#define TFRG_WP_LOWER_ASCII 1u
+#define TFRG_WP_SPECIAL 2u
+#define TFRG_WP_MAX_WORD_BYTES 1024u
+typedef struct tfrg_wp_spec {
+  uint32_t slot;            /* a bytes_list slot, as in tfrg_set_schema */
+  uint32_t max_elems;       /* 0: every element of a row; else its first max_elems */
+  uint32_t max_pieces;      /* 0: every piece of a row; else at most that many ids, cls and sep included */
+  uint32_t flags;           /* TFRG_WP_LOWER_ASCII | TFRG_WP_SPECIAL; other bits refused */
+  uint64_t delims[2];       /* bit b of the 128: ASCII byte b separates words; both words 0: 09 0a 0b 0c 0d 20 */
+  uint64_t isolate[2];      /* bit b of the 128: ASCII byte b is a word of its own */
+  const tfrg_vocab* vocab;       /* the pieces that may begin a word; not NULL */
+  const tfrg_vocab* vocab_cont;  /* the continuation pieces without their prefix; or NULL */
+  int64_t unk_id;
+  int64_t cls_id;           /* read with TFRG_WP_SPECIAL only, as sep_id */
+  int64_t sep_id;
+  uint32_t max_word_bytes;  /* a longer word is unk_id; 0: 100; at most TFRG_WP_MAX_WORD_BYTES */
+  uint32_t reserved;        /* 0 */
+  uint64_t tok_cap;         /* ids that `ids` can hold */
+  int64_t* ids;             /* device [tok_cap], caller-owned; NULL: offsets and counters only */
+  int64_t* row_offsets;     /* device [m + 1], caller-owned, not NULL */
+} tfrg_wp_spec;             /* 120 bytes */
+int tfrg_result_wordpiece_ids(tfrg_ctx* ctx, const tfrg_wp_spec* specs, uint32_t n_specs,
+                              const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
+                              uint64_t* d_totals, uint32_t* d_stats, void* consumer_stream);
+
 /* Filtered row lists: the WHERE clause over the last result, on the device. Predicates over the
  * decoded columns in, the compacted list of the passing rows in device memory out -- usable as it is
  * as d_rows of tfrg_result_dense_rows / tfrg_result_ragged_rows of the same context(s), with the same

@@ -20,6 +20,7 @@
 #include "tfrg_elems.h"
 #include "tfrg_ids.h"
 #include "tfrg_tokens.h"
+#include "tfrg_wordpiece.h"
 #include "tfrg_ragged.h"
 #include "tfrg_select.h"
 #include "tfrg_frame.h"
@@ -142,6 +143,7 @@ struct Arena {
   DBuf el_tsum;  // tfrg_result_ragged_elems: the per-tile element counts and byte sums
   DBuf id_tsum;  // tfrg_result_elem_ids: the per-tile element counts
   DBuf tk_tsum;  // tfrg_result_token_ids: the per-tile token counts
+  DBuf wp_tsum;  // tfrg_result_wordpiece_ids: the per-tile piece counts
   DBuf sel_buf;  // tfrg_result_select_rows: the candidates' ballot words, then the per-tile sums
   template <class F>
   void each(F f) {
@@ -150,7 +152,7 @@ struct Arena {
                          &totals, &kind_totals, &ident, &i64, &f32, &b_off, &b_len, &big_list, &slow_list, &miss, &info,
                          &tsum, &crc_rec, &crc_base, &crc_part, &dq, &dq_cnt, &lmask, &rlist, &bdata, &boff64, &blb,
                          &bbig, &tpl, &spec, &fr_tab, &fr_dev, &rg_tsum, &el_tsum,
-                         &id_tsum, &tk_tsum, &sel_buf};
+                         &id_tsum, &tk_tsum, &wp_tsum, &sel_buf};
     static_assert(sizeof(all) / sizeof(*all) * sizeof(DBuf) == sizeof(Arena), "a buffer is missing from the list");
     for (DBuf* b : all) f(*b);
   }
@@ -2002,6 +2004,86 @@ int tfrg_result_token_ids(tfrg_ctx* c, const tfrg_tok_spec* specs, uint32_t n_sp
         return 0;
       },
       [m](const tfrg_tok_spec& s, hipStream_t st) -> int {
+        HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
+        return 0;
+      });
+}
+
+// One id per WordPiece of the words of a bytes_list slot for a list of rows (tfrg_wordpiece.h: piece
+// counts, tile scan, row offsets and ids). Every grid size comes from m, n_specs and the tile: nothing is
+// read back.
+int tfrg_result_wordpiece_ids(tfrg_ctx* c, const tfrg_wp_spec* specs, uint32_t n_specs, const void* d_rows,
+                              uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
+                              void* consumer_stream) {
+  static_assert(TFRG_WP_MAX_SPECS == kWpMaxSpecs && TFRG_WP_LOWER_ASCII == kWpLowerAscii && TFRG_WP_SPECIAL == kWpSpecial &&
+                    TFRG_WP_MAX_WORD_BYTES == kWpMaxWordBytes,
+                "tfrg.h mirrors tfrg_wordpiece.h");
+  static_assert(sizeof(tfrg_wp_spec) == 120, "tfrg.h states the size");
+  static_assert(kWpNoLen == kElemsNoLen && kWpOffStored == kElemsOffStored, "const_len_of / const_off_of serve tfrg_wordpiece.h");
+  const RowListKind kind{"tfrg_result_wordpiece_ids", TFRG_WP_MAX_SPECS, &Arena::wp_tsum, 1, 0, 0};  // (no split)
+  return result_row_list<WpArgs>(
+      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
+      [c](const tfrg_wp_spec& s, const std::string& at, const auto& bad, bool&) -> int {
+        if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
+        if (!s.row_offsets) return bad(at + "row_offsets is NULL");
+        if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.ids & 7u)) return bad(at + "row_offsets and ids must be 8-byte aligned");
+        if (s.flags & ~(TFRG_WP_LOWER_ASCII | TFRG_WP_SPECIAL)) return bad(at + "unknown flag bits " + std::to_string(s.flags));
+        if (s.reserved) return bad(at + "reserved must be 0");
+        if (!s.vocab) return bad(at + "vocab is NULL");
+        for (const tfrg_vocab* v : {s.vocab, s.vocab_cont}) {
+          if (v && !v->d_mem) return bad(at + "a vocabulary was built host-only (device -1)");
+          if (v && v->device != c->device)
+            return bad(at + "a vocabulary is on device " + std::to_string(v->device) + ", the context on " + std::to_string(c->device));
+        }
+        if (s.max_word_bytes > TFRG_WP_MAX_WORD_BYTES)
+          return bad(at + "max_word_bytes must be at most " + std::to_string(TFRG_WP_MAX_WORD_BYTES));
+        if ((s.flags & TFRG_WP_SPECIAL) && s.max_pieces == 1) return bad(at + "max_pieces 1 leaves no room for cls and sep");
+        return 0;
+      },
+      [c, specs](WpArgs& a, uint32_t, hipStream_t st) -> int {
+        a.split = c->token_split;
+        for (uint32_t i = 0; i < a.n_specs; ++i) {
+          const tfrg_wp_spec& s = specs[i];
+          WpSpec& d = a.sp[i];
+          d.ids = s.ids;
+          d.row_offsets = s.row_offsets;
+          d.tok_cap = s.tok_cap;
+          const struct {
+            const tfrg_vocab* v;
+            WpTab* t;
+          } tabs[2] = {{s.vocab, &d.first}, {s.vocab_cont, &d.cont}};
+          for (const auto& e : tabs) {
+            if (!e.v) continue;
+            e.t->table = e.v->d_table;
+            e.t->w_offs = e.v->d_offs;
+            e.t->blob = e.v->d_blob;
+            e.t->w_ids = e.v->d_ids;
+            e.t->mask = (uint32_t)e.v->table.size() - 1u;
+            e.t->max_probe = e.v->max_probe;
+            e.t->max_word = e.v->max_word;
+            e.t->blob_bound = e.v->d_blob_bound;
+          }
+          const bool dflt = !s.delims[0] && !s.delims[1];  // (bytes.split()'s: 09 0a 0b 0c 0d 20)
+          d.delims[0] = dflt ? 0x100003e00ull : s.delims[0];
+          d.delims[1] = s.delims[1];
+          d.isolate[0] = s.isolate[0] & ~d.delims[0];  // (a byte in both sets is a delimiter)
+          d.isolate[1] = s.isolate[1] & ~d.delims[1];
+          d.cls_id = s.cls_id;
+          d.sep_id = s.sep_id;
+          d.unk_id = s.unk_id;
+          d.slot = s.slot;
+          d.max_elems = s.max_elems;
+          d.special = (s.flags & TFRG_WP_SPECIAL) ? 1u : 0u;
+          d.limit = !s.max_pieces ? kWpUnbounded : s.max_pieces - 2u * d.special;
+          d.lower = (s.flags & TFRG_WP_LOWER_ASCII) ? 1u : 0u;
+          d.const_len = const_len_of(c, s.slot, true);
+          d.const_off = const_off_of(c, s.slot, true);
+          d.max_word_bytes = s.max_word_bytes ? s.max_word_bytes : kWpDefaultWordBytes;
+        }
+        HIP_TRY(launch_wordpiece(a, st));
+        return 0;
+      },
+      [m](const tfrg_wp_spec& s, hipStream_t st) -> int {
         HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
         return 0;
       });

@@ -18,6 +18,7 @@ from tfr_reader.reader import (
     set_devices,
 )
 from tfr_reader.tokens import TokenIds
+from tfr_reader.wordpiece import WordPieceIds, WordPieceVocab
 
 __all__ = [
     "ElementIds",
@@ -30,6 +31,8 @@ __all__ = [
     "TFRecordFileReader",
     "TokenIds",
     "Vocabulary",
+    "WordPieceIds",
+    "WordPieceVocab",
     "inspect_dataset_example",
     "join_path",
     "load_from_directory",

@@ -261,6 +261,33 @@ class TfrgTokSpec(C.Structure):
 TOK_MAX_SPECS = 16
 TOK_LOWER_ASCII = 1
 TOK_SCAN_THREADS = 1024  # (csrc/tfrg_tokens.h: the tile sums its scan kernel takes per pass)
+
+
+class TfrgWpSpec(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("max_elems", C.c_uint32),
+        ("max_pieces", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("delims", C.c_uint64 * 2),
+        ("isolate", C.c_uint64 * 2),
+        ("vocab", C.c_void_p),
+        ("vocab_cont", C.c_void_p),
+        ("unk_id", C.c_int64),
+        ("cls_id", C.c_int64),
+        ("sep_id", C.c_int64),
+        ("max_word_bytes", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("tok_cap", C.c_uint64),
+        ("ids", C.c_void_p),
+        ("row_offsets", C.c_void_p),
+    ]
+
+
+WP_MAX_SPECS = 16
+WP_LOWER_ASCII = 1
+WP_SPECIAL = 2
+WP_MAX_WORD_BYTES = 1024
 VOCAB_EMPTY = 0xFFFFFFFF  # a slot of a vocabulary's table without a word
 VOCAB_MIN_CAPACITY = 16
 
@@ -406,6 +433,8 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_result_token_ids": (C.c_int, [C.c_void_p, C.POINTER(TfrgTokSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                         C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_ctx_set_token_split": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "tfrg_result_wordpiece_ids": (C.c_int, [C.c_void_p, C.POINTER(TfrgWpSpec), C.c_uint32, C.c_void_p, C.c_uint32,
+                                            C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_result_select_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgSelectTerm), C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_uint32, C.c_void_p]),

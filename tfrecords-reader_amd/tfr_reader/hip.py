@@ -557,6 +557,17 @@ class HipDecoder:
 
         return T.decoder_token_ids(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
 
+    def wordpiece_ids(self, specs, *, rows=None, capacity=None, out=None, stream: int | None = None):
+        """The WordPiece ids of the ``bytes_list`` elements of the last decode (punctuation split off, every
+        word cut greedily into the longest pieces of a vocabulary, ``[UNK]``, optionally ``[CLS]`` ...
+        ``[SEP]``) as ``(ids, row_offsets)`` torch tensors on this decoder's device, one pair per
+        ``tfr_reader.wordpiece.WordPieceIds`` spec, for every record or for the list ``rows``
+        (tfrg_result_wordpiece_ids); ``capacity=None`` sizes the ids with a first call. See
+        ``tfr_reader.wordpiece.decoder_wordpiece_ids``."""
+        from tfr_reader import wordpiece as W  # noqa: PLC0415, N812
+
+        return W.decoder_wordpiece_ids(self, specs, rows=rows, capacity=capacity, out=out, stream=stream)
+
     def raw(self, specs, rows=None, out=None, stream: int | None = None, strict: bool = False):
         """Tensors stored as bytes (``image.tobytes()``, PCM, a float16 feature map) of the last decode,
         decoded, cast, scaled per channel and laid out -- ``[m, *shape]``, or planar ``[m, channels,
@@ -904,6 +915,14 @@ class BatchResult:
         from tfr_reader import tokens as T  # noqa: PLC0415, N812
 
         return T.batch_token_ids(self, specs, rows)
+
+    def wordpiece_ids(self, specs, rows=None):
+        """``(ids, row_offsets)`` numpy arrays of ``tfr_reader.wordpiece.WordPieceIds`` specs from the fetched
+        columns (the host counterpart of ``HipDecoder.wordpiece_ids``, in pure Python): a ``WordPieceBatch``
+        with ``.totals`` and ``.stats``. ``rows``: as for ``ragged``."""
+        from tfr_reader import wordpiece as W  # noqa: PLC0415, N812
+
+        return W.batch_wordpiece_ids(self, specs, rows)
 
     def raw(self, specs, rows=None):
         """The outputs of ``tfr_reader.raw.Raw`` specs as numpy arrays from the fetched columns (the host
