@@ -567,6 +567,80 @@ int tfrg_result_raw_resize(tfrg_ctx* ctx, const tfrg_resize_spec* specs, uint32_
                            uint32_t rows_dtype, uint32_t m, int64_t row0, const int32_t* d_boxes,
                            const uint8_t* d_flip, uint32_t* d_stats, uint32_t* d_skipped, void* consumer_stream);
 
+/* Log-mel spectrograms from PCM bytes features: what tf.signal.stft + linear_to_mel_weight_matrix + log, or
+ * torch.stft + a matmul + a log, compute, for a list of rows in one launch per tile size. Element 0 of a
+ * bytes_list slot is a little-endian signal of `src` elements (any TFRG_RAW_* type), interleaved over
+ * `channels`: sample n is element n * channels + channel. Rows, skipped rows, d_stats, d_skipped, stream
+ * order and confirmation are tfrg_result_raw_rows's. Per spec and output row k whose record g is not
+ * skipped, with L the element's whole samples (byte length / esz / channels, rounded down: a trailing
+ * partial sample does not exist), n_fft, n_bins = n_fft / 2 + 1, window, n_mels and fb those of `mel`:
+ *   s[n] = x[n] for n < min(L, samples), else 0 (the signal cut or zero-padded to `samples`);
+ *   frame t, t < frames: center 0: s[t * hop + j], j < n_fft, which needs (frames - 1) * hop + n_fft <=
+ *     samples; center 1: y[t * hop - n_fft / 2 + j] with y the reflection of s about its first and last
+ *     sample (torch.stft(center=True, pad_mode="reflect")), which needs samples > n_fft / 2 and
+ *     (frames - 1) * hop <= samples;
+ *   X[t][b] = sum_j window[j] * frame_t[j] * exp(-2 pi i b j / n_fft), b < n_bins; P = |X| (power 1) or
+ *     |X|^2 (power 2); mel[t][f] = sum_b fb[f][b] * P[t][b];
+ *   v = mel (TFRG_MEL_LINEAR), ln(max(mel, floor)) (TFRG_MEL_LN) or log10(max(mel, floor)) (TFRG_MEL_LOG10);
+ *   out[k][f][t] = fmaf(v, scale, bias), rounded once to the output type (frames contiguous: the layout
+ *     torchaudio and Whisper use);
+ *   lengths[k] = the element's byte length.
+ * Arithmetic: float32 throughout, the two sums on the float32 matrix units (v_mfma_f32_16x16x4_f32) in an
+ * unspecified order, |X|^2 as fmaf(re, re, im * im), sqrtf, ln and log10 evaluated in float64 and rounded once
+ * to float32. A record without the element (an empty or absent list) gives a row of `fill`, which
+ * is not transformed: it is not the spectrogram of silence, which an element of zero bytes gives.
+ * d_stats[spec]: rows whose byte length is above samples * channels * esz (truncated), below it (padded),
+ * without an element (empty), with more than one (multi; element 0 is used).
+ * The tables live in a tfrg_mel, made once per (n_fft, window, filterbank) and device: window[n_fft] and
+ * fb[n_mels][n_bins] are the caller's float32 arrays (the library takes no side on HTK, Slaney or Whisper
+ * conventions). tfrg_mel_create builds the windowed cos / sin basis in float64, the angle reduced exactly as
+ * (b * j) mod n_fft before the trig call, rounds once to float32 and uploads both tables in the order the
+ * kernel loads them; it synchronises the device. tfrg_mel_destroy synchronises the device before it frees.
+ * tfrg_mel_info: any pointer may be NULL. tfrg_mel_tile_frames: the frames of one work item of the kernel
+ * for this n_fft and hop (64, 32 or 16; 0 for arguments out of range): tests put seams there.
+ * TFRG_E_ARG (text in tfrg_last_error, prefixed with the function's name; nothing is launched or written):
+ * tfrg_mel_create: a negative device, n_fft odd or outside 2..TFRG_MEL_MAX_FFT, n_mels outside
+ * 1..TFRG_MEL_MAX_MELS, a NULL or non-finite window or fb. tfrg_result_mel: what tfrg_result_raw_rows
+ * refuses of the arguments both have, out = TFRG_RAW_OUT_SAME, a NULL mel or one of another device, channel
+ * >= channels, samples outside 1..TFRG_MEL_MAX_SAMPLES, frames outside 1..TFRG_MEL_MAX_FRAMES, hop outside
+ * 1..n_fft, a frame past `samples` (above), center above 1, power other than 1 or 2, an unknown log, a log
+ * with a floor that is not finite and positive, a non-finite scale or bias, a misaligned lengths. */
+#define TFRG_MEL_LINEAR 0
+#define TFRG_MEL_LN 1
+#define TFRG_MEL_LOG10 2
+#define TFRG_MEL_MAX_FFT 2048
+#define TFRG_MEL_MAX_MELS 128
+#define TFRG_MEL_MAX_SAMPLES 16777216 /* 2^24 */
+#define TFRG_MEL_MAX_FRAMES 1048576   /* 2^20 */
+typedef struct tfrg_mel tfrg_mel;
+int tfrg_mel_create(int device, uint32_t n_fft, const float* window, uint32_t n_mels, const float* fb, tfrg_mel** out);
+int tfrg_mel_destroy(tfrg_mel* mel);
+int tfrg_mel_info(const tfrg_mel* mel, uint32_t* n_fft, uint32_t* n_mels, uint32_t* n_bins, uint64_t* device_bytes);
+uint32_t tfrg_mel_tile_frames(uint32_t n_fft, uint32_t hop);
+typedef struct tfrg_mel_spec {
+  uint32_t slot;      /* a bytes_list slot: the signal is element 0 */
+  uint32_t src;       /* TFRG_RAW_U8 .. TFRG_RAW_F32 */
+  uint32_t out;       /* TFRG_RAW_OUT_F32 / _F16 / _BF16 */
+  uint32_t channels;  /* 1..TFRG_RAW_MAX_CHANNELS */
+  uint32_t channel;   /* below channels */
+  uint32_t samples;   /* the signal's fixed length, 1..TFRG_MEL_MAX_SAMPLES */
+  uint32_t frames;    /* 1..TFRG_MEL_MAX_FRAMES */
+  uint32_t hop;       /* 1..n_fft */
+  uint32_t center;    /* 0 / 1 */
+  uint32_t power;     /* 1 / 2 */
+  uint32_t log;       /* TFRG_MEL_LINEAR / _LN / _LOG10 */
+  uint32_t fill;      /* raw low bits of the value of a row without an element, in the output type */
+  float floor;        /* > 0 with a log */
+  float scale;
+  float bias;
+  uint32_t reserved;  /* 0 */
+  const tfrg_mel* mel;
+  void* out_ptr;      /* device, [m][n_mels][frames] of the output type, caller-owned */
+  int32_t* lengths;   /* device [m], or NULL */
+} tfrg_mel_spec;      /* 88 bytes */
+int tfrg_result_mel(tfrg_ctx* ctx, const tfrg_mel_spec* specs, uint32_t n_specs, const void* d_rows, uint32_t rows_dtype,
+                    uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped, void* consumer_stream);
+
 /* Ragged minibatches: packed values and offsets for a list of rows (the tf.io.parse_example
  * VarLenFeature / RaggedTensor side, next to the FixedLenFeature side above; the packed form varlen
  * attention, jagged tensors and EmbeddingBag take). Per spec and output row k < m, with

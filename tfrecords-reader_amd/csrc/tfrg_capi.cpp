@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <numeric>
 #include <string>
@@ -17,6 +18,7 @@
 #include "tfrg_dense.h"
 #include "tfrg_raw.h"
 #include "tfrg_resize.h"
+#include "tfrg_mel.h"
 #include "tfrg_elems.h"
 #include "tfrg_ids.h"
 #include "tfrg_tokens.h"
@@ -1747,6 +1749,217 @@ int tfrg_result_raw_resize(tfrg_ctx* c, const tfrg_resize_spec* specs, uint32_t 
       if (mine) lds_words = std::max(lds_words, (aa ? resize_aa_lds_words : resize_lds_words)(d.out_w, d.channels));
     }
     if (m && c->res.req.n) HIP_TRY((aa ? launch_resize_aa : launch_resize)(a, blocks, lds_words * 4u, st));
+  }
+  return fence_close(c, st, cs);
+}
+
+// ---- The tables of a mel transform (tfrg_mel.h has their layout): the windowed cos / -sin basis and the
+// filterbank, each in the order the lanes of k_mel load it, built in float64 and rounded once.
+int tfrg_mel_create(int device, uint32_t n_fft, const float* window, uint32_t n_mels, const float* fb, tfrg_mel** out) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_mel_create: " + why);
+    return TFRG_E_ARG;
+  };
+  static_assert(TFRG_MEL_MAX_FFT == kMelMaxFft && TFRG_MEL_MAX_MELS == kMelMaxMels && TFRG_MEL_MAX_SAMPLES == kMelMaxSamples &&
+                    TFRG_MEL_MAX_FRAMES == kMelMaxFrames && TFRG_MEL_LINEAR == kMelLinear && TFRG_MEL_LN == kMelLn &&
+                    TFRG_MEL_LOG10 == kMelLog10,
+                "tfrg.h mirrors tfrg_mel.h");
+  if (!out) return bad("out is NULL");
+  *out = nullptr;
+  if (device < 0) return bad("device must be a device ordinal");
+  if (n_fft < 2 || n_fft > TFRG_MEL_MAX_FFT || (n_fft & 1u)) return bad("n_fft must be even and in 2.." + std::to_string(TFRG_MEL_MAX_FFT));
+  if (n_mels == 0 || n_mels > TFRG_MEL_MAX_MELS) return bad("n_mels must be 1.." + std::to_string(TFRG_MEL_MAX_MELS));
+  if (!window || !fb) return bad("window or fb is NULL");
+  const uint32_t n_bins = n_fft / 2 + 1, KG = mel_k16(n_fft) / kMelKGroup, NCH = mel_chunks(n_fft), MT = mel_mtiles(n_mels);
+  for (uint32_t k = 0; k < n_fft; ++k)
+    if (!std::isfinite(window[k])) return bad("window[" + std::to_string(k) + "] is not finite");
+  for (uint64_t i = 0; i < (uint64_t)n_mels * n_bins; ++i)
+    if (!std::isfinite(fb[i])) return bad("fb[" + std::to_string(i) + "] is not finite");
+  const uint64_t nb = mel_basis_words(n_fft), nf = mel_fb_words(n_fft, n_mels);
+  std::vector<float> h;
+  tfrg_mel* mel = new (std::nothrow) tfrg_mel;
+  try {
+    h.assign(nb + nf, 0.f);
+  } catch (const std::bad_alloc&) {
+    delete mel;
+    mel = nullptr;
+  }
+  if (!mel) {
+    set_error("tfrg_mel_create: out of memory");
+    return TFRG_E_NOMEM;
+  }
+  const double step = 6.283185307179586476925286766559 / (double)n_fft;
+  for (uint32_t bt = 0; bt < NCH * 4u; ++bt)
+    for (uint32_t kg = 0; kg < KG; ++kg)
+      for (uint32_t lane = 0; lane < 64; ++lane)
+        for (uint32_t j = 0; j < 4; ++j) {
+          const uint32_t k = kMelKGroup * kg + 4u * j + lane / 16u, col = lane % 16u, bin = kMelTileBins * bt + col / 2u;
+          if (k >= n_fft || bin >= n_bins) continue;
+          // (the angle reduced exactly: bin * k mod n_fft, before the trig call)
+          const double ang = step * (double)(((uint64_t)bin * k) % n_fft);
+          h[(((uint64_t)bt * KG + kg) * 64u + lane) * 4u + j] = (float)((double)window[k] * ((col & 1u) ? -std::sin(ang) : std::cos(ang)));
+        }
+  for (uint32_t mt = 0; mt < MT; ++mt)
+    for (uint32_t ch = 0; ch < NCH; ++ch)
+      for (uint32_t hh = 0; hh < 2; ++hh)
+        for (uint32_t lane = 0; lane < 64; ++lane)
+          for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t f = 16u * mt + lane % 16u, bin = kMelChunkBins * ch + 16u * hh + 4u * j + lane / 16u;
+            if (f < n_mels && bin < n_bins) h[nb + ((((uint64_t)mt * NCH + ch) * 2u + hh) * 64u + lane) * 4u + j] = fb[(uint64_t)f * n_bins + bin];
+          }
+  void* p = nullptr;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipMalloc(&p, h.size() * 4);
+  if (e == hipSuccess) e = hipMemcpy(p, h.data(), h.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    if (p) (void)hipFree(p);
+    delete mel;
+    set_error(std::string("tfrg_mel_create: upload: ") + hipGetErrorString(e));
+    return TFRG_E_HIP;
+  }
+  mel->device = device;
+  mel->n_fft = n_fft;
+  mel->n_mels = n_mels;
+  mel->d_mem = p;
+  mel->d_basis = static_cast<const float*>(p);
+  mel->d_fb = mel->d_basis + nb;
+  mel->device_bytes = h.size() * 4;
+  *out = mel;
+  return 0;
+}
+
+int tfrg_mel_destroy(tfrg_mel* mel) {
+  if (!mel) return 0;
+  HIP_TRY(hipSetDevice(mel->device));
+  HIP_TRY(hipDeviceSynchronize());  // (work already queued may still read the tables)
+  HIP_TRY(hipFree(mel->d_mem));
+  delete mel;
+  return 0;
+}
+
+int tfrg_mel_info(const tfrg_mel* mel, uint32_t* n_fft, uint32_t* n_mels, uint32_t* n_bins, uint64_t* device_bytes) {
+  if (!mel) {
+    set_error("tfrg_mel_info: mel is NULL");
+    return TFRG_E_ARG;
+  }
+  if (n_fft) *n_fft = mel->n_fft;
+  if (n_mels) *n_mels = mel->n_mels;
+  if (n_bins) *n_bins = mel->n_fft / 2 + 1;
+  if (device_bytes) *device_bytes = mel->device_bytes;
+  return 0;
+}
+
+uint32_t tfrg_mel_tile_frames(uint32_t n_fft, uint32_t hop) {
+  if (n_fft < 2 || n_fft > TFRG_MEL_MAX_FFT || hop == 0 || hop > n_fft) return 0;
+  return mel_tile_frames(n_fft, hop);
+}
+
+// Log-mel spectrograms for a list of rows (tfrg_mel.h): one launch of k_mel per tile size among the specs
+// (at most three). The frame is tfrg_result_raw_rows's; its own are the framing checks and the tile of a spec.
+int tfrg_result_mel(tfrg_ctx* c, const tfrg_mel_spec* specs, uint32_t n_specs, const void* d_rows, uint32_t rows_dtype,
+                    uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped, void* consumer_stream) {
+  auto bad = [](const std::string& why) {
+    set_error("tfrg_result_mel: " + why);
+    return TFRG_E_ARG;
+  };
+  static_assert(sizeof(tfrg_mel_spec) == 88, "tfrg.h states the size");
+  if (const int rc = check_specs(c, specs, n_specs, TFRG_RAW_MAX_SPECS, bad)) return rc;
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_mel_spec& s = specs[i];
+    const std::string at = "spec " + std::to_string(i) + ": ";
+    if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
+    if (s.src >= kRawSrcs) return bad(at + "unknown src " + std::to_string(s.src));
+    if (s.out >= kRawOutSame) return bad(at + "out must be TFRG_RAW_OUT_F32, _F16 or _BF16, not " + std::to_string(s.out));
+    if (!s.mel) return bad(at + "mel is NULL");
+    if (s.mel->device != c->device)
+      return bad(at + "the tables are on device " + std::to_string(s.mel->device) + ", the context on " + std::to_string(c->device));
+    const uint32_t n_fft = s.mel->n_fft;
+    if (s.channels == 0 || s.channels > TFRG_RAW_MAX_CHANNELS) return bad(at + "channels must be 1.." + std::to_string(TFRG_RAW_MAX_CHANNELS));
+    if (s.channel >= s.channels) return bad(at + "channel must be below channels");
+    if (s.samples == 0 || s.samples > TFRG_MEL_MAX_SAMPLES) return bad(at + "samples must be 1.." + std::to_string(TFRG_MEL_MAX_SAMPLES));
+    if (s.frames == 0 || s.frames > TFRG_MEL_MAX_FRAMES) return bad(at + "frames must be 1.." + std::to_string(TFRG_MEL_MAX_FRAMES));
+    if (s.hop == 0 || s.hop > n_fft) return bad(at + "hop must be 1..n_fft");
+    if (s.center > 1) return bad(at + "center must be 0 or 1");
+    if (s.power != 1 && s.power != 2) return bad(at + "power must be 1 or 2");
+    if (s.log >= kMelLogs) return bad(at + "unknown log " + std::to_string(s.log));
+    if (s.log != TFRG_MEL_LINEAR && !(s.floor > 0.f && std::isfinite(s.floor))) return bad(at + "a log needs a finite floor > 0");
+    if (!std::isfinite(s.scale) || !std::isfinite(s.bias)) return bad(at + "scale and bias must be finite");
+    const uint64_t last = (uint64_t)(s.frames - 1) * s.hop;
+    if (s.center) {
+      if (s.samples <= n_fft / 2) return bad(at + "center reflects: samples must exceed n_fft / 2");
+      if (last > s.samples) return bad(at + "the last frame's centre lies past samples");
+    } else if (last + n_fft > s.samples) {
+      return bad(at + "the last frame ends past samples");
+    }
+    if (!s.out_ptr) return bad(at + "out_ptr is NULL");
+    if ((uintptr_t)s.out_ptr & (raw_out_size(s.src, s.out) - 1u)) return bad(at + "out_ptr must be aligned to the output element size");
+    if ((uintptr_t)s.lengths & 3u) return bad(at + "lengths must be 4-byte aligned");
+    if (s.reserved) return bad(at + "reserved must be 0");
+  }
+  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
+  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = confirm_pending(c)) return rc;
+  MelArgs a{};
+  a.rows = d_rows;
+  a.rows64 = d_rows && rows_dtype == TFRG_ROWS_I64;
+  a.m = m;
+  a.row0 = row0;
+  a.skipped = d_skipped;
+  fill_columns(c, a);
+  fill_bytes_source(c, a);
+  a.stats = d_stats;
+  a.n_specs = n_specs;
+  for (uint32_t i = 0; i < n_specs; ++i) {
+    const tfrg_mel_spec& s = specs[i];
+    MelSpec& d = a.sp[i];
+    d.out = s.out_ptr;
+    d.lengths = s.lengths;
+    d.basis = s.mel->d_basis;
+    d.fb = s.mel->d_fb;
+    d.fill = s.out == TFRG_RAW_OUT_F32 ? s.fill : s.fill & 0xffffu;
+    d.slot = s.slot;
+    d.src = s.src;
+    d.outt = s.out;
+    d.channels = s.channels;
+    d.channel = s.channel;
+    d.samples = s.samples;
+    d.frames = s.frames;
+    d.hop = s.hop;
+    d.n_fft = s.mel->n_fft;
+    d.n_mels = s.mel->n_mels;
+    d.center = s.center;
+    d.power = s.power;
+    d.log = s.log;
+    d.floor = s.floor;
+    d.scale = s.scale;
+    d.bias = s.bias;
+    d.hop_magic = s.hop >= 2 ? (uint32_t)((0x100000000ull + s.hop - 1) / s.hop) : 0u;
+    d.tf = mel_tile_frames(d.n_fft, d.hop);
+    d.tiles = (d.frames + d.tf - 1) / d.tf;
+    d.const_len = const_len_of(c, s.slot, true);
+    d.const_off = const_off_of(c, s.slot, true);
+  }
+  hipStream_t st, cs;
+  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
+  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
+  // (a row list over an empty result: no record to read, every row is skipped)
+  if (d_skipped)
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_skipped), c->res.req.n ? 0 : (int)m, n_specs, st));
+  // Per tile size, the blk0 table of its launch (as tfrg_result_raw_resize's per kernel): a workgroup per
+  // work item within an even share of 2 per CU -- what the LDS of a tile lets a CU hold -- striding over the rest.
+  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 2u / n_specs);
+  for (const uint32_t tf : {64u, 32u, 16u}) {
+    uint32_t blocks = 0, lds_words = 0;
+    for (uint32_t i = 0; i < n_specs; ++i) {
+      MelSpec& d = a.sp[i];
+      d.blk0 = blocks;
+      d.nblk = d.tf == tf ? (uint32_t)std::min<uint64_t>(cap, (uint64_t)m * d.tiles) : 0u;
+      blocks += d.nblk;
+      if (d.tf == tf) lds_words = std::max(lds_words, mel_lds_words(d.n_fft, d.hop, tf));
+    }
+    if (m && c->res.req.n) HIP_TRY(launch_mel(a, tf, blocks, lds_words * 4u, st));
   }
   return fence_close(c, st, cs);
 }

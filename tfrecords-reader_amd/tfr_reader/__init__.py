@@ -7,6 +7,7 @@ spreads the readers' files over several GPUs.
 
 from tfr_reader.example import Feature, set_decoder_type
 from tfr_reader.ids import ElementIds, Vocabulary
+from tfr_reader.mel import Mel, MelBank
 from tfr_reader.ragged import Ragged, RaggedBatch
 from tfr_reader.raw import Raw, Resize
 from tfr_reader.reader import (
@@ -23,6 +24,8 @@ from tfr_reader.wordpiece import WordPieceIds, WordPieceVocab
 __all__ = [
     "ElementIds",
     "Feature",
+    "Mel",
+    "MelBank",
     "Ragged",
     "RaggedBatch",
     "Raw",

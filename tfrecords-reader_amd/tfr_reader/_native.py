@@ -182,6 +182,37 @@ RESIZE_BAND = 16  # (csrc/tfrg_resize.h: the output rows of one work item)
 RESIZE_AA_BAND, RESIZE_AA_GROUP = 8, 4
 
 
+class TfrgMelSpec(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("src", C.c_uint32),
+        ("out", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("channel", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("frames", C.c_uint32),
+        ("hop", C.c_uint32),
+        ("center", C.c_uint32),
+        ("power", C.c_uint32),
+        ("log", C.c_uint32),
+        ("fill", C.c_uint32),
+        ("floor", C.c_float),
+        ("scale", C.c_float),
+        ("bias", C.c_float),
+        ("reserved", C.c_uint32),
+        ("mel", C.c_void_p),
+        ("out_ptr", C.c_void_p),
+        ("lengths", C.c_void_p),
+    ]
+
+
+MEL_LINEAR, MEL_LN, MEL_LOG10 = range(3)  # tfrg_mel_spec.log (TFRG_MEL_*)
+MEL_MAX_FFT = 2048
+MEL_MAX_MELS = 128
+MEL_MAX_SAMPLES = 1 << 24
+MEL_MAX_FRAMES = 1 << 20
+
+
 class TfrgRaggedSpec(C.Structure):
     _fields_ = [
         ("slot", C.c_uint32),
@@ -418,6 +449,12 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_result_raw_resize": (C.c_int, [C.c_void_p, C.POINTER(TfrgResizeSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "tfrg_mel_create": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "tfrg_mel_destroy": (C.c_int, [C.c_void_p]),
+    "tfrg_mel_info": (C.c_int, [C.c_void_p, u32p, u32p, u32p, u64p]),
+    "tfrg_mel_tile_frames": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "tfrg_result_mel": (C.c_int, [C.c_void_p, C.POINTER(TfrgMelSpec), C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_result_ragged_rows": (C.c_int, [C.c_void_p, C.POINTER(TfrgRaggedSpec), C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tfrg_ctx_set_ragged_tile": (C.c_int, [C.c_void_p, C.c_uint32]),

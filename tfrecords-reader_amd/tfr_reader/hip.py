@@ -578,6 +578,15 @@ class HipDecoder:
 
         return W.decoder_raw(self, specs, rows=rows, out=out, stream=stream, strict=strict)
 
+    def mel(self, specs, rows=None, out=None, stream: int | None = None, strict: bool = False):
+        """Log-mel spectrograms of PCM stored as bytes -- a windowed STFT, ``|X| ** power``, a mel filterbank, a
+        log, scale and bias, ``[m, n_mels, frames]`` -- as torch tensors on this decoder's device, one per
+        ``tfr_reader.mel.Mel`` spec, for every record or for the list ``rows`` (tfrg_result_mel: both
+        contractions on the MFMA units); see ``tfr_reader.mel.decoder_mel``."""
+        from tfr_reader import mel as M  # noqa: PLC0415, N812
+
+        return M.decoder_mel(self, specs, rows=rows, out=out, stream=stream, strict=strict)
+
     def resize(self, specs, rows=None, boxes=None, flip=None, out=None, stream: int | None = None, strict: bool = False):
         """Raw images whose height and width are int64 features of their record, cropped (``boxes``: an
         int32 ``[m, 4]`` device tensor of top, left, height, width per output row), mirrored (``flip``: a
@@ -931,6 +940,14 @@ class BatchResult:
         from tfr_reader import raw as W  # noqa: PLC0415
 
         return W.batch_raw(self, specs, rows)
+
+    def mel(self, specs, rows=None):
+        """The outputs of ``tfr_reader.mel.Mel`` specs as numpy arrays from the fetched columns (the host
+        counterpart of ``HipDecoder.mel``: the definition in float64 with ``np.fft.rfft``, rounded once): a
+        ``DenseBatch`` with ``.lengths`` and ``.stats``; bfloat16 outputs as their uint16 bits."""
+        from tfr_reader import mel as M  # noqa: PLC0415, N812
+
+        return M.batch_mel(self, specs, rows)
 
     def resize(self, specs, rows=None, boxes=None, flip=None):
         """The outputs of ``tfr_reader.raw.Resize`` specs as numpy arrays from the fetched columns (the host

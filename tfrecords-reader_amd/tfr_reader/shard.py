@@ -393,6 +393,13 @@ class ShardDecoder:
 
         return W.shard_raw(self, plan, specs, rows=rows, out=out, stream=stream, strict=strict)
 
+    def mel(self, plan: np.ndarray, specs, rows=None, out=None, stream: int | None = None, strict: bool = False):
+        """The last ``decode_device`` / ``decode_device32`` as log-mel spectrograms over the whole plan
+        (``tfr_reader.mel.Mel`` specs), as ``raw``; see ``tfr_reader.mel.shard_mel``."""
+        from tfr_reader import mel as M  # noqa: PLC0415, N812
+
+        return M.shard_mel(self, plan, specs, rows=rows, out=out, stream=stream, strict=strict)
+
     def resize(self, plan: np.ndarray, specs, rows=None, boxes=None, flip=None, out=None, stream: int | None = None,
                strict: bool = False):
         """The last ``decode_device`` / ``decode_device32`` as resized-image outputs over the whole plan
