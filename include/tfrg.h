@@ -312,7 +312,27 @@ typedef struct tfrg_info {
    * place and unchanged, until the next decode on the context -- exactly as d_bytes must stay for
    * the bytes views and for the confirmation of the decode. */
   uint64_t implicit_off_slots;
+  /* bytes per value of the int64 column as the last decode stored it: 8, or 4 / 2 for a narrowed
+   * decode. An optimistic decode (tfrg_result_info) whose learned record shapes hold every int64 slot
+   * as one varint of at most 4 / 2 bytes -- every value below 2^28 / 2^14 -- stores the column in a
+   * separate buffer in elements of that width, element i at byte i * width with the int64 column's
+   * own index i (slot_base + row). The column stays int64 wherever it is looked at:
+   * tfrg_result_device and tfrg_result_fetch write the int64 column out from the narrow one first
+   * (one small kernel on the decode's stream, once per decode); tfrg_result_dense / _dense_rows /
+   * _ragged_rows / _select_rows / _raw_resize read the narrow column as it is and write nothing;
+   * tfrg_result_i64_narrow hands it to a device consumer. Any other decode -- not optimistic, re-run
+   * after a miss, without record shapes, from host memory, or with env TFRG_NARROW_I64=0 at context
+   * creation -- stores 8-byte values (8). */
+  uint32_t i64_width;
 } tfrg_info;
+
+/* The int64 column of the last decode as it was stored, for a device consumer: *d_values is the
+ * narrow column and *width 4 or 2 after a narrowed decode (tfrg_info.i64_width), else the int64
+ * column and 8. Element i, the int64 column's own index (slot_base + row), is the unsigned integer
+ * of *width bytes at byte i * *width. No widening pass, and no host synchronisation beyond the
+ * confirmation of an optimistic decode. The column lives as long as the other result columns: until
+ * the next decode on the context. */
+int tfrg_result_i64_narrow(tfrg_ctx* ctx, const void** d_values, uint32_t* width);
 
 /* The end-relative element offset of bytes slot `slot` in the context's learned record shapes
  * (tfrg_info.implicit_off_slots): *delta such that the slot's element of a record ending at e lies at

@@ -99,6 +99,7 @@ struct DecodeReq {
   uint64_t bound = 0;       // no record above this; 0: the context's record_bound
   bool full = false;        // no optimistic pass
   bool worst_case = false;  // the value-capacity hints ignored
+  bool host = false;        // tfrg_decode_host: its reader is tfrg_result_fetch, the int64 column stays 8 bytes wide
 };
 
 // Everything known about the last decode. Replaced as a whole: decode_device_any and tfrg_set_schema
@@ -114,6 +115,8 @@ struct Result {
   bool rs_complete = false;   // the placed slots' identity rows are written into the device columns
   bool cols_complete = false; // tfrg_result_device wrote the constant columns (constant_fills)
   bool off_complete = false;  // fill_implicit_off wrote the implicit bytes_off words
+  bool i64_complete = false;  // widen_i64 wrote the int64 column from the narrow one
+  uint32_t i64_w = 8;         // bytes per int64 value it stored: 4 or 2 into i64n (i64_width), else 8 into i64
   uint32_t implicit = 0;      // TFRG_IMPLICIT_* columns the decode did not store
   uint64_t off_mask = 0;      // slots whose bytes_off words it did not store (implicit_off_slots)
   bool aux_zero = false;      // ran optimistically with stored statuses: aux is all 0
@@ -135,6 +138,7 @@ struct Arena {
   // columns and work space of a decode
   DBuf status, aux, verdict, order, count, loc, rs, slot_base, totals, kind_totals;
   DBuf ident;  // 0, 1, 2, ... (ident_n words): the fetched row splits of placed slots
+  DBuf i64n;  // the int64 column of a narrowed decode: element i at byte i * width (tfrg_info.i64_width)
   DBuf i64, f32, b_off, b_len, big_list, slow_list, miss, info, tsum, crc_rec, crc_base, crc_part;
   DBuf dq, dq_cnt;  // deferred packed-int64 bodies (k_body_count)
   DBuf lmask, rlist;  // k_tpl_lane's per-group miss masks and listed groups
@@ -151,7 +155,7 @@ struct Arena {
   void each(F f) {
     DBuf* const all[] = {&crc_tab, &consts, &ht, &key_hash, &key_off, &key_blob, &key_slot, &slot_kind, &key_w, &krec,
                          &in_bytes, &in_start, &in_end, &status, &aux, &verdict, &order, &count, &loc, &rs, &slot_base,
-                         &totals, &kind_totals, &ident, &i64, &f32, &b_off, &b_len, &big_list, &slow_list, &miss, &info,
+                         &totals, &kind_totals, &ident, &i64n, &i64, &f32, &b_off, &b_len, &big_list, &slow_list, &miss, &info,
                          &tsum, &crc_rec, &crc_base, &crc_part, &dq, &dq_cnt, &lmask, &rlist, &bdata, &boff64, &blb,
                          &bbig, &tpl, &spec, &fr_tab, &fr_dev, &rg_tsum, &el_tsum,
                          &id_tsum, &tk_tsum, &wp_tsum, &sel_buf};
@@ -168,6 +172,7 @@ struct Switches {
   uint32_t tpl_gpw = 0;      // TFRG_TPL_GPW=2, 4 or 8: its groups per wave; 0: launch_tpl_lane's choice
   bool optimistic = true;    // TFRG_OPTIMISTIC=0: no optimistic decodes
   bool implicit_off = true;  // TFRG_IMPLICIT_OFF=0: every bytes_off word stored
+  bool narrow_i64 = true;    // TFRG_NARROW_I64=0: every int64 value stored as 8 bytes
   bool walk_beside = true;   // TFRG_WALK_BESIDE=0: large records walked before the CRC
   uint32_t walk_blocks = 0;  // TFRG_WALK_BLOCKS: cap on its walking workgroups; 0 = automatic
   int dense_nt = 0;          // TFRG_DENSE_NT=1: k_dense's output stores nontemporal
@@ -222,6 +227,7 @@ struct tfrg_ctx : Arena {
   std::vector<uint32_t> const_len;  // per slot: that length
   uint64_t off_rel = 0;       // bytes slots at one end-relative offset in every shape
   std::vector<int32_t> rel_off;  // per slot: that offset
+  uint32_t i64_width = 8;     // bytes that hold every int64 value the shapes place (Learned::i64_width)
   // optional per-stage HIP events (tfrg_ctx_set_profiling)
   bool profiling = false;
   bool have_events = false;
@@ -257,6 +263,7 @@ int tfrg_ctx_create(int device, tfrg_ctx** out) {
   s.spec_on = num("TFRG_SPEC", 1) != 0;
   s.optimistic = num("TFRG_OPTIMISTIC", 1) != 0;
   s.implicit_off = num("TFRG_IMPLICIT_OFF", 1) != 0;
+  s.narrow_i64 = num("TFRG_NARROW_I64", 1) != 0;
   s.walk_beside = num("TFRG_WALK_BESIDE", 1) != 0;
   s.tpl_stage = num("TFRG_TPL_STAGE", 1);
   const int gpw = num("TFRG_TPL_GPW", 0);
@@ -615,6 +622,7 @@ int tfrg_set_schema(tfrg_ctx* c, uint32_t n_keys, const uint8_t* key_blob, const
   c->n_tpl = 0;  // slots may have moved: learn again from the next host batch
   c->off_rel = 0;
   c->rel_off.clear();
+  c->i64_width = 8;
   c->tpl_learned = false;
   c->have_spec = false;
   return 0;
@@ -657,6 +665,7 @@ extern "C" int tfrg_learn_templates(tfrg_ctx* c, const uint8_t* h_bytes, uint64_
   c->have_spec = false;
   c->off_rel = 0;  // (no shape, no end-relative slot: tfrg_ctx_rel_off answers from the kept shapes only)
   c->rel_off.clear();
+  c->i64_width = 8;  // (no shape, no bound)
   if (!c->n_keys) return 0;
   const TplSchema sch{c->key_id, c->key_slot_h, c->slot_kind_h};
   Learned L;
@@ -691,6 +700,7 @@ extern "C" int tfrg_learn_templates(tfrg_ctx* c, const uint8_t* h_bytes, uint64_
     c->const_len = L.const_len;
     c->off_rel = L.off_rel;
     c->rel_off = L.rel_off;
+    c->i64_width = L.i64_width;
   }
   if (L.have_spec) HIP_TRY(hipMemcpy(c->spec.p, L.spec.data(), spec_bytes, hipMemcpyHostToDevice));
   c->spec_h = L.spec;
@@ -772,6 +782,14 @@ static int ensure_group(tfrg_ctx* c, const char* group, std::initializer_list<st
       return TFRG_E_NOMEM;
     }
   return 0;
+}
+
+// LaunchCfg::i64n_alloc: the context's narrow int64 column, grown (after the work that may still use the
+// old one) only when a decode that narrows needs more
+static void* alloc_i64n(void* owner, uint64_t bytes) {
+  tfrg_ctx* c = static_cast<tfrg_ctx*>(owner);
+  if (c->i64n.cap >= bytes && c->i64n.p) return c->i64n.p;
+  return ensure_group(c, " (narrow int64 column)", {{&c->i64n, bytes}}) ? nullptr : c->i64n.p;
 }
 
 static int decode_device_any(tfrg_ctx* c, const DecodeReq& req) {
@@ -939,6 +957,13 @@ static int decode_device_any(tfrg_ctx* c, const DecodeReq& req) {
   cfg.implicit = 0;
   cfg.off_rel = c->sw.implicit_off ? c->off_rel : 0ull;  // (launch_decode: u32 offsets, no byte gather)
   cfg.implicit_off = 0;
+  // (the narrow int64 column: launch_decode decides whether the decode narrows and asks for the column
+  // then. Never a host decode: what reads it is tfrg_result_fetch, which would pay the widening pass)
+  cfg.i64_width = c->sw.narrow_i64 && !q.host ? c->i64_width : 8u;
+  cfg.i64n_alloc = alloc_i64n;
+  cfg.i64n_owner = c;
+  cfg.i64n = nullptr;
+  cfg.narrow = 8;
   // deferred packed bodies when records above lane_max may be walked from HBM: one 64-row block
   // (2,048 entries of 16 bytes) per 256 KiB of input, at least 16
   o.dq = nullptr;
@@ -990,6 +1015,7 @@ static int decode_device_any(tfrg_ctx* c, const DecodeReq& req) {
   r.mat_pending = r.opt_pending && mat && S;
   r.implicit = n != 0 ? cfg.implicit : 0u;
   r.off_mask = n != 0 ? cfg.implicit_off : 0ull;
+  r.i64_w = n != 0 ? cfg.narrow : 8u;
   // (k_tpl_lane stored status and verdict per record and no aux: every record of a confirmed decode is OK)
   r.aux_zero = r.opt_pending && !cfg.ran_quiet_big && !(cfg.implicit & TFRG_IMPLICIT_STATUS);
   for (uint32_t k = 0; (r.implicit || r.off_mask) && k < S && k < kLeanMaxSlots; ++k) {
@@ -1036,6 +1062,7 @@ int tfrg_decode_host(tfrg_ctx* c, const uint8_t* h_bytes, uint64_t nbytes, const
   q.off.e64 = c->in_end.as<uint64_t>();
   q.cap_in = total;
   q.bound = widest ? widest : 1;
+  q.host = true;
   return decode_device_any(c, q);
 }
 
@@ -1124,6 +1151,7 @@ int tfrg_result_info(tfrg_ctx* c, tfrg_info* info) {
   info->placed_slots = ((uint64_t)h[kInfoPlacedHi] << 32) | h[kInfoPlacedLo];
   info->implicit_cols = r.implicit;
   info->implicit_off_slots = r.off_mask;
+  info->i64_width = r.i64_w;
   return overflow_status(h);
 }
 
@@ -1191,6 +1219,33 @@ static int fill_implicit_off(tfrg_ctx* c) {
   return 0;
 }
 
+// The int64 column of a narrowed decode (tfrg_info.i64_width 4 or 2) written out from the narrow one,
+// once per decode, on the decode's stream: tfrg_result_device hands out a true int64 column and
+// tfrg_result_fetch copies one. Every int64 slot of such a decode is placed, slot rows n * its rank
+// among the int64 slots: the values it stored are the column's first min(n * slots, capacity)
+// elements. Only after the decode is confirmed (a re-run stores 8-byte words: i64_w 8). The row-list
+// consumers read the narrow column as it is (fill_columns) and do not come here.
+static int widen_i64(tfrg_ctx* c) {
+  Result& r = c->res;
+  if (r.i64_w >= 8u || r.i64_complete || !r.req.n) return 0;
+  uint64_t slots = 0;
+  for (uint32_t k = 0; k < c->n_slots; ++k) slots += (c->slot_kind_h[k] & 3u) == TFRG_KIND_INT64;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(launch_widen_i64(c->i64.as<int64_t>(), c->i64n.p, r.i64_w, std::min<uint64_t>(slots * r.req.n, r.cap_i64),
+                           c->last_stream));
+  r.i64_complete = true;
+  return 0;
+}
+
+int tfrg_result_i64_narrow(tfrg_ctx* c, const void** d_values, uint32_t* width) {
+  if (!c || !c->res.valid || !d_values || !width) return TFRG_E_ARG;
+  if (const int rc = confirm_pending(c)) return rc;
+  const Result& r = c->res;
+  *width = r.i64_w;
+  *d_values = r.i64_w < 8u ? c->i64n.p : c->i64.p;
+  return 0;
+}
+
 int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
   if (!c || !c->res.valid) return TFRG_E_ARG;
   if (const int rc = confirm_pending(c)) return rc;  // (before the view, as tfrg_result_info does)
@@ -1221,6 +1276,7 @@ int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
   }
   r.cols_complete = true;
   if (const int rc = fill_implicit_off(c)) return rc;
+  if (const int rc = widen_i64(c)) return rc;
   d->status = c->status.as<int32_t>();
   d->aux = c->aux.as<int64_t>();
   d->verdict = c->verdict.as<uint8_t>();
@@ -1285,12 +1341,26 @@ template <class T>
 static const T* view_col(const tfrg_ctx* c, const DBuf& b) {
   return static_cast<const T*>(b.p ? b.p : c->slot_base.p);
 }
+// The width of the int64 column, for the argument structs that have the word (the passes that read
+// int64 values: dense, ragged, select, resize); false for the others
+template <class Args>
+static auto set_i64_w(Args& a, uint32_t w, int) -> decltype((void)(a.i64_w = w), true) {
+  a.i64_w = w;
+  return true;
+}
+template <class Args>
+static bool set_i64_w(Args&, uint32_t, long) {
+  return false;
+}
 // The column view of the last result: what DenseArgs, RaggedArgs and SelectArgs have in common
 template <class Args>
 static void fill_columns(const tfrg_ctx* c, Args& a) {
   a.rs = c->rs.as<uint32_t>();
   a.slot_base = c->slot_base.as<uint64_t>();
-  a.i64 = view_col<int64_t>(c, c->i64);
+  // (a narrowed decode: the narrow column as it is for the passes that read int64 values, through
+  // col_i64 -- no widening pass; the others read neither column)
+  const bool narrow = set_i64_w(a, c->res.i64_w, 0) && c->res.i64_w < 8u;
+  a.i64 = view_col<int64_t>(c, narrow ? c->i64n : c->i64);
   a.f32 = view_col<uint32_t>(c, c->f32);
   a.b_len = view_col<uint32_t>(c, c->b_len);
   if (c->res.materialized) a.b_off64 = view_col<uint64_t>(c, c->boff64);
@@ -2517,6 +2587,9 @@ int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {
     }
   }
   HIP_TRY(cp(h->slot_base, c->slot_base.p, S * 8));
+  // (a narrowed decode: the int64 column written out from the narrow one first, as the device view does)
+  if (h->i64)
+    if (const int rc2 = widen_i64(c)) return rc2;
   HIP_TRY(cp(h->i64, c->i64.p, cl(info.kind_totals[TFRG_KIND_INT64], r.cap_i64) * 8));
   HIP_TRY(cp(h->f32, c->f32.p, cl(info.kind_totals[TFRG_KIND_FLOAT], r.cap_f32) * 4));
   // (implicit offset words: written into the device column first, by the device view's fill)

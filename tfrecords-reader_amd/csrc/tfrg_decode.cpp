@@ -64,7 +64,11 @@ static LeanArgs lean_args(const DevBatch& b, const DevSchema& sc, const DevOut& 
     const uint64_t cap = kind == TFRG_KIND_INT64 ? o.cap_i64 : kind == TFRG_KIND_FLOAT ? o.cap_f32 : o.cap_b;
     t.lim = cap > base ? (uint32_t)std::min<uint64_t>(cap - base, n) : 0u;
     t.kind = kind;
-    if (kind == TFRG_KIND_INT64) t.v1 = o.i64 + base;
+    t.vw = 8u;
+    if (kind == TFRG_KIND_INT64 && cfg.narrow < 8u) {  // (the same index in the narrow column)
+      t.v1 = static_cast<uint8_t*>(cfg.i64n) + base * cfg.narrow;
+      t.vw = cfg.narrow;
+    } else if (kind == TFRG_KIND_INT64) t.v1 = o.i64 + base;
     else if (kind == TFRG_KIND_FLOAT) t.v1 = o.f32 + base;
     else t.v1 = o.b_off + base;
     t.v2 = o.b_len + base;
@@ -133,6 +137,23 @@ hipError_t launch_decode(const DevBatch& b, const DevSchema& sc, const DevOut& o
   // u32 ends are on the device to recompute them from: tfrg_info.implicit_off_slots. Every slot of
   // such a decode is placed, so the slot's column rows are n * its rank among the bytes slots)
   cfg.implicit_off = lean && quiet_tpl && b.omode != kOffU64 && !(b.flags & kFlagMaterializeBytes) ? cfg.off_rel : 0ull;
+  // (and the int64 column in elements of 2 or 4 bytes, when every int64 value the shapes place fits
+  // them, Learned::i64_width: the same gate -- every slot placed, k_tpl_lane the column's only writer --
+  // whatever the offsets and the byte gather are. tfrg_info.i64_width)
+  // Every int64 slot is placed, rows n * rank: the column's stored elements are its first
+  // min(n * int64 slots, capacity), and the narrow column is asked for at that size, by this decode only.
+  cfg.narrow = 8u;
+  cfg.i64n = nullptr;
+  if (lean && quiet_tpl && cfg.i64n_alloc && (cfg.i64_width == 2u || cfg.i64_width == 4u)) {
+    uint64_t slots = 0;
+    for (uint32_t k = 0; k < S; ++k) slots += (cfg.spec_h[k] & 3u) == TFRG_KIND_INT64;
+    const uint64_t elems = std::min<uint64_t>(o.cap_i64, slots * b.n);
+    if (elems) {
+      cfg.i64n = cfg.i64n_alloc(cfg.i64n_owner, elems * cfg.i64_width);
+      if (!cfg.i64n) return hipErrorOutOfMemory;
+      cfg.narrow = cfg.i64_width;
+    }
+  }
   DevOut ox = o;
   if (!lean) {
     ox.lmask = nullptr;

@@ -119,7 +119,7 @@ __device__ __forceinline__ typename ValT<DT>::type value_at(const Sp& x, uint64_
   using T = typename ValT<DT>::type;
   const bool ok = j < c;
   const uint64_t i = ok ? e + j : 0ull;
-  const T v = DT == kDenseF32 ? (T)x.a->f32[i] : (T)(uint64_t)x.a->i64[i];
+  const T v = DT == kDenseF32 ? (T)x.a->f32[i] : (T)col_i64(x.a, i);
   return ok ? v : (T)x.s->fill;
 }
 

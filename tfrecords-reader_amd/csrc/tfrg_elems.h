@@ -60,7 +60,8 @@ struct ElemsArgs {
   uint32_t tiles;             // ceil(m / tile) >= 1
   uint32_t split;             // S: copying workgroups per tile; 0: no spec has bytes to store
   // (fill_columns' common view: the numeric columns are not read here)
-  const int64_t* i64;
+  const int64_t* i64;   // (not read)
+  uint32_t i64_w;       // (fill_columns sets it beside i64)
   const uint32_t* f32;
   ElemsSpec sp[kElemsMaxSpecs];
 };

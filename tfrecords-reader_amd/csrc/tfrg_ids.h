@@ -63,7 +63,8 @@ struct IdsArgs {
   uint32_t tiles;             // ceil(m / tile) >= 1
   uint32_t pad;
   // (fill_columns' common view: the numeric columns are not read here)
-  const int64_t* i64;
+  const int64_t* i64;   // (not read)
+  uint32_t i64_w;       // (fill_columns sets it beside i64)
   const uint32_t* f32;
   IdsSpec sp[kIdsMaxSpecs];
 };

@@ -51,7 +51,8 @@ struct LeanTgt {
   uint32_t kind;   // speculative placement kind (0: the slot is not placed speculatively)
   uint32_t no_off; // bytes slot whose offset words this decode leaves implicit (LaunchCfg::implicit_off):
                    // v1 is not stored
-  uint32_t pad;
+  uint32_t vw;     // int64 slot: bytes per stored value, 8, or 4 / 2 where the decode narrows the column
+                   // (LaunchCfg::narrow): v1 is then the narrow column, element r at byte r * vw
 };
 struct LeanArgs {
   uint32_t n_tpl;
@@ -296,6 +297,16 @@ struct LaunchCfg {
                            // 0: TFRG_IMPLICIT_OFF=0, or a decode whose byte gather reads the column)
   uint64_t implicit_off;   // (out) the slots of off_rel whose bytes_off words the decode did not store: a
                            // lean optimistic decode with u32 offsets (element r is end32[r] + rel_off)
+  uint32_t i64_width;      // bytes that hold every int64 value the learned shapes place (Learned::i64_width;
+                           // 8: no bound, or TFRG_NARROW_I64=0)
+  // the narrow int64 column of at least `bytes` bytes, asked for only by a decode that narrows (null
+  // return: the allocation failed, and so does the decode; null function: this decode cannot narrow)
+  void* (*i64n_alloc)(void* owner, uint64_t bytes);
+  void* i64n_owner;
+  void* i64n;              // (out) that column: element i at byte i * narrow, i the int64 column's own index
+  uint32_t narrow;         // (out) bytes per int64 value the decode stored: i64_width into i64n for a lean
+                           // optimistic decode with shapes (k_tpl_lane the column's only writer), else 8 into
+                           // DevOut::i64
 };
 
 // Kernel stages, in launch order (profiling events bracket each one).
@@ -327,6 +338,9 @@ void launch_tail_gather(const DevBatch& b, const DevSchema& sc, const DevOut& o,
 hipError_t launch_fill_placed_rows(uint32_t* rs, const uint32_t* info, uint32_t n_slots, uint32_t n, hipStream_t st);
 // off[r] = end32[r] + delta for r < n: an implicit bytes_off run written out (tfrg_info.implicit_off_slots)
 hipError_t launch_fill_rel_off(uint32_t* off, const uint32_t* end32, uint32_t delta, uint32_t n, hipStream_t st);
+// i64[i] = narrow[i] for i < count, narrow in elements of `width` (4 or 2) bytes: the int64 view of a
+// narrowed decode written out (tfrg_info.i64_width)
+hipError_t launch_widen_i64(int64_t* i64, const void* narrow, uint32_t width, uint64_t count, hipStream_t st);
 hipError_t launch_stream_read(const void* d, uint64_t nbytes, uint32_t* sink, hipStream_t st, int variant);
 // tfrg_frame.hip: every phase of the chunked framing index (tfrg_frame.h) enqueued on st
 struct FrTab;

@@ -406,6 +406,23 @@ uint32_t learn_shapes(const TplSchema* c, uint32_t S, const uint8_t* h_bytes, ui
     out.off_rel |= 1ull << s2;
     out.rel_off[s2] = (int32_t)p0;
   }
+  // the width of the int64 column: every int64 slot one inline varint in every kept shape, and the
+  // longest of them (7 value bits per varint byte: <= 2 bytes is below 2^14, <= 4 below 2^28)
+  out.i64_width = 8;
+  {
+    uint32_t longest = 0;
+    bool any = false, all = S <= kLeanMaxSlots;
+    for (uint32_t s2 = 0; all && s2 < S; ++s2) {
+      if ((c->slot_kind[s2] & 3u) != TFRG_KIND_INT64) continue;
+      any = true;
+      for (uint32_t k = 0; all && k < nt; ++k) {
+        const uint32_t zk = w[(size_t)k * kLtWords + kLtSlot + 3 * s2];
+        all = (zk & 0xffu) == 1u && (zk >> 16) != 0;
+        longest = std::max(longest, (zk >> 8) & 0xffu);
+      }
+    }
+    if (any && all && longest >= 1u && longest <= 4u) out.i64_width = longest <= 2u ? 2u : 4u;
+  }
   out.w = std::move(w);
   out.spec = std::move(spec);
   out.img = std::move(img);

@@ -38,6 +38,11 @@ struct Learned {
   // decode with u32 offsets leaves such a slot's bytes_off words implicit (tfrg_info.implicit_off_slots)
   uint64_t off_rel = 0;
   std::vector<int32_t> rel_off;
+  // bytes that hold every value the kept templates place in the int64 column: 2 when every int64 slot
+  // is one inline varint (mode 1, present) of <= 2 bytes in every kept template (the value is below
+  // 2^14), 4 when of <= 4 bytes (below 2^28), 8 otherwise or without an int64 slot. One width for the
+  // whole column. An optimistic decode stores the column in elements of that width (tfrg_info.i64_width)
+  uint32_t i64_width = 8;
 };
 
 // Returns the template count (0: none).

@@ -37,7 +37,8 @@ struct RaggedSpec {
 struct RaggedArgs {
   const uint32_t* rs;         // [n_slots][n + 1] row splits (rows of placed slots are not read)
   const uint64_t* slot_base;  // [n_slots]
-  const int64_t* i64;
+  const int64_t* i64;         // int64 values, or (i64_w 4 / 2) the narrow column of a narrowed decode: read by col_i64
+  uint32_t i64_w;             // bytes per element of i64: 8, 4 or 2 (tfrg_info.i64_width)
   const uint32_t* f32;
   const uint32_t* b_off;      // bytes views into `in` (null: materialized)
   const uint32_t* b_len;

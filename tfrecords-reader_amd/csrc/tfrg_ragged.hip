@@ -204,8 +204,8 @@ struct ValT<kDenseI64> {
 template <uint32_t DT>
 __device__ __forceinline__ typename ValT<DT>::type value_at(const Sp& x, uint32_t s, uint64_t j) {
   const uint64_t i = x.base + s + j;
-  if constexpr (DT == kDenseI64) return (uint64_t)x.a->i64[i];
-  else if constexpr (DT == kDenseI32) return reinterpret_cast<const uint32_t*>(x.a->i64)[2u * i];  // the low 32 bits
+  if constexpr (DT == kDenseI64) return col_i64(x.a, i);
+  else if constexpr (DT == kDenseI32) return col_i64_lo(x.a, i);  // the low 32 bits
   else return x.a->f32[i];
 }
 

@@ -59,6 +59,7 @@ struct RawArgs {
   const uint32_t* rs;
   const uint64_t* slot_base;
   const int64_t* i64;   // (not read)
+  uint32_t i64_w;       // (fill_columns sets it beside i64)
   const uint32_t* f32;  // (not read)
   const uint32_t* b_off;
   const uint32_t* b_len;

@@ -81,7 +81,8 @@ struct ResizeSpec {
 struct ResizeArgs {
   const uint32_t* rs;
   const uint64_t* slot_base;
-  const int64_t* i64;
+  const int64_t* i64;         // int64 values, or (i64_w 4 / 2) the narrow column of a narrowed decode: read by col_i64
+  uint32_t i64_w;             // bytes per element of i64: 8, 4 or 2 (tfrg_info.i64_width)
   const uint32_t* f32;  // (not read)
   const uint32_t* b_off;
   const uint32_t* b_len;

@@ -41,7 +41,7 @@ __device__ __forceinline__ bool extent(const Sp& x, uint32_t slot, uint32_t kons
     c = rfl32(rs[g + 1u]) - lo;
   }
   const uint64_t e = c ? x.a->slot_base[slot] + lo : 0ull;
-  *v = (int64_t)rfl64((uint64_t)x.a->i64[e]);
+  *v = (int64_t)rfl64(col_i64(x.a, e));
   return c != 0u;
 }
 

@@ -77,6 +77,24 @@ __device__ __forceinline__ const uint32_t* slot_splits(A a, uint32_t slot) {
   return (slot < 64u && ((placed >> slot) & 1ull)) ? nullptr : a->rs + (uint64_t)slot * ((uint64_t)a->n + 1u);
 }
 
+// Element i of the int64 column. A narrowed decode (tfrg_info.i64_width 4 or 2: every value a template
+// placed is below 2^28 or 2^14) stored it in elements of i64_w bytes at the same index, and a->i64 then
+// points at that narrow column (fill_columns): the one place its width is applied on the device.
+// (a uniform switch on a kernel-argument word)
+template <class A>
+__device__ __forceinline__ uint64_t col_i64(A a, uint64_t i) {
+  const uint32_t w = a->i64_w;
+  if (w == 2u) return reinterpret_cast<const uint16_t*>(a->i64)[i];
+  if (w == 4u) return reinterpret_cast<const uint32_t*>(a->i64)[i];
+  return (uint64_t)a->i64[i];
+}
+// its low 32 bits (an int32 output of a full-width column reads 4 bytes, not 8)
+template <class A>
+__device__ __forceinline__ uint32_t col_i64_lo(A a, uint64_t i) {
+  if (a->i64_w == 8u) return reinterpret_cast<const uint32_t*>(a->i64)[2u * i];
+  return (uint32_t)col_i64(a, i);
+}
+
 // the input of the bytes views as a buffer resource bounded to the batch: a load at or past in_bound
 // gives zeros without a memory access
 template <class A>

@@ -421,4 +421,38 @@ hipError_t launch_fill_rel_off(uint32_t* off, const uint32_t* end32, uint32_t de
   return hipGetLastError();
 }
 
+// The int64 column of a narrowed decode (tfrg_info.i64_width 4 or 2: k_tpl_lane stored every value in
+// the narrow column) written into the int64 column, for tfrg_result_device's view and
+// tfrg_result_fetch: element i of the one is element i of the other, zero-extended (no value a
+// template places is negative).
+// Two elements per thread and step: one 4- or 8-byte load and one 16-byte store, consecutive lanes at
+// consecutive addresses (a wave stores 1 KiB in one piece); both columns begin at an allocation, so
+// every such access is aligned. An odd last element goes to one thread.
+template <class T>
+__global__ __launch_bounds__(256) void k_widen_i64(int64_t* __restrict__ i64, const T* __restrict__ narrow, uint64_t count) {
+  typedef T tx2 __attribute__((ext_vector_type(2)));
+  typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+  const uint64_t n2 = count >> 1;
+  for (uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x; j < n2; j += (uint64_t)gridDim.x * 256u) {
+    const tx2 v = reinterpret_cast<const tx2*>(narrow)[j];
+    u64x2 w;
+    w.x = (uint64_t)v.x;
+    w.y = (uint64_t)v.y;
+    reinterpret_cast<u64x2*>(i64)[j] = w;
+  }
+  if ((count & 1u) && blockIdx.x == 0 && threadIdx.x == 0) i64[count - 1u] = (int64_t)(uint64_t)narrow[count - 1u];
+}
+
+hipError_t launch_widen_i64(int64_t* i64, const void* narrow, uint32_t width, uint64_t count, hipStream_t st) {
+  if (!count) return hipSuccess;
+  if (width != 2u && width != 4u) return hipErrorInvalidValue;
+  const uint64_t blocks = ((count >> 1) + 255u) / 256u;  // (at least one: the odd element)
+  const dim3 grid((uint32_t)(blocks < 8192u ? (blocks ? blocks : 1u) : 8192u));
+  if (width == 2u)
+    hipLaunchKernelGGL(k_widen_i64<uint16_t>, grid, dim3(256), 0, st, i64, static_cast<const uint16_t*>(narrow), count);
+  else
+    hipLaunchKernelGGL(k_widen_i64<uint32_t>, grid, dim3(256), 0, st, i64, static_cast<const uint32_t*>(narrow), count);
+  return hipGetLastError();
+}
+
 }  // namespace tfrg

@@ -71,7 +71,7 @@ __device__ __forceinline__ bool value_term(KArgs a, KTerm t, uint64_t i) {
     if (sel_float_nan(u) || t->rhs_nan) return t->op == kSelNe;
     return sel_cmp(sel_float_key(u), t->rhs, t->op);
   }
-  return sel_cmp(a->i64[i], t->rhs, t->op);
+  return sel_cmp((int64_t)col_i64(a, i), t->rhs, t->op);
 }
 
 // term t for record g (ok: g is a record; else everything indexed by g is taken from record 0 and dropped)

@@ -71,7 +71,8 @@ struct TokArgs {
   uint32_t tiles;             // ceil(m / tile) >= 1
   uint32_t split;             // kTokSplitMin .. kTokSplitMax
   // (fill_columns' common view: the numeric columns are not read here)
-  const int64_t* i64;
+  const int64_t* i64;   // (not read)
+  uint32_t i64_w;       // (fill_columns sets it beside i64)
   const uint32_t* f32;
   TokSpec sp[kTokMaxSpecs];
 };

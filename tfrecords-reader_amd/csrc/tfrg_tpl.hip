@@ -414,7 +414,11 @@ __global__ __launch_bounds__(kTplBlock, W == 16 ? 6 : (W == 32 ? 4 : 2)) void k_
             if (r < T.lim) {
               constexpr bool kNt = ST && TFRG_TPL_STORE_NT;
               if (T.kind == TFRG_KIND_INT64) {
-                st_nt<kNt>(reinterpret_cast<uint64_t*>(T.v1) + r, (uint64_t)lx);
+                // (uniform; vw 2 / 4: a narrowed decode, the value is below 2^14 / 2^28 in every shape and
+                // v1 the narrow column -- tfrg_info.i64_width)
+                if (T.vw == 2u) st_nt<kNt>(reinterpret_cast<uint16_t*>(T.v1) + r, (uint16_t)lx);
+                else if (T.vw == 4u) st_nt<kNt>(reinterpret_cast<uint32_t*>(T.v1) + r, lx);
+                else st_nt<kNt>(reinterpret_cast<uint64_t*>(T.v1) + r, (uint64_t)lx);
               } else {
                 // (uniform; no_off: the element's offset en + pos is the caller's u32 end plus a constant
                 // of the shapes, left implicit -- tfrg_info.implicit_off_slots)

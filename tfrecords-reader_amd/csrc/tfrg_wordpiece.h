@@ -89,7 +89,8 @@ struct WpArgs {
   uint32_t tile;
   uint32_t tiles;
   uint32_t split;  // kTokSplitMin .. kTokSplitMax (tfrg_ctx_set_token_split)
-  const int64_t* i64;
+  const int64_t* i64;   // (not read)
+  uint32_t i64_w;       // (fill_columns sets it beside i64)
   const uint32_t* f32;
   WpSpec sp[kWpMaxSpecs];
 };

@@ -43,6 +43,7 @@ class TfrgInfo(C.Structure):
         ("implicit_cols", C.c_uint32),
         ("placed_slots", C.c_uint64),
         ("implicit_off_slots", C.c_uint64),
+        ("i64_width", C.c_uint32),
     ]
 
 
@@ -439,6 +440,7 @@ SIGNATURES: dict[str, tuple] = {
     "tfrg_stream_set_device_index": (C.c_int, [C.c_void_p, C.c_int]),
     "tfrg_result_info": (C.c_int, [C.c_void_p, C.POINTER(TfrgInfo)]),
     "tfrg_ctx_rel_off": (C.c_int, [C.c_void_p, C.c_uint32, i32p]),
+    "tfrg_result_i64_narrow": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u32p]),
     "tfrg_result_device": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),
     "tfrg_result_fetch": (C.c_int, [C.c_void_p, C.POINTER(TfrgColumns)]),
     "tfrg_result_dense": (C.c_int, [C.c_void_p, C.POINTER(TfrgDenseSpec), C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -489,6 +491,10 @@ FLAG_STRICT_CRC = 8
 FLAG_MATERIALIZE_BYTES = 16
 
 
+# entry points that libraries built from earlier revisions (tools/build_rev.sh) do not export
+_SINCE = {"tfrg_result_i64_narrow"}
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -504,6 +510,10 @@ def lib() -> C.CDLL:
             )
         lib_ = C.CDLL(str(_LIB_PATH))
         for name, (res, args) in SIGNATURES.items():
+            # (a measurement library of an earlier revision, TFRG_LIB: the entry point is not there to
+            # bind, and a call of it raises AttributeError)
+            if name in _SINCE and not hasattr(lib_, name):
+                continue
             fn = getattr(lib_, name)
             fn.restype = res
             fn.argtypes = args

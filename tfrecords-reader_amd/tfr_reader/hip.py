@@ -261,10 +261,20 @@ class HipDecoder:
         """Device pointers of the last result (tfrg_result_device): valid until the next decode on
         this decoder; the placed slots' identity row splits, the constant columns and the
         end-relative ``bytes_off`` words an optimistic decode left implicit (``info().implicit_cols``,
-        ``info().implicit_off_slots``) are written into them on the decode's stream first."""
+        ``info().implicit_off_slots``) are written into them on the decode's stream first, and so is
+        the int64 column of a narrowed decode (``info().i64_width``)."""
         cols = N.TfrgColumns()
         N.check(self._lib.tfrg_result_device(self._ctx, C.byref(cols)), "tfrg_result_device")
         return cols
+
+    def i64_narrow(self) -> tuple[int, int]:
+        """(device address, bytes per element) of the int64 column as the last decode stored it
+        (tfrg_result_i64_narrow): elements of 2 or 4 bytes after a narrowed decode, else the int64
+        column and 8. Element i is the int64 column's element i; nothing is widened. Valid until the
+        next decode on this decoder."""
+        p, w = C.c_void_p(), C.c_uint32()
+        N.check(self._lib.tfrg_result_i64_narrow(self._ctx, C.byref(p), C.byref(w)), "tfrg_result_i64_narrow")
+        return int(p.value or 0), int(w.value)
 
     def _learn_misses(self, buf: np.ndarray, info: N.TfrgInfo) -> bool:
         m = min(info.n_miss_entries, 1 << 16)
