@@ -1,248 +1,15 @@
 // tfrg_capi.cpp — device context of libtfrg: key table upload, HBM arena, decode orchestration and
 // result transfer (include/tfrg.h). The kernels live in the .hip files; launch_decode (tfrg_decode.cpp)
-// is their launch policy.
-#include <hip/hip_runtime.h>
+// is their launch policy. The context itself is in tfrg_ctx.h; the views of the last result are in
+// tfrg_fixed.cpp (dense, raw, resize, mel) and tfrg_rowlist.cpp (ragged, elems, ids, tokens, wordpiece, select).
 #include <stdlib.h>
 #include <string.h>
 
-#include <algorithm>
-#include <cmath>
-#include <map>
 #include <numeric>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/tfrg.h"
 #include "crc32c.h"
-#include "tfrg_dense.h"
-#include "tfrg_raw.h"
-#include "tfrg_resize.h"
-#include "tfrg_mel.h"
-#include "tfrg_elems.h"
-#include "tfrg_ids.h"
-#include "tfrg_tokens.h"
-#include "tfrg_wordpiece.h"
-#include "tfrg_ragged.h"
-#include "tfrg_select.h"
-#include "tfrg_frame.h"
-#include "tfrg_internal.h"
+#include "tfrg_ctx.h"
 #include "tfrg_learn.h"
-#include "tfrg_vocab.h"
-
-namespace tfrg {
-void set_error(const std::string& s);
-
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));               \
-      return TFRG_E_HIP;                                                           \
-    }                                                                              \
-  } while (0)
-
-// grow-only device buffer
-struct DBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) {
-      hipError_t e = hipFree(p);
-      if (e != hipSuccess) return e;
-      p = nullptr;
-      cap = 0;
-    }
-    size_t want = bytes < 256 ? 256 : bytes;
-    want = (want + 4095) & ~(size_t)4095;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
-
-constexpr uint32_t kMissCap = 1u << 16;
-
-}  // namespace tfrg
-
-using namespace tfrg;
-
-// record offsets of one decode call (DevBatch: u64 pairs, u32 pairs, or u32 ends of back-to-back records)
-struct Offsets {
-  const uint64_t* s64 = nullptr;
-  const uint64_t* e64 = nullptr;
-  const uint32_t* s32 = nullptr;
-  const uint32_t* e32 = nullptr;
-  uint32_t first = 0;
-  uint32_t mode = kOffU64;
-};
-
-// One decode as decode_device_any runs it: the three public entry points build one, finish_decode
-// re-runs a copy of the stored one with `full` / `worst_case` set.
-struct DecodeReq {
-  const uint8_t* d_bytes = nullptr;
-  uint64_t nbytes = 0;
-  Offsets off;
-  uint32_t n = 0, flags = 0;
-  hipStream_t stream = nullptr;  // NULL: the context's own
-  uint64_t cap_in = 0;      // total bytes of the ranges (tfrg_decode_host: > nbytes when they overlap); 0: nbytes
-  uint64_t bound = 0;       // no record above this; 0: the context's record_bound
-  bool full = false;        // no optimistic pass
-  bool worst_case = false;  // the value-capacity hints ignored
-  bool host = false;        // tfrg_decode_host: its reader is tfrg_result_fetch, the int64 column stays 8 bytes wide
-};
-
-// Everything known about the last decode. Replaced as a whole: decode_device_any and tfrg_set_schema
-// clear it (`valid` false: no result), and a decode assigns it once it is enqueued.
-struct Result {
-  bool valid = false;
-  DecodeReq req;  // as it ran: stream, capacity and bound resolved (the consumers' d_bytes, nbytes and e32)
-  uint64_t cap_i64 = 0, cap_f32 = 0, cap_b = 0;
-  bool materialized = false;
-  bool hinted = false;        // ran with a value-capacity hint below its worst case
-  bool opt_pending = false;   // ran optimistically and is not confirmed yet
-  bool mat_pending = false;   // its byte materialization waits for that confirmation
-  bool rs_complete = false;   // the placed slots' identity rows are written into the device columns
-  bool cols_complete = false; // tfrg_result_device wrote the constant columns (constant_fills)
-  bool off_complete = false;  // fill_implicit_off wrote the implicit bytes_off words
-  bool i64_complete = false;  // widen_i64 wrote the int64 column from the narrow one
-  uint32_t i64_w = 8;         // bytes per int64 value it stored: 4 or 2 into i64n (i64_width), else 8 into i64
-  uint32_t implicit = 0;      // TFRG_IMPLICIT_* columns the decode did not store
-  uint64_t off_mask = 0;      // slots whose bytes_off words it did not store (implicit_off_slots)
-  bool aux_zero = false;      // ran optimistically with stored statuses: aux is all 0
-  // the learned constants behind those columns as the decode ran with them (a later re-learn does not
-  // change its result), each copied only where its bit is set. Only k_tpl_lane leaves a column implicit
-  // (launch_decode), so such a decode has at most kLeanMaxSlots slots: no allocation per decode.
-  struct SlotConst {
-    int32_t rel_off;      // off_mask: the end-relative element offset
-    uint32_t elem_len;    // TFRG_IMPLICIT_BYTES_LEN: the bytes element length
-    uint16_t order_word;  // TFRG_IMPLICIT_ORDER
-  } slot[kLeanMaxSlots] = {};
-};
-
-// Every device buffer of a context. `each` is the one list of them, checked against the members.
-struct Arena {
-  DBuf crc_tab, consts;  // constants
-  DBuf ht, key_hash, key_off, key_blob, key_slot, slot_kind, key_w, krec;  // schema
-  DBuf in_bytes, in_start, in_end;  // host staging for tfrg_decode_host
-  // columns and work space of a decode
-  DBuf status, aux, verdict, order, count, loc, rs, slot_base, totals, kind_totals;
-  DBuf ident;  // 0, 1, 2, ... (ident_n words): the fetched row splits of placed slots
-  DBuf i64n;  // the int64 column of a narrowed decode: element i at byte i * width (tfrg_info.i64_width)
-  DBuf i64, f32, b_off, b_len, big_list, slow_list, miss, info, tsum, crc_rec, crc_base, crc_part;
-  DBuf dq, dq_cnt;  // deferred packed-int64 bodies (k_body_count)
-  DBuf lmask, rlist;  // k_tpl_lane's per-group miss masks and listed groups
-  DBuf bdata, boff64, blb, bbig;  // TFRG_FLAG_MATERIALIZE_BYTES
-  DBuf tpl, spec;  // record-shape templates, speculative placement (tfrg_learn_templates)
-  DBuf fr_tab, fr_dev;  // tfrg_index_device: chunk table, piece rows + summary
-  DBuf rg_tsum;  // tfrg_result_ragged_rows: the per-tile sums
-  DBuf el_tsum;  // tfrg_result_ragged_elems: the per-tile element counts and byte sums
-  DBuf id_tsum;  // tfrg_result_elem_ids: the per-tile element counts
-  DBuf tk_tsum;  // tfrg_result_token_ids: the per-tile token counts
-  DBuf wp_tsum;  // tfrg_result_wordpiece_ids: the per-tile piece counts
-  DBuf sel_buf;  // tfrg_result_select_rows: the candidates' ballot words, then the per-tile sums
-  template <class F>
-  void each(F f) {
-    DBuf* const all[] = {&crc_tab, &consts, &ht, &key_hash, &key_off, &key_blob, &key_slot, &slot_kind, &key_w, &krec,
-                         &in_bytes, &in_start, &in_end, &status, &aux, &verdict, &order, &count, &loc, &rs, &slot_base,
-                         &totals, &kind_totals, &ident, &i64n, &i64, &f32, &b_off, &b_len, &big_list, &slow_list, &miss, &info,
-                         &tsum, &crc_rec, &crc_base, &crc_part, &dq, &dq_cnt, &lmask, &rlist, &bdata, &boff64, &blb,
-                         &bbig, &tpl, &spec, &fr_tab, &fr_dev, &rg_tsum, &el_tsum,
-                         &id_tsum, &tk_tsum, &wp_tsum, &sel_buf};
-    static_assert(sizeof(all) / sizeof(*all) * sizeof(DBuf) == sizeof(Arena), "a buffer is missing from the list");
-    for (DBuf* b : all) f(*b);
-  }
-};
-
-// Switches read from the environment in tfrg_ctx_create (A/B measurements and tests)
-struct Switches {
-  bool tpl_on = true;        // TFRG_TEMPLATES (also tfrg_ctx_set_templates)
-  bool spec_on = true;       // TFRG_SPEC: speculative single-value placement
-  int tpl_stage = 1;         // TFRG_TPL_STAGE: k_tpl_lane's staged windows 0 off, 1 on large batches, 2 on any
-  uint32_t tpl_gpw = 0;      // TFRG_TPL_GPW=2, 4 or 8: its groups per wave; 0: launch_tpl_lane's choice
-  bool optimistic = true;    // TFRG_OPTIMISTIC=0: no optimistic decodes
-  bool implicit_off = true;  // TFRG_IMPLICIT_OFF=0: every bytes_off word stored
-  bool narrow_i64 = true;    // TFRG_NARROW_I64=0: every int64 value stored as 8 bytes
-  bool walk_beside = true;   // TFRG_WALK_BESIDE=0: large records walked before the CRC
-  uint32_t walk_blocks = 0;  // TFRG_WALK_BLOCKS: cap on its walking workgroups; 0 = automatic
-  int dense_nt = 0;          // TFRG_DENSE_NT=1: k_dense's output stores nontemporal
-  // TFRG_DEBUG_POISON_LOC="r0,r1,..." (at most 4): records whose list locations are poisoned after the count passes
-  uint32_t poison[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-};
-
-// Per context: the device, its streams and events, the arena, the schema, the learned shapes and the
-// settings. What belongs to one decode is in `res`.
-struct tfrg_ctx : Arena {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t last_stream = nullptr;  // of the last decode enqueued: arena buffers may be in use on it
-  Switches sw;
-  uint32_t lane_max = 2048;
-  uint32_t wave_stage = 0xffffffffu;  // clamped to the kernel's stage size
-  uint64_t record_bound = 0;  // tfrg_ctx_set_record_bound: no record above this (0 = unknown)
-  int num_cus = 256;
-  uint32_t cu_lds = 65536;     // LDS bytes of a CU
-  uint32_t n_keys = 0, n_slots = 0, ht_mask = 0;
-  size_t ident_n = 0;
-  bool tsum_dirty = true;  // the scan words must be cleared before the next decode
-  // info words: two slots, decode k using slot k % 2; k_lane_count zeroes the other one for the
-  // next decode (no per-call memset). info_clean: the next slot is known to be zero.
-  uint32_t info_slot = 0;
-  bool info_clean = false;
-  uint32_t* info_pin = nullptr;  // pinned host copy of the info words + kind totals (confirmation)
-  hipEvent_t order_ev = nullptr;  // orders a decode on a new stream after the previous one
-  hipEvent_t consumer_ev[2] = {nullptr, nullptr};  // fence_open / fence_close: consumer stream -> decode stream -> consumer
-  Result res;  // the last decode
-  // record-shape templates (tfrg_learn_templates): host key table, device templates
-  std::unordered_map<std::string, uint32_t> key_id;
-  std::vector<int32_t> key_slot_h;  // [4 * key]: flags, slot per kind
-  uint32_t n_tpl = 0;
-  uint32_t tpl_w = 0;  // window words of the templates (16 / 32 / 64)
-  size_t tpl_img_off = 0;  // the lane image follows the window-form templates in tpl
-  uint32_t tpl_img_words = 0;
-  uint32_t tpl_tab_words = 0;  // the packed CRC position tables follow the image
-  std::vector<uint32_t> tpl_h;  // host copy of the template words
-  bool tpl_learned = false;
-  bool tpl_full = false;  // the templates took every record of their learning sample
-  uint32_t tpl_frames = 0;  // frame classes of the kept templates: bit 0 spec, bit 1 unchecked
-  // speculative single-value placement (DevSchema::spec), derived from the templates
-  std::vector<uint8_t> slot_kind_h;
-  std::vector<uint32_t> spec_h;  // host copy (k_tpl_lane's placement targets)
-  bool have_spec = false;
-  // what the learned shapes have in common (Learned): an optimistic decode (launch_decode: a batch of
-  // C1-shaped records whose templates took the learning sample runs as k_tpl_lane alone) leaves such
-  // columns implicit and snapshots the constant into its Result
-  bool ord_const = false;     // every shape has the same order words
-  bool len_const = false;     // ... and the same bytes element lengths
-  std::vector<uint32_t> const_len;  // per slot: that length
-  uint64_t off_rel = 0;       // bytes slots at one end-relative offset in every shape
-  std::vector<int32_t> rel_off;  // per slot: that offset
-  uint32_t i64_width = 8;     // bytes that hold every int64 value the shapes place (Learned::i64_width)
-  // optional per-stage HIP events (tfrg_ctx_set_profiling)
-  bool profiling = false;
-  bool have_events = false;
-  hipEvent_t ev[kNumStages + 1] = {};
-  // value-capacity hints (tfrg_ctx_set_value_caps; 0: the worst case)
-  uint64_t hint_i64 = 0, hint_f32 = 0, hint_b = 0;
-  uint64_t hint_reruns = 0;  // decodes re-run: a hint was too small, or an optimistic decode incomplete
-  uint32_t index_chunk = kIndexChunkDefault;  // tfrg_ctx_set_index_chunk
-  uint32_t ragged_tile = kRaggedTileDefault;  // tfrg_ctx_set_ragged_tile: rows per tile
-  uint32_t select_tile = kSelTileDefault;     // tfrg_ctx_set_select_tile: candidates per tile
-  uint32_t token_split = kTokSplitDefault;   // tfrg_ctx_set_token_split: rows above it go by wave
-  uint32_t select_scan = kSelScanDefault;     // tfrg_ctx_set_select_scan: CONTAINS elements above it go by wave
-  void* fr_pin = nullptr;  // tfrg_index_device: pinned host staging
-  size_t fr_pin_cap = 0;
-};
 
 extern "C" {
 
@@ -1112,9 +879,8 @@ static int overflow_status(const uint32_t* h) {
   return TFRG_E_LIMIT;
 }
 
-// An optimistic decode, or one whose value capacities were hinted below the worst case, is confirmed
-// (or re-run in full / at the worst case) before anything reads its columns on the device.
-static int confirm_pending(tfrg_ctx* c) {
+// (tfrg_ctx.h: the confirmation every reader of the device columns starts with)
+extern "C++" int tfrg::confirm_pending(tfrg_ctx* c) {
   if (!c->res.opt_pending && !c->res.hinted) return 0;
   HIP_TRY(hipSetDevice(c->device));
   uint32_t h[kInfoCount];
@@ -1171,8 +937,6 @@ static std::vector<std::pair<uint32_t, uint64_t>> bytes_slot_rows(const tfrg_ctx
   return out;
 }
 
-// (TFRG_IMPLICIT_BYTES_LEN) a bytes slot's constant element length, as the decode ran with it
-static uint32_t implicit_len(const Result& r, uint32_t slot) { return slot < kLeanMaxSlots ? r.slot[slot].elem_len : 0u; }
 
 // The constant columns of the last decode (tfrg_info.implicit_cols, and the aux words of an optimistic
 // decode with stored statuses): rows [first, first + rows) of `col` hold `value` in elements of `width`
@@ -1291,1250 +1055,6 @@ int tfrg_result_device(tfrg_ctx* c, tfrg_columns* d) {
   d->bytes_data = r.materialized ? c->bdata.as<uint8_t>() : nullptr;
   d->bytes_offsets = r.materialized ? c->boff64.as<uint64_t>() : nullptr;
   return 0;
-}
-
-// ---- Host-side setup shared by the entry points over the last result (tfrg_result_dense / _dense_rows,
-// _ragged_rows, _select_rows). `bad` is the entry point's own: it prefixes the function's name.
-extern "C++" {
-template <class Bad>
-static int check_result(const tfrg_ctx* c, const Bad& bad) {
-  if (!c) return bad("no context");
-  if (!c->res.valid) return bad("no result (decode first)");
-  return 0;
-}
-template <class Bad>
-static int check_specs(const tfrg_ctx* c, const void* specs, uint32_t n_specs, uint32_t max_specs, const Bad& bad) {
-  if (const int rc = check_result(c, bad)) return rc;
-  if (!specs || n_specs == 0 || n_specs > max_specs) return bad("n_specs must be 1.." + std::to_string(max_specs));
-  return 0;
-}
-// (the spec's slot exists and its TFRG_DENSE_* dtype fits the slot's kind)
-template <class Bad>
-static int check_slot_dtype(const tfrg_ctx* c, const std::string& at, uint32_t slot, uint32_t dtype, const Bad& bad) {
-  if (slot >= c->n_slots) return bad(at + "slot " + std::to_string(slot) + " >= n_slots");
-  const uint32_t kind = c->slot_kind_h[slot] & 3u;
-  const bool fits = (kind == TFRG_KIND_INT64 && (dtype == TFRG_DENSE_I64 || dtype == TFRG_DENSE_I32)) ||
-                    (kind == TFRG_KIND_FLOAT && dtype == TFRG_DENSE_F32) ||
-                    (kind == TFRG_KIND_BYTES && dtype == TFRG_DENSE_U8);
-  if (!fits) return bad(at + "dtype " + std::to_string(dtype) + " does not fit the slot's kind " + std::to_string(kind));
-  return 0;
-}
-// The row list. tfrg_result_dense_rows always has one (`required`): its rows_dtype is checked whatever
-// d_rows is, and m > 0 rows need a d_rows. Ragged and select take a NULL d_rows as the identity list and
-// read rows_dtype only beside a list. (Two functions: select checks its out_dtype between them.)
-template <class Bad>
-static int check_rows_dtype(const void* d_rows, uint32_t rows_dtype, bool required, const Bad& bad) {
-  if ((required || d_rows) && rows_dtype != TFRG_ROWS_I32 && rows_dtype != TFRG_ROWS_I64)
-    return bad("rows_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(rows_dtype));
-  return 0;
-}
-template <class Bad>
-static int check_rows_m(const void* d_rows, uint32_t m, bool required, const Bad& bad) {
-  if (m >= 0x80000000u) return bad("m must be below 2^31");
-  if (required && m && !d_rows) return bad("d_rows is NULL");
-  return 0;
-}
-
-// (a record without a value reads element 0 of a value array and drops it: an array that was never
-// allocated is stood in for by the slot bases, which every result has)
-template <class T>
-static const T* view_col(const tfrg_ctx* c, const DBuf& b) {
-  return static_cast<const T*>(b.p ? b.p : c->slot_base.p);
-}
-// The width of the int64 column, for the argument structs that have the word (the passes that read
-// int64 values: dense, ragged, select, resize); false for the others
-template <class Args>
-static auto set_i64_w(Args& a, uint32_t w, int) -> decltype((void)(a.i64_w = w), true) {
-  a.i64_w = w;
-  return true;
-}
-template <class Args>
-static bool set_i64_w(Args&, uint32_t, long) {
-  return false;
-}
-// The column view of the last result: what DenseArgs, RaggedArgs and SelectArgs have in common
-template <class Args>
-static void fill_columns(const tfrg_ctx* c, Args& a) {
-  a.rs = c->rs.as<uint32_t>();
-  a.slot_base = c->slot_base.as<uint64_t>();
-  // (a narrowed decode: the narrow column as it is for the passes that read int64 values, through
-  // col_i64 -- no widening pass; the others read neither column)
-  const bool narrow = set_i64_w(a, c->res.i64_w, 0) && c->res.i64_w < 8u;
-  a.i64 = view_col<int64_t>(c, narrow ? c->i64n : c->i64);
-  a.f32 = view_col<uint32_t>(c, c->f32);
-  a.b_len = view_col<uint32_t>(c, c->b_len);
-  if (c->res.materialized) a.b_off64 = view_col<uint64_t>(c, c->boff64);
-  a.info = c->info.as<uint32_t>() + c->info_slot * kInfoCount;
-  a.n = c->res.req.n;
-}
-// The bytes' source: the views' input buffer, readable to round_up(nbytes, 16), or the byte column
-template <class Args>
-static void fill_bytes_source(const tfrg_ctx* c, Args& a) {
-  a.b_off = view_col<uint32_t>(c, c->b_off);
-  const Result& r = c->res;
-  a.in = r.materialized ? c->bdata.as<uint8_t>() : r.req.d_bytes;
-  const uint64_t bound = r.materialized ? (uint64_t)c->bdata.cap & ~15ull : (r.req.nbytes + 15ull) & ~15ull;
-  a.in_bound = a.in ? (uint32_t)std::min<uint64_t>(bound, 0xfffffff0ull) : 0;
-  // (the decode's u32 ends, for the specs with a const_off: read for such a spec only)
-  a.end32 = r.off_mask ? r.req.off.e32 : nullptr;
-}
-}  // extern "C++"
-
-// A bytes slot's end-relative element offset where the last decode did not store its bytes_off words
-// (tfrg_info.implicit_off_slots: the element of record g is end32[g] + that); else the kernels' "the
-// column is stored" sentinel.
-static_assert(kDenseOffStored == kRaggedOffStored, "one const_off lookup serves both");
-static int32_t const_off_of(const tfrg_ctx* c, uint32_t slot, bool reads_off) {
-  if (!reads_off || slot >= kLeanMaxSlots || !((c->res.off_mask >> slot) & 1ull)) return kDenseOffStored;
-  return c->res.slot[slot].rel_off;
-}
-
-// A bytes slot's constant element length where the last decode did not store the bytes_len column (as
-// constant_fills: the shapes' length holds); else, or for a spec / term that reads no length, the
-// kernels' "the column is stored" sentinel.
-static_assert(kDenseNoLen == kRaggedNoLen && kRaggedNoLen == kSelNoLen, "one const_len lookup serves all three");
-static_assert(kElemsNoLen == kDenseNoLen && kElemsOffStored == kDenseOffStored, "and tfrg_elems.h's kernels");
-static uint32_t const_len_of(const tfrg_ctx* c, uint32_t slot, bool reads_len) {
-  if (!reads_len || !(c->res.implicit & TFRG_IMPLICIT_BYTES_LEN)) return kDenseNoLen;
-  return implicit_len(c->res, slot);
-}
-
-// The consumer-stream fence: the work an entry point puts on the decode's stream *st starts after what
-// the consumer stream *cs holds so far (fence_open), and the consumer waits for it (fence_close). A
-// NULL consumer_stream is the decode's own stream: no fence.
-static int fence_open(tfrg_ctx* c, void* consumer_stream, hipStream_t* st, hipStream_t* cs) {
-  *st = c->last_stream;
-  *cs = consumer_stream ? static_cast<hipStream_t>(consumer_stream) : *st;
-  if (*cs == *st) return 0;
-  for (hipEvent_t& e : c->consumer_ev)
-    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(c->consumer_ev[0], *cs));
-  HIP_TRY(hipStreamWaitEvent(*st, c->consumer_ev[0], 0));
-  return 0;
-}
-static int fence_close(tfrg_ctx* c, hipStream_t st, hipStream_t cs) {
-  if (cs == st) return 0;
-  HIP_TRY(hipEventRecord(c->consumer_ev[1], st));
-  HIP_TRY(hipStreamWaitEvent(cs, c->consumer_ev[1], 0));
-  return 0;
-}
-
-// The row list of tfrg_result_dense_rows (d_rows null: tfrg_result_dense, every record in order)
-struct DenseRows {
-  const void* d_rows = nullptr;
-  uint32_t dtype = 0, m = 0;
-  int64_t row0 = 0;
-  uint32_t* d_skipped = nullptr;
-};
-
-static int result_dense(const char* fn, bool by_rows, tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_specs,
-                        const DenseRows& rows, uint32_t* d_stats, void* consumer_stream) {
-  auto bad = [fn](const std::string& why) {
-    set_error(std::string(fn) + ": " + why);
-    return TFRG_E_ARG;
-  };
-  if (const int rc = check_specs(c, specs, n_specs, TFRG_DENSE_MAX_SPECS, bad)) return rc;
-  static_assert(TFRG_DENSE_MAX_SPECS == kDenseMaxSpecs && TFRG_DENSE_MAX_WIDTH == kDenseMaxWidth &&
-                    TFRG_DENSE_I64 == kDenseI64 && TFRG_DENSE_I32 == kDenseI32 && TFRG_DENSE_F32 == kDenseF32 &&
-                    TFRG_DENSE_U8 == kDenseU8,
-                "tfrg.h mirrors tfrg_dense.h");
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_dense_spec& s = specs[i];
-    const std::string at = "spec " + std::to_string(i) + ": ";
-    if (const int rc = check_slot_dtype(c, at, s.slot, s.dtype, bad)) return rc;
-    if (s.width == 0 || s.width > TFRG_DENSE_MAX_WIDTH)
-      return bad(at + "width must be 1.." + std::to_string(TFRG_DENSE_MAX_WIDTH));
-    if (!s.out) return bad(at + "out is NULL");
-    if (s.reserved) return bad(at + "reserved must be 0");
-  }
-  if (by_rows) {
-    if (const int rc = check_rows_dtype(rows.d_rows, rows.dtype, true, bad)) return rc;
-    if (const int rc = check_rows_m(rows.d_rows, rows.m, true, bad)) return rc;
-  }
-  if (!by_rows && c->res.req.n == 0) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  if (const int rc = confirm_pending(c)) return rc;
-  // the rows of every output
-  const uint32_t out_rows = by_rows ? rows.m : c->res.req.n;
-  DenseArgs a{};
-  if (by_rows) {
-    a.rows = rows.d_rows;
-    a.rows64 = rows.dtype == TFRG_ROWS_I64;
-    a.m = rows.m;
-    a.row0 = rows.row0;
-    a.skipped = rows.d_skipped;
-  }
-  fill_columns(c, a);
-  fill_bytes_source(c, a);
-  a.stats = d_stats;
-  a.n_specs = n_specs;
-  a.nt = (uint32_t)c->sw.dense_nt;
-  // workgroups per spec: one per chunk of its output, within an even share of 16 per CU
-  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 16u / n_specs);
-  uint32_t blocks = 0;
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_dense_spec& s = specs[i];
-    DenseSpec& d = a.sp[i];
-    d.out = s.out;
-    d.lengths = s.lengths;
-    d.fill = s.fill;
-    d.slot = s.slot;
-    d.dtype = s.dtype;
-    d.width = s.width;
-    d.const_len = const_len_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
-    d.const_off = const_off_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
-    const uint64_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
-    const uint64_t total = (uint64_t)out_rows * s.width * isz;
-    // 16-byte units, or single elements where the output's base is not 16-byte aligned
-    const uint64_t work = ((uintptr_t)s.out & 15u) ? total / isz : (total >> 4) + 16;
-    d.blk0 = blocks;
-    d.nblk = (uint32_t)std::min<uint64_t>(cap, (work + kDenseChunk - 1) / kDenseChunk);
-    blocks += d.nblk;
-  }
-  hipStream_t st, cs;
-  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
-  // (counters that lie back to back, stats first, are zeroed by one memset: one launch less per step)
-  const bool one_memset = by_rows && c->res.req.n && d_stats && rows.d_skipped == d_stats + 4 * (size_t)n_specs;
-  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * (one_memset ? 20 : 16), st));
-  // (a row list over an empty result: no record to read, every row is skipped)
-  if (by_rows && rows.d_skipped && !one_memset)
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rows.d_skipped), c->res.req.n ? 0 : (int)rows.m, n_specs, st));
-  if (out_rows && c->res.req.n) HIP_TRY(launch_dense(a, blocks, st));
-  return fence_close(c, st, cs);
-}
-
-int tfrg_result_dense(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_specs, uint32_t* d_stats,
-                      void* consumer_stream) {
-  return result_dense("tfrg_result_dense", false, c, specs, n_specs, DenseRows{}, d_stats, consumer_stream);
-}
-
-int tfrg_result_dense_rows(tfrg_ctx* c, const tfrg_dense_spec* specs, uint32_t n_specs, const void* d_rows,
-                           uint32_t rows_dtype, uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped,
-                           void* consumer_stream) {
-  DenseRows rows;
-  rows.d_rows = d_rows;
-  rows.dtype = rows_dtype;
-  rows.m = m;
-  rows.row0 = row0;
-  rows.d_skipped = d_skipped;
-  return result_dense("tfrg_result_dense_rows", true, c, specs, n_specs, rows, d_stats, consumer_stream);
-}
-
-// ---- The frame of the entry points that pack per-spec outputs for a list of rows (tfrg_result_ragged_rows,
-// _ragged_elems, _elem_ids): the checks in the one order all three make them, the tiles and the split,
-// the scratch, the consumer fence and the counters, around what an entry point brings as its own.
-struct RowListCall {  // the arguments the three have in common
-  const void* d_rows;
-  uint32_t rows_dtype, m;
-  int64_t row0;
-  uint64_t* d_totals;
-  uint32_t* d_stats;
-  void* consumer_stream;
-};
-struct RowListKind {
-  const char* fn;
-  uint32_t max_specs;
-  DBuf Arena::*tsum;   // the scratch of the per-tile sums
-  uint32_t words;      // u64 words per (spec, tile) in it, and per spec in d_totals
-  uint32_t split0;     // workgroups per tile that share its bytes: where no spec has bytes to store,
-  uint32_t max_split;  // and at the most (while the launch is below 4 per CU)
-};
-extern "C++" {
-// check(spec, at, bad, any_values): the spec's own checks; any_values: it has bytes to store.
-// launch(a, split, st): the spec table of `a` (its other fields are filled) and the kernels.
-// empty(spec, st): the spec's offsets of a result without a row or a record, where all of them are 0.
-// Nothing is written on the device before every check has passed.
-template <class Args, class Spec, class Check, class Launch, class Empty>
-static int result_row_list(const RowListKind& k, tfrg_ctx* c, const Spec* specs, uint32_t n_specs, const RowListCall& q,
-                           const Check& check, const Launch& launch, const Empty& empty) {
-  auto bad = [&k](const std::string& why) {
-    set_error(std::string(k.fn) + ": " + why);
-    return TFRG_E_ARG;
-  };
-  if (const int rc = check_specs(c, specs, n_specs, k.max_specs, bad)) return rc;
-  bool any_values = false;
-  for (uint32_t i = 0; i < n_specs; ++i)
-    if (const int rc = check(specs[i], "spec " + std::to_string(i) + ": ", bad, any_values)) return rc;
-  if (const int rc = check_rows_dtype(q.d_rows, q.rows_dtype, false, bad)) return rc;
-  if (const int rc = check_rows_m(q.d_rows, q.m, false, bad)) return rc;
-  const uint32_t m = q.m, tile = c->ragged_tile;
-  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile;
-  uint64_t split = k.split0;
-  if (any_values && tiles) {
-    const uint64_t want = (uint64_t)std::max(c->num_cus, 1) * 4u, have = tiles * n_specs;
-    split = std::min<uint64_t>(k.max_split, std::max<uint64_t>(1, (want + have - 1) / have));
-  }
-  if (tiles * n_specs * std::max<uint64_t>(split, 1) > 0x7fffffffull)
-    return bad("too many tiles for one launch: raise the ragged tile");
-  HIP_TRY(hipSetDevice(c->device));
-  if (const int rc = confirm_pending(c)) return rc;
-  const bool run = m && c->res.req.n;
-  DBuf& tsum = c->*k.tsum;
-  if (run) HIP_TRY(tsum.ensure((size_t)(tiles * n_specs) * k.words * 8));
-  hipStream_t st, cs;
-  if (const int rc = fence_open(c, q.consumer_stream, &st, &cs)) return rc;
-  if (q.d_stats) HIP_TRY(hipMemsetAsync(q.d_stats, 0, (size_t)n_specs * 16, st));
-  if (run) {
-    Args a{};
-    fill_columns(c, a);
-    fill_bytes_source(c, a);
-    a.stats = q.d_stats;
-    a.totals = q.d_totals;
-    a.tsum = tsum.as<uint64_t>();
-    a.rows = q.d_rows;
-    a.rows64 = q.rows_dtype == TFRG_ROWS_I64;
-    a.row0 = q.row0;
-    a.m = m;
-    a.n_specs = n_specs;
-    a.tile = tile;
-    a.tiles = (uint32_t)tiles;
-    if (const int rc = launch(a, (uint32_t)split, st)) return rc;
-  } else {
-    // no row, or no record (every row is skipped): all offsets and totals are 0
-    for (uint32_t i = 0; i < n_specs; ++i) {
-      if (const int rc = empty(specs[i], st)) return rc;
-      if (q.d_stats && m)
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(q.d_stats + 4 * (size_t)i + 3), (int)m, 1, st));
-    }
-    if (q.d_totals) HIP_TRY(hipMemsetAsync(q.d_totals, 0, (size_t)n_specs * k.words * 8, st));
-  }
-  return fence_close(c, st, cs);
-}
-// (the spec's slot exists and is a bytes_list slot)
-template <class Bad>
-static int check_bytes_slot(const tfrg_ctx* c, const std::string& at, uint32_t slot, const Bad& bad) {
-  if (slot >= c->n_slots) return bad(at + "slot " + std::to_string(slot) + " >= n_slots");
-  const uint32_t kind = c->slot_kind_h[slot] & 3u;
-  if (kind != TFRG_KIND_BYTES)
-    return bad(at + "slot " + std::to_string(slot) + " is not a bytes_list slot (kind " + std::to_string(kind) + ")");
-  return 0;
-}
-}  // extern "C++"
-
-// Raw tensors from bytes features for a list of rows (tfrg_raw.h): one launch, all specs. The checks,
-// the column view, the confirmation and the consumer fence are the ones above; what is its own is the
-// spec table and the split into work items.
-int tfrg_result_raw_rows(tfrg_ctx* c, const tfrg_raw_spec* specs, uint32_t n_specs, const void* d_rows,
-                         uint32_t rows_dtype, uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped,
-                         void* consumer_stream) {
-  auto bad = [](const std::string& why) {
-    set_error("tfrg_result_raw_rows: " + why);
-    return TFRG_E_ARG;
-  };
-  static_assert(TFRG_RAW_MAX_SPECS == kRawMaxSpecs && TFRG_RAW_MAX_COUNT == kRawMaxCount &&
-                    TFRG_RAW_MAX_CHANNELS == kRawMaxChannels && TFRG_RAW_U8 == kRawU8 && TFRG_RAW_I8 == kRawI8 &&
-                    TFRG_RAW_U16 == kRawU16 && TFRG_RAW_I16 == kRawI16 && TFRG_RAW_I32 == kRawI32 &&
-                    TFRG_RAW_F16 == kRawF16 && TFRG_RAW_BF16 == kRawBF16 && TFRG_RAW_F32 == kRawF32 &&
-                    TFRG_RAW_OUT_F32 == kRawOutF32 && TFRG_RAW_OUT_F16 == kRawOutF16 &&
-                    TFRG_RAW_OUT_BF16 == kRawOutBF16 && TFRG_RAW_OUT_SAME == kRawOutSame,
-                "tfrg.h mirrors tfrg_raw.h");
-  static_assert(sizeof(tfrg_raw_spec) == 176, "tfrg.h states the size");
-  static_assert(kRawNoLen == kDenseNoLen && kRawOffStored == kDenseOffStored, "const_len_of / const_off_of serve k_raw");
-  if (const int rc = check_specs(c, specs, n_specs, TFRG_RAW_MAX_SPECS, bad)) return rc;
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_raw_spec& s = specs[i];
-    const std::string at = "spec " + std::to_string(i) + ": ";
-    if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
-    if (s.src >= kRawSrcs) return bad(at + "unknown src " + std::to_string(s.src));
-    if (s.out >= kRawOuts) return bad(at + "unknown out " + std::to_string(s.out));
-    if (s.count == 0 || s.count > TFRG_RAW_MAX_COUNT) return bad(at + "count must be 1.." + std::to_string(TFRG_RAW_MAX_COUNT));
-    if (s.channels == 0 || s.channels > TFRG_RAW_MAX_CHANNELS)
-      return bad(at + "channels must be 1.." + std::to_string(TFRG_RAW_MAX_CHANNELS));
-    if (s.count % s.channels) return bad(at + "count must be a multiple of channels");
-    if (s.planar > 1) return bad(at + "planar must be 0 or 1");
-    if (!s.out_ptr) return bad(at + "out_ptr is NULL");
-    if ((uintptr_t)s.out_ptr & (raw_out_size(s.src, s.out) - 1u)) return bad(at + "out_ptr must be aligned to the output element size");
-    if (s.reserved) return bad(at + "reserved must be 0");
-  }
-  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
-  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if (const int rc = confirm_pending(c)) return rc;
-  RawArgs a{};
-  a.rows = d_rows;
-  a.rows64 = d_rows && rows_dtype == TFRG_ROWS_I64;
-  a.m = m;
-  a.row0 = row0;
-  a.skipped = d_skipped;
-  fill_columns(c, a);
-  fill_bytes_source(c, a);
-  a.stats = d_stats;
-  a.n_specs = n_specs;
-  a.nt = (uint32_t)c->sw.dense_nt;
-  // workgroups per spec: one per work item (wide rows: kRawSpan tiles; narrow rows: four rows, a wave
-  // each), within an even share of 32 per CU; they stride over what is left
-  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 32u / n_specs);
-  uint32_t blocks = 0;
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_raw_spec& s = specs[i];
-    RawSpec& d = a.sp[i];
-    const uint32_t osz = raw_out_size(s.src, s.out);
-    d.out = s.out_ptr;
-    d.lengths = s.lengths;
-    d.fill = osz == 4 ? s.fill : s.fill & ((1u << (8 * osz)) - 1u);
-    d.slot = s.slot;
-    d.src = s.src;
-    d.outt = s.out;
-    d.count = s.count;
-    d.channels = s.channels;
-    d.planar = s.planar;
-    d.const_len = const_len_of(c, s.slot, true);
-    d.const_off = const_off_of(c, s.slot, true);
-    const uint32_t tp = raw_tile_pixels(s.channels), tiles = (s.count / s.channels + tp - 1) / tp;
-    d.spans = (tiles + kRawSpan - 1) / kRawSpan;
-    const uint64_t work = s.count > kRawNarrow ? (uint64_t)m * d.spans : ((uint64_t)m + 3) / 4;
-    d.blk0 = blocks;
-    d.nblk = (uint32_t)std::min<uint64_t>(cap, work);
-    blocks += d.nblk;
-    memcpy(d.scale, s.scale, sizeof d.scale);
-    memcpy(d.bias, s.bias, sizeof d.bias);
-  }
-  hipStream_t st, cs;
-  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
-  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
-  // (a row list over an empty result: no record to read, every row is skipped)
-  if (d_skipped)
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_skipped), c->res.req.n ? 0 : (int)m, n_specs, st));
-  if (m && c->res.req.n) HIP_TRY(launch_raw(a, blocks, st));
-  return fence_close(c, st, cs);
-}
-
-// Resized raw images for a list of rows (tfrg_resize.h): one launch of k_resize for all plain specs and
-// one of k_resize_aa for all antialiased ones. The frame is tfrg_result_raw_rows's; its own are the int64
-// slots of the shape, the geometry of the outputs, the split into bands and each launch's LDS.
-int tfrg_result_raw_resize(tfrg_ctx* c, const tfrg_resize_spec* specs, uint32_t n_specs, const void* d_rows,
-                           uint32_t rows_dtype, uint32_t m, int64_t row0, const int32_t* d_boxes,
-                           const uint8_t* d_flip, uint32_t* d_stats, uint32_t* d_skipped, void* consumer_stream) {
-  auto bad = [](const std::string& why) {
-    set_error("tfrg_result_raw_resize: " + why);
-    return TFRG_E_ARG;
-  };
-  static_assert(TFRG_RESIZE_MAX_SPECS == kResizeMaxSpecs && TFRG_RESIZE_MAX_CHANNELS == kResizeMaxChannels &&
-                    TFRG_RESIZE_MAX_OUT == kResizeMaxOut && TFRG_RESIZE_MAX_SRC == kResizeMaxSrc &&
-                    TFRG_RESIZE_MAX_ROW_BYTES == kResizeMaxRowBytes && TFRG_RESIZE_CONST == kResizeConst &&
-                    TFRG_RESIZE_BILINEAR == kResizeBilinear && TFRG_RESIZE_NEAREST == kResizeNearest &&
-                    TFRG_RESIZE_ANTIALIAS == kResizeAntialias,
-                "tfrg.h mirrors tfrg_resize.h");
-  static_assert(sizeof(tfrg_resize_spec) == 104, "tfrg.h states the size");
-  if (const int rc = check_specs(c, specs, n_specs, TFRG_RESIZE_MAX_SPECS, bad)) return rc;
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_resize_spec& s = specs[i];
-    const std::string at = "spec " + std::to_string(i) + ": ";
-    if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
-    if (s.src >= kRawSrcs) return bad(at + "unknown src " + std::to_string(s.src));
-    if (s.out >= kRawOuts) return bad(at + "unknown out " + std::to_string(s.out));
-    if (s.interp == (TFRG_RESIZE_NEAREST | TFRG_RESIZE_ANTIALIAS))
-      return bad(at + "TFRG_RESIZE_ANTIALIAS filters: it goes with TFRG_RESIZE_BILINEAR only");
-    if (s.interp >= kResizeInterps && s.interp != (TFRG_RESIZE_BILINEAR | TFRG_RESIZE_ANTIALIAS))
-      return bad(at + "unknown interp " + std::to_string(s.interp));
-    if (s.out == TFRG_RAW_OUT_SAME && s.interp != TFRG_RESIZE_NEAREST)
-      return bad(at + "TFRG_RAW_OUT_SAME copies bits: it goes with TFRG_RESIZE_NEAREST only");
-    if (s.channels == 0 || s.channels > TFRG_RESIZE_MAX_CHANNELS)
-      return bad(at + "channels must be 1.." + std::to_string(TFRG_RESIZE_MAX_CHANNELS));
-    if (s.out_h == 0 || s.out_h > TFRG_RESIZE_MAX_OUT || s.out_w == 0 || s.out_w > TFRG_RESIZE_MAX_OUT)
-      return bad(at + "out_h and out_w must be 1.." + std::to_string(TFRG_RESIZE_MAX_OUT));
-    if (s.out_w * s.channels > TFRG_RESIZE_MAX_OUT)
-      return bad(at + "out_w * channels must be at most " + std::to_string(TFRG_RESIZE_MAX_OUT));
-    const struct {
-      const char* what;
-      uint32_t slot, konst;
-    } ext[2] = {{"h_slot", s.h_slot, s.src_h}, {"w_slot", s.w_slot, s.src_w}};
-    for (const auto& e : ext) {
-      if (e.slot == TFRG_RESIZE_CONST) {
-        if (e.konst == 0 || e.konst > TFRG_RESIZE_MAX_SRC)
-          return bad(at + "a constant extent must be 1.." + std::to_string(TFRG_RESIZE_MAX_SRC));
-      } else if (e.slot >= c->n_slots || (c->slot_kind_h[e.slot] & 3u) != TFRG_KIND_INT64) {
-        return bad(at + e.what + " " + std::to_string(e.slot) + " is not an int64_list slot");
-      }
-    }
-    if (s.planar > 1) return bad(at + "planar must be 0 or 1");
-    if (!s.out_ptr) return bad(at + "out_ptr is NULL");
-    if ((uintptr_t)s.out_ptr & (raw_out_size(s.src, s.out) - 1u)) return bad(at + "out_ptr must be aligned to the output element size");
-    if ((uintptr_t)s.shapes & 3u) return bad(at + "shapes must be 4-byte aligned");
-    if (s.reserved) return bad(at + "reserved must be 0");
-  }
-  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
-  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
-  if ((uintptr_t)d_boxes & 3u) return bad("d_boxes must be 4-byte aligned");
-  HIP_TRY(hipSetDevice(c->device));
-  if (const int rc = confirm_pending(c)) return rc;
-  ResizeArgs a{};
-  a.rows = d_rows;
-  a.rows64 = d_rows && rows_dtype == TFRG_ROWS_I64;
-  a.m = m;
-  a.row0 = row0;
-  a.skipped = d_skipped;
-  a.boxes = d_boxes;
-  a.flips = d_flip;
-  fill_columns(c, a);
-  fill_bytes_source(c, a);
-  a.stats = d_stats;
-  a.n_specs = n_specs;
-  a.nt = (uint32_t)c->sw.dense_nt;
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_resize_spec& s = specs[i];
-    ResizeSpec& d = a.sp[i];
-    const uint32_t osz = raw_out_size(s.src, s.out);
-    d.out = s.out_ptr;
-    d.shapes = s.shapes;
-    d.fill = osz == 4 ? s.fill : s.fill & ((1u << (8 * osz)) - 1u);
-    d.slot = s.slot;
-    d.src = s.src;
-    d.outt = s.out;
-    d.channels = s.channels;
-    d.planar = s.planar;
-    d.interp = s.interp;
-    d.out_h = s.out_h;
-    d.out_w = s.out_w;
-    d.h_slot = s.h_slot;
-    d.w_slot = s.w_slot;
-    d.src_h = s.src_h;
-    d.src_w = s.src_w;
-    d.const_len = const_len_of(c, s.slot, true);
-    d.const_off = const_off_of(c, s.slot, true);
-    memcpy(d.scale, s.scale, sizeof d.scale);
-    memcpy(d.bias, s.bias, sizeof d.bias);
-  }
-  hipStream_t st, cs;
-  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
-  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
-  // (a row list over an empty result: no record to read, every row is skipped)
-  if (d_skipped)
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_skipped), c->res.req.n ? 0 : (int)m, n_specs, st));
-  // Per kernel, the blk0 table of its launch: workgroups per spec of its kind, one per band of a row, within
-  // an even share of 8 per CU (what the LDS of the common sizes lets a CU hold, and more); they stride over
-  // what is left. A spec of the other kind has no workgroup, so no block index selects it; the spec index,
-  // and with it the counters, are the call's in both launches.
-  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 8u / n_specs);
-  for (const bool aa : {false, true}) {
-    uint32_t blocks = 0, lds_words = 0;
-    for (uint32_t i = 0; i < n_specs; ++i) {
-      ResizeSpec& d = a.sp[i];
-      const bool mine = ((d.interp & kResizeAntialias) != 0) == aa;
-      const uint32_t band = aa ? resize_aa_band(d.out_w * d.channels) : kResizeBand;
-      d.bands = (d.out_h + band - 1) / band;
-      d.blk0 = blocks;
-      d.nblk = mine ? (uint32_t)std::min<uint64_t>(cap, (uint64_t)m * d.bands) : 0u;
-      blocks += d.nblk;
-      if (mine) lds_words = std::max(lds_words, (aa ? resize_aa_lds_words : resize_lds_words)(d.out_w, d.channels));
-    }
-    if (m && c->res.req.n) HIP_TRY((aa ? launch_resize_aa : launch_resize)(a, blocks, lds_words * 4u, st));
-  }
-  return fence_close(c, st, cs);
-}
-
-// ---- The tables of a mel transform (tfrg_mel.h has their layout): the windowed cos / -sin basis and the
-// filterbank, each in the order the lanes of k_mel load it, built in float64 and rounded once.
-int tfrg_mel_create(int device, uint32_t n_fft, const float* window, uint32_t n_mels, const float* fb, tfrg_mel** out) {
-  auto bad = [](const std::string& why) {
-    set_error("tfrg_mel_create: " + why);
-    return TFRG_E_ARG;
-  };
-  static_assert(TFRG_MEL_MAX_FFT == kMelMaxFft && TFRG_MEL_MAX_MELS == kMelMaxMels && TFRG_MEL_MAX_SAMPLES == kMelMaxSamples &&
-                    TFRG_MEL_MAX_FRAMES == kMelMaxFrames && TFRG_MEL_LINEAR == kMelLinear && TFRG_MEL_LN == kMelLn &&
-                    TFRG_MEL_LOG10 == kMelLog10,
-                "tfrg.h mirrors tfrg_mel.h");
-  if (!out) return bad("out is NULL");
-  *out = nullptr;
-  if (device < 0) return bad("device must be a device ordinal");
-  if (n_fft < 2 || n_fft > TFRG_MEL_MAX_FFT || (n_fft & 1u)) return bad("n_fft must be even and in 2.." + std::to_string(TFRG_MEL_MAX_FFT));
-  if (n_mels == 0 || n_mels > TFRG_MEL_MAX_MELS) return bad("n_mels must be 1.." + std::to_string(TFRG_MEL_MAX_MELS));
-  if (!window || !fb) return bad("window or fb is NULL");
-  const uint32_t n_bins = n_fft / 2 + 1, KG = mel_k16(n_fft) / kMelKGroup, NCH = mel_chunks(n_fft), MT = mel_mtiles(n_mels);
-  for (uint32_t k = 0; k < n_fft; ++k)
-    if (!std::isfinite(window[k])) return bad("window[" + std::to_string(k) + "] is not finite");
-  for (uint64_t i = 0; i < (uint64_t)n_mels * n_bins; ++i)
-    if (!std::isfinite(fb[i])) return bad("fb[" + std::to_string(i) + "] is not finite");
-  const uint64_t nb = mel_basis_words(n_fft), nf = mel_fb_words(n_fft, n_mels);
-  std::vector<float> h;
-  tfrg_mel* mel = new (std::nothrow) tfrg_mel;
-  try {
-    h.assign(nb + nf, 0.f);
-  } catch (const std::bad_alloc&) {
-    delete mel;
-    mel = nullptr;
-  }
-  if (!mel) {
-    set_error("tfrg_mel_create: out of memory");
-    return TFRG_E_NOMEM;
-  }
-  const double step = 6.283185307179586476925286766559 / (double)n_fft;
-  for (uint32_t bt = 0; bt < NCH * 4u; ++bt)
-    for (uint32_t kg = 0; kg < KG; ++kg)
-      for (uint32_t lane = 0; lane < 64; ++lane)
-        for (uint32_t j = 0; j < 4; ++j) {
-          const uint32_t k = kMelKGroup * kg + 4u * j + lane / 16u, col = lane % 16u, bin = kMelTileBins * bt + col / 2u;
-          if (k >= n_fft || bin >= n_bins) continue;
-          // (the angle reduced exactly: bin * k mod n_fft, before the trig call)
-          const double ang = step * (double)(((uint64_t)bin * k) % n_fft);
-          h[(((uint64_t)bt * KG + kg) * 64u + lane) * 4u + j] = (float)((double)window[k] * ((col & 1u) ? -std::sin(ang) : std::cos(ang)));
-        }
-  for (uint32_t mt = 0; mt < MT; ++mt)
-    for (uint32_t ch = 0; ch < NCH; ++ch)
-      for (uint32_t hh = 0; hh < 2; ++hh)
-        for (uint32_t lane = 0; lane < 64; ++lane)
-          for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t f = 16u * mt + lane % 16u, bin = kMelChunkBins * ch + 16u * hh + 4u * j + lane / 16u;
-            if (f < n_mels && bin < n_bins) h[nb + ((((uint64_t)mt * NCH + ch) * 2u + hh) * 64u + lane) * 4u + j] = fb[(uint64_t)f * n_bins + bin];
-          }
-  void* p = nullptr;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&p, h.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(p, h.data(), h.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    if (p) (void)hipFree(p);
-    delete mel;
-    set_error(std::string("tfrg_mel_create: upload: ") + hipGetErrorString(e));
-    return TFRG_E_HIP;
-  }
-  mel->device = device;
-  mel->n_fft = n_fft;
-  mel->n_mels = n_mels;
-  mel->d_mem = p;
-  mel->d_basis = static_cast<const float*>(p);
-  mel->d_fb = mel->d_basis + nb;
-  mel->device_bytes = h.size() * 4;
-  *out = mel;
-  return 0;
-}
-
-int tfrg_mel_destroy(tfrg_mel* mel) {
-  if (!mel) return 0;
-  HIP_TRY(hipSetDevice(mel->device));
-  HIP_TRY(hipDeviceSynchronize());  // (work already queued may still read the tables)
-  HIP_TRY(hipFree(mel->d_mem));
-  delete mel;
-  return 0;
-}
-
-int tfrg_mel_info(const tfrg_mel* mel, uint32_t* n_fft, uint32_t* n_mels, uint32_t* n_bins, uint64_t* device_bytes) {
-  if (!mel) {
-    set_error("tfrg_mel_info: mel is NULL");
-    return TFRG_E_ARG;
-  }
-  if (n_fft) *n_fft = mel->n_fft;
-  if (n_mels) *n_mels = mel->n_mels;
-  if (n_bins) *n_bins = mel->n_fft / 2 + 1;
-  if (device_bytes) *device_bytes = mel->device_bytes;
-  return 0;
-}
-
-uint32_t tfrg_mel_tile_frames(uint32_t n_fft, uint32_t hop) {
-  if (n_fft < 2 || n_fft > TFRG_MEL_MAX_FFT || hop == 0 || hop > n_fft) return 0;
-  return mel_tile_frames(n_fft, hop);
-}
-
-// Log-mel spectrograms for a list of rows (tfrg_mel.h): one launch of k_mel per tile size among the specs
-// (at most three). The frame is tfrg_result_raw_rows's; its own are the framing checks and the tile of a spec.
-int tfrg_result_mel(tfrg_ctx* c, const tfrg_mel_spec* specs, uint32_t n_specs, const void* d_rows, uint32_t rows_dtype,
-                    uint32_t m, int64_t row0, uint32_t* d_stats, uint32_t* d_skipped, void* consumer_stream) {
-  auto bad = [](const std::string& why) {
-    set_error("tfrg_result_mel: " + why);
-    return TFRG_E_ARG;
-  };
-  static_assert(sizeof(tfrg_mel_spec) == 88, "tfrg.h states the size");
-  if (const int rc = check_specs(c, specs, n_specs, TFRG_RAW_MAX_SPECS, bad)) return rc;
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_mel_spec& s = specs[i];
-    const std::string at = "spec " + std::to_string(i) + ": ";
-    if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
-    if (s.src >= kRawSrcs) return bad(at + "unknown src " + std::to_string(s.src));
-    if (s.out >= kRawOutSame) return bad(at + "out must be TFRG_RAW_OUT_F32, _F16 or _BF16, not " + std::to_string(s.out));
-    if (!s.mel) return bad(at + "mel is NULL");
-    if (s.mel->device != c->device)
-      return bad(at + "the tables are on device " + std::to_string(s.mel->device) + ", the context on " + std::to_string(c->device));
-    const uint32_t n_fft = s.mel->n_fft;
-    if (s.channels == 0 || s.channels > TFRG_RAW_MAX_CHANNELS) return bad(at + "channels must be 1.." + std::to_string(TFRG_RAW_MAX_CHANNELS));
-    if (s.channel >= s.channels) return bad(at + "channel must be below channels");
-    if (s.samples == 0 || s.samples > TFRG_MEL_MAX_SAMPLES) return bad(at + "samples must be 1.." + std::to_string(TFRG_MEL_MAX_SAMPLES));
-    if (s.frames == 0 || s.frames > TFRG_MEL_MAX_FRAMES) return bad(at + "frames must be 1.." + std::to_string(TFRG_MEL_MAX_FRAMES));
-    if (s.hop == 0 || s.hop > n_fft) return bad(at + "hop must be 1..n_fft");
-    if (s.center > 1) return bad(at + "center must be 0 or 1");
-    if (s.power != 1 && s.power != 2) return bad(at + "power must be 1 or 2");
-    if (s.log >= kMelLogs) return bad(at + "unknown log " + std::to_string(s.log));
-    if (s.log != TFRG_MEL_LINEAR && !(s.floor > 0.f && std::isfinite(s.floor))) return bad(at + "a log needs a finite floor > 0");
-    if (!std::isfinite(s.scale) || !std::isfinite(s.bias)) return bad(at + "scale and bias must be finite");
-    const uint64_t last = (uint64_t)(s.frames - 1) * s.hop;
-    if (s.center) {
-      if (s.samples <= n_fft / 2) return bad(at + "center reflects: samples must exceed n_fft / 2");
-      if (last > s.samples) return bad(at + "the last frame's centre lies past samples");
-    } else if (last + n_fft > s.samples) {
-      return bad(at + "the last frame ends past samples");
-    }
-    if (!s.out_ptr) return bad(at + "out_ptr is NULL");
-    if ((uintptr_t)s.out_ptr & (raw_out_size(s.src, s.out) - 1u)) return bad(at + "out_ptr must be aligned to the output element size");
-    if ((uintptr_t)s.lengths & 3u) return bad(at + "lengths must be 4-byte aligned");
-    if (s.reserved) return bad(at + "reserved must be 0");
-  }
-  if (const int rc = check_rows_dtype(d_rows, rows_dtype, false, bad)) return rc;
-  if (const int rc = check_rows_m(d_rows, m, false, bad)) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if (const int rc = confirm_pending(c)) return rc;
-  MelArgs a{};
-  a.rows = d_rows;
-  a.rows64 = d_rows && rows_dtype == TFRG_ROWS_I64;
-  a.m = m;
-  a.row0 = row0;
-  a.skipped = d_skipped;
-  fill_columns(c, a);
-  fill_bytes_source(c, a);
-  a.stats = d_stats;
-  a.n_specs = n_specs;
-  for (uint32_t i = 0; i < n_specs; ++i) {
-    const tfrg_mel_spec& s = specs[i];
-    MelSpec& d = a.sp[i];
-    d.out = s.out_ptr;
-    d.lengths = s.lengths;
-    d.basis = s.mel->d_basis;
-    d.fb = s.mel->d_fb;
-    d.fill = s.out == TFRG_RAW_OUT_F32 ? s.fill : s.fill & 0xffffu;
-    d.slot = s.slot;
-    d.src = s.src;
-    d.outt = s.out;
-    d.channels = s.channels;
-    d.channel = s.channel;
-    d.samples = s.samples;
-    d.frames = s.frames;
-    d.hop = s.hop;
-    d.n_fft = s.mel->n_fft;
-    d.n_mels = s.mel->n_mels;
-    d.center = s.center;
-    d.power = s.power;
-    d.log = s.log;
-    d.floor = s.floor;
-    d.scale = s.scale;
-    d.bias = s.bias;
-    d.hop_magic = s.hop >= 2 ? (uint32_t)((0x100000000ull + s.hop - 1) / s.hop) : 0u;
-    d.tf = mel_tile_frames(d.n_fft, d.hop);
-    d.tiles = (d.frames + d.tf - 1) / d.tf;
-    d.const_len = const_len_of(c, s.slot, true);
-    d.const_off = const_off_of(c, s.slot, true);
-  }
-  hipStream_t st, cs;
-  if (const int rc = fence_open(c, consumer_stream, &st, &cs)) return rc;
-  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_specs * 16, st));
-  // (a row list over an empty result: no record to read, every row is skipped)
-  if (d_skipped)
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_skipped), c->res.req.n ? 0 : (int)m, n_specs, st));
-  // Per tile size, the blk0 table of its launch (as tfrg_result_raw_resize's per kernel): a workgroup per
-  // work item within an even share of 2 per CU -- what the LDS of a tile lets a CU hold -- striding over the rest.
-  const uint64_t cap = std::max<uint64_t>(1, (uint64_t)c->num_cus * 2u / n_specs);
-  for (const uint32_t tf : {64u, 32u, 16u}) {
-    uint32_t blocks = 0, lds_words = 0;
-    for (uint32_t i = 0; i < n_specs; ++i) {
-      MelSpec& d = a.sp[i];
-      d.blk0 = blocks;
-      d.nblk = d.tf == tf ? (uint32_t)std::min<uint64_t>(cap, (uint64_t)m * d.tiles) : 0u;
-      blocks += d.nblk;
-      if (d.tf == tf) lds_words = std::max(lds_words, mel_lds_words(d.n_fft, d.hop, tf));
-    }
-    if (m && c->res.req.n) HIP_TRY(launch_mel(a, tf, blocks, lds_words * 4u, st));
-  }
-  return fence_close(c, st, cs);
-}
-
-// Packed values + offsets for a list of rows (tfrg_ragged.h: lengths, tile scan, gather). Every grid
-// size comes from m, n_specs, the tile and the split: nothing is read back from the device.
-int tfrg_result_ragged_rows(tfrg_ctx* c, const tfrg_ragged_spec* specs, uint32_t n_specs, const void* d_rows,
-                            uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
-                            void* consumer_stream) {
-  static_assert(TFRG_RAGGED_MAX_SPECS == kRaggedMaxSpecs, "tfrg.h mirrors tfrg_ragged.h");
-  // (the split: workgroups per tile that share its span, 1 where nothing is stored)
-  const RowListKind kind{"tfrg_result_ragged_rows", TFRG_RAGGED_MAX_SPECS, &Arena::rg_tsum, 1, 1, kRaggedMaxSplit};
-  return result_row_list<RaggedArgs>(
-      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
-      [c](const tfrg_ragged_spec& s, const std::string& at, const auto& bad, bool& any_values) -> int {
-        if (const int rc = check_slot_dtype(c, at, s.slot, s.dtype, bad)) return rc;
-        if (!s.offsets) return bad(at + "offsets is NULL");
-        if (s.reserved) return bad(at + "reserved must be 0");
-        const uintptr_t isz = s.dtype == TFRG_DENSE_I64 ? 8 : s.dtype == TFRG_DENSE_U8 ? 1 : 4;
-        if (((uintptr_t)s.values & (isz - 1)) || ((uintptr_t)s.offsets & 7u))
-          return bad(at + "values and offsets must be aligned to their element size");
-        any_values |= s.values != nullptr && s.cap != 0;
-        return 0;
-      },
-      [c, specs](RaggedArgs& a, uint32_t split, hipStream_t st) -> int {
-        a.split = split;
-        for (uint32_t i = 0; i < a.n_specs; ++i) {
-          const tfrg_ragged_spec& s = specs[i];
-          RaggedSpec& d = a.sp[i];
-          d.values = s.values;
-          d.offsets = s.offsets;
-          d.cap = s.cap;
-          d.slot = s.slot;
-          d.dtype = s.dtype;
-          d.max_len = s.max_len;
-          d.const_len = const_len_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
-          d.const_off = const_off_of(c, s.slot, s.dtype == TFRG_DENSE_U8);
-        }
-        HIP_TRY(launch_ragged(a, st));
-        return 0;
-      },
-      [m](const tfrg_ragged_spec& s, hipStream_t st) -> int {
-        HIP_TRY(hipMemsetAsync(s.offsets, 0, ((size_t)m + 1) * 8, st));
-        return 0;
-      });
-}
-
-// Every element of a bytes_list slot for a list of rows: bytes + element offsets + row offsets
-// (tfrg_elems.h: counts and byte sums, tile scan, offsets, copy). Every grid size comes from m, n_specs,
-// the tile and the split: nothing is read back from the device.
-int tfrg_result_ragged_elems(tfrg_ctx* c, const tfrg_elems_spec* specs, uint32_t n_specs, const void* d_rows,
-                             uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
-                             void* consumer_stream) {
-  static_assert(TFRG_ELEMS_MAX_SPECS == kElemsMaxSpecs, "tfrg.h mirrors tfrg_elems.h");
-  static_assert(sizeof(tfrg_elems_spec) == 56, "tfrg.h states the size");
-  // (the split: workgroups per tile that share its bytes; 0: no spec has bytes to store, and the copy
-  // is not launched)
-  const RowListKind kind{"tfrg_result_ragged_elems", TFRG_ELEMS_MAX_SPECS, &Arena::el_tsum, 2, 0, kElemsMaxSplit};
-  return result_row_list<ElemsArgs>(
-      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
-      [c](const tfrg_elems_spec& s, const std::string& at, const auto& bad, bool& any_values) -> int {
-        if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
-        if (!s.row_offsets) return bad(at + "row_offsets is NULL");
-        if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.elem_offsets & 7u))
-          return bad(at + "row_offsets and elem_offsets must be 8-byte aligned");
-        if (s.values && !s.elem_offsets) return bad(at + "values without elem_offsets");
-        if (s.reserved) return bad(at + "reserved must be 0");
-        any_values |= s.values != nullptr && s.cap != 0 && s.elem_cap != 0;
-        return 0;
-      },
-      [c, specs](ElemsArgs& a, uint32_t split, hipStream_t st) -> int {
-        a.split = split;
-        for (uint32_t i = 0; i < a.n_specs; ++i) {
-          const tfrg_elems_spec& s = specs[i];
-          ElemsSpec& d = a.sp[i];
-          d.values = s.values;
-          d.elem_offsets = s.elem_offsets;
-          d.row_offsets = s.row_offsets;
-          d.elem_cap = s.elem_cap;
-          d.cap = s.cap;
-          d.slot = s.slot;
-          d.max_elems = s.max_elems;
-          d.max_len = s.max_len;
-          d.const_len = const_len_of(c, s.slot, true);
-          d.const_off = const_off_of(c, s.slot, true);
-        }
-        HIP_TRY(launch_elems(a, st));
-        return 0;
-      },
-      [m](const tfrg_elems_spec& s, hipStream_t st) -> int {
-        HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
-        if (s.elem_offsets) HIP_TRY(hipMemsetAsync(s.elem_offsets, 0, 8, st));
-        return 0;
-      });
-}
-
-// ---- The device half of a vocabulary (tfrg_vocab.h; the host half, tfrg_host.cpp, calls it through
-// g_vocab_device). One allocation: ids, table, offsets, then the blob and zeros to a multiple of 16.
-static int vocab_upload(tfrg_vocab* v) {
-  if (v->blob.size() >= 0xfffffff0ull) {  // (the kernels read the blob through a 32-bit buffer bound)
-    set_error("tfrg_vocab_create: words of 2^32 - 16 bytes or more in all cannot go to a device");
-    return TFRG_E_ARG;
-  }
-  HIP_TRY(hipSetDevice(v->device));
-  const size_t n_ids = v->ids.size() * 8, n_tab = v->table.size() * 4, n_off = v->offs.size() * 4;
-  const size_t at_tab = n_ids, at_off = at_tab + n_tab, at_blob = (at_off + n_off + 15) & ~(size_t)15;
-  const size_t blob_room = (v->blob.size() + 16) & ~(size_t)15;
-  const size_t total = at_blob + blob_room;
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, total));
-  uint8_t* const d = static_cast<uint8_t*>(p);
-  hipError_t e = hipMemset(d + at_blob, 0, blob_room);
-  if (e == hipSuccess && n_ids) e = hipMemcpy(d, v->ids.data(), n_ids, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + at_tab, v->table.data(), n_tab, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + at_off, v->offs.data(), n_off, hipMemcpyHostToDevice);
-  if (e == hipSuccess && !v->blob.empty()) e = hipMemcpy(d + at_blob, v->blob.data(), v->blob.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    (void)hipFree(p);
-    v->d_mem = nullptr;
-    set_error(std::string("tfrg_vocab_create: upload: ") + hipGetErrorString(e));
-    return TFRG_E_HIP;
-  }
-  v->d_mem = p;
-  v->d_ids = reinterpret_cast<const int64_t*>(d);
-  v->d_table = reinterpret_cast<const uint32_t*>(d + at_tab);
-  v->d_offs = reinterpret_cast<const uint32_t*>(d + at_off);
-  v->d_blob = d + at_blob;
-  v->d_blob_bound = (uint32_t)std::min<uint64_t>(blob_room, 0xfffffff0ull);
-  v->device_bytes = total;
-  return 0;
-}
-static int vocab_release(tfrg_vocab* v) {
-  HIP_TRY(hipSetDevice(v->device));
-  HIP_TRY(hipDeviceSynchronize());  // (work already queued may still read the table)
-  HIP_TRY(hipFree(v->d_mem));
-  v->d_mem = nullptr;
-  return 0;
-}
-static const bool g_vocab_device_registered = (tfrg::g_vocab_device = {vocab_upload, vocab_release}, true);
-
-// One id per element of a bytes_list slot for a list of rows (tfrg_ids.h: counts, tile scan, row
-// offsets and ids). Every grid size comes from m, n_specs and the tile: nothing is read back.
-int tfrg_result_elem_ids(tfrg_ctx* c, const tfrg_ids_spec* specs, uint32_t n_specs, const void* d_rows,
-                         uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
-                         void* consumer_stream) {
-  static_assert(TFRG_IDS_MAX_SPECS == kIdsMaxSpecs, "tfrg.h mirrors tfrg_ids.h");
-  static_assert(sizeof(tfrg_ids_spec) == 72, "tfrg.h states the size");
-  static_assert(kIdsNoLen == kElemsNoLen && kIdsOffStored == kElemsOffStored, "const_len_of / const_off_of serve tfrg_ids.h");
-  const RowListKind kind{"tfrg_result_elem_ids", TFRG_IDS_MAX_SPECS, &Arena::id_tsum, 1, 0, 0};  // (no split)
-  return result_row_list<IdsArgs>(
-      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
-      [c](const tfrg_ids_spec& s, const std::string& at, const auto& bad, bool&) -> int {
-        if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
-        if (!s.row_offsets) return bad(at + "row_offsets is NULL");
-        if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.ids & 7u)) return bad(at + "row_offsets and ids must be 8-byte aligned");
-        if (s.reserved0 || s.reserved1) return bad(at + "reserved words must be 0");
-        if (!s.vocab && !s.num_oov_buckets) return bad(at + "no vocabulary and no hash buckets");
-        if (s.vocab && !s.vocab->d_mem) return bad(at + "the vocabulary was built host-only (device -1)");
-        if (s.vocab && s.vocab->device != c->device)
-          return bad(at + "the vocabulary is on device " + std::to_string(s.vocab->device) + ", the context on " +
-                     std::to_string(c->device));
-        return 0;
-      },
-      [c, specs](IdsArgs& a, uint32_t, hipStream_t st) -> int {
-        for (uint32_t i = 0; i < a.n_specs; ++i) {
-          const tfrg_ids_spec& s = specs[i];
-          IdsSpec& d = a.sp[i];
-          d.ids = s.ids;
-          d.row_offsets = s.row_offsets;
-          d.elem_cap = s.elem_cap;
-          if (const tfrg_vocab* v = s.vocab) {
-            d.table = v->d_table;
-            d.w_offs = v->d_offs;
-            d.blob = v->d_blob;
-            d.w_ids = v->d_ids;
-            d.mask = (uint32_t)v->table.size() - 1u;
-            d.max_probe = v->max_probe;
-            d.max_word = v->max_word;
-            d.blob_bound = v->d_blob_bound;
-          }
-          d.n_buckets = s.num_oov_buckets;
-          d.oov_base = s.oov_base;
-          d.default_id = s.default_id;
-          d.slot = s.slot;
-          d.max_elems = s.max_elems;
-          d.const_len = const_len_of(c, s.slot, true);
-          d.const_off = const_off_of(c, s.slot, true);
-        }
-        HIP_TRY(launch_ids(a, st));
-        return 0;
-      },
-      [m](const tfrg_ids_spec& s, hipStream_t st) -> int {
-        HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
-        return 0;
-      });
-}
-
-// One id per token of the elements of a bytes_list slot for a list of rows (tfrg_tokens.h: token counts,
-// tile scan, row offsets and ids). Every grid size comes from m, n_specs and the tile: nothing is read back.
-int tfrg_result_token_ids(tfrg_ctx* c, const tfrg_tok_spec* specs, uint32_t n_specs, const void* d_rows,
-                          uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
-                          void* consumer_stream) {
-  static_assert(TFRG_TOK_MAX_SPECS == kTokMaxSpecs && TFRG_TOK_LOWER_ASCII == kTokLowerAscii, "tfrg.h mirrors tfrg_tokens.h");
-  static_assert(sizeof(tfrg_tok_spec) == 88, "tfrg.h states the size");
-  static_assert(sizeof(TokArgs) < 4096, "the kernel argument");
-  static_assert(kTokNoLen == kElemsNoLen && kTokOffStored == kElemsOffStored, "const_len_of / const_off_of serve tfrg_tokens.h");
-  const RowListKind kind{"tfrg_result_token_ids", TFRG_TOK_MAX_SPECS, &Arena::tk_tsum, 1, 0, 0};  // (no split)
-  return result_row_list<TokArgs>(
-      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
-      [c](const tfrg_tok_spec& s, const std::string& at, const auto& bad, bool&) -> int {
-        if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
-        if (!s.row_offsets) return bad(at + "row_offsets is NULL");
-        if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.ids & 7u)) return bad(at + "row_offsets and ids must be 8-byte aligned");
-        if (s.flags & ~TFRG_TOK_LOWER_ASCII) return bad(at + "unknown flag bits " + std::to_string(s.flags));
-        if (!s.vocab && !s.num_oov_buckets) return bad(at + "no vocabulary and no hash buckets");
-        if (s.vocab && !s.vocab->d_mem) return bad(at + "the vocabulary was built host-only (device -1)");
-        if (s.vocab && s.vocab->device != c->device)
-          return bad(at + "the vocabulary is on device " + std::to_string(s.vocab->device) + ", the context on " +
-                     std::to_string(c->device));
-        return 0;
-      },
-      [c, specs](TokArgs& a, uint32_t, hipStream_t st) -> int {
-        a.split = c->token_split;
-        for (uint32_t i = 0; i < a.n_specs; ++i) {
-          const tfrg_tok_spec& s = specs[i];
-          TokSpec& d = a.sp[i];
-          d.ids = s.ids;
-          d.row_offsets = s.row_offsets;
-          d.tok_cap = s.tok_cap;
-          if (const tfrg_vocab* v = s.vocab) {
-            d.table = v->d_table;
-            d.w_offs = v->d_offs;
-            d.blob = v->d_blob;
-            d.w_ids = v->d_ids;
-            d.mask = (uint32_t)v->table.size() - 1u;
-            d.max_probe = v->max_probe;
-            d.max_word = v->max_word;
-            d.blob_bound = v->d_blob_bound;
-          }
-          d.n_buckets = s.num_oov_buckets;
-          d.oov_base = s.oov_base;
-          d.default_id = s.default_id;
-          const bool dflt = !s.delims[0] && !s.delims[1];  // (bytes.split()'s: 09 0a 0b 0c 0d 20)
-          d.delims[0] = dflt ? 0x100003e00ull : s.delims[0];
-          d.delims[1] = s.delims[1];
-          d.slot = s.slot;
-          d.max_elems = s.max_elems;
-          d.max_tokens = s.max_tokens;
-          d.lower = (s.flags & TFRG_TOK_LOWER_ASCII) ? 1u : 0u;
-          d.const_len = const_len_of(c, s.slot, true);
-          d.const_off = const_off_of(c, s.slot, true);
-        }
-        HIP_TRY(launch_tokens(a, st));
-        return 0;
-      },
-      [m](const tfrg_tok_spec& s, hipStream_t st) -> int {
-        HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
-        return 0;
-      });
-}
-
-// One id per WordPiece of the words of a bytes_list slot for a list of rows (tfrg_wordpiece.h: piece
-// counts, tile scan, row offsets and ids). Every grid size comes from m, n_specs and the tile: nothing is
-// read back.
-int tfrg_result_wordpiece_ids(tfrg_ctx* c, const tfrg_wp_spec* specs, uint32_t n_specs, const void* d_rows,
-                              uint32_t rows_dtype, uint32_t m, int64_t row0, uint64_t* d_totals, uint32_t* d_stats,
-                              void* consumer_stream) {
-  static_assert(TFRG_WP_MAX_SPECS == kWpMaxSpecs && TFRG_WP_LOWER_ASCII == kWpLowerAscii && TFRG_WP_SPECIAL == kWpSpecial &&
-                    TFRG_WP_MAX_WORD_BYTES == kWpMaxWordBytes,
-                "tfrg.h mirrors tfrg_wordpiece.h");
-  static_assert(sizeof(tfrg_wp_spec) == 120, "tfrg.h states the size");
-  static_assert(kWpNoLen == kElemsNoLen && kWpOffStored == kElemsOffStored, "const_len_of / const_off_of serve tfrg_wordpiece.h");
-  const RowListKind kind{"tfrg_result_wordpiece_ids", TFRG_WP_MAX_SPECS, &Arena::wp_tsum, 1, 0, 0};  // (no split)
-  return result_row_list<WpArgs>(
-      kind, c, specs, n_specs, RowListCall{d_rows, rows_dtype, m, row0, d_totals, d_stats, consumer_stream},
-      [c](const tfrg_wp_spec& s, const std::string& at, const auto& bad, bool&) -> int {
-        if (const int rc = check_bytes_slot(c, at, s.slot, bad)) return rc;
-        if (!s.row_offsets) return bad(at + "row_offsets is NULL");
-        if (((uintptr_t)s.row_offsets & 7u) || ((uintptr_t)s.ids & 7u)) return bad(at + "row_offsets and ids must be 8-byte aligned");
-        if (s.flags & ~(TFRG_WP_LOWER_ASCII | TFRG_WP_SPECIAL)) return bad(at + "unknown flag bits " + std::to_string(s.flags));
-        if (s.reserved) return bad(at + "reserved must be 0");
-        if (!s.vocab) return bad(at + "vocab is NULL");
-        for (const tfrg_vocab* v : {s.vocab, s.vocab_cont}) {
-          if (v && !v->d_mem) return bad(at + "a vocabulary was built host-only (device -1)");
-          if (v && v->device != c->device)
-            return bad(at + "a vocabulary is on device " + std::to_string(v->device) + ", the context on " + std::to_string(c->device));
-        }
-        if (s.max_word_bytes > TFRG_WP_MAX_WORD_BYTES)
-          return bad(at + "max_word_bytes must be at most " + std::to_string(TFRG_WP_MAX_WORD_BYTES));
-        if ((s.flags & TFRG_WP_SPECIAL) && s.max_pieces == 1) return bad(at + "max_pieces 1 leaves no room for cls and sep");
-        return 0;
-      },
-      [c, specs](WpArgs& a, uint32_t, hipStream_t st) -> int {
-        a.split = c->token_split;
-        for (uint32_t i = 0; i < a.n_specs; ++i) {
-          const tfrg_wp_spec& s = specs[i];
-          WpSpec& d = a.sp[i];
-          d.ids = s.ids;
-          d.row_offsets = s.row_offsets;
-          d.tok_cap = s.tok_cap;
-          const struct {
-            const tfrg_vocab* v;
-            WpTab* t;
-          } tabs[2] = {{s.vocab, &d.first}, {s.vocab_cont, &d.cont}};
-          for (const auto& e : tabs) {
-            if (!e.v) continue;
-            e.t->table = e.v->d_table;
-            e.t->w_offs = e.v->d_offs;
-            e.t->blob = e.v->d_blob;
-            e.t->w_ids = e.v->d_ids;
-            e.t->mask = (uint32_t)e.v->table.size() - 1u;
-            e.t->max_probe = e.v->max_probe;
-            e.t->max_word = e.v->max_word;
-            e.t->blob_bound = e.v->d_blob_bound;
-          }
-          const bool dflt = !s.delims[0] && !s.delims[1];  // (bytes.split()'s: 09 0a 0b 0c 0d 20)
-          d.delims[0] = dflt ? 0x100003e00ull : s.delims[0];
-          d.delims[1] = s.delims[1];
-          d.isolate[0] = s.isolate[0] & ~d.delims[0];  // (a byte in both sets is a delimiter)
-          d.isolate[1] = s.isolate[1] & ~d.delims[1];
-          d.cls_id = s.cls_id;
-          d.sep_id = s.sep_id;
-          d.unk_id = s.unk_id;
-          d.slot = s.slot;
-          d.max_elems = s.max_elems;
-          d.special = (s.flags & TFRG_WP_SPECIAL) ? 1u : 0u;
-          d.limit = !s.max_pieces ? kWpUnbounded : s.max_pieces - 2u * d.special;
-          d.lower = (s.flags & TFRG_WP_LOWER_ASCII) ? 1u : 0u;
-          d.const_len = const_len_of(c, s.slot, true);
-          d.const_off = const_off_of(c, s.slot, true);
-          d.max_word_bytes = s.max_word_bytes ? s.max_word_bytes : kWpDefaultWordBytes;
-        }
-        HIP_TRY(launch_wordpiece(a, st));
-        return 0;
-      },
-      [m](const tfrg_wp_spec& s, hipStream_t st) -> int {
-        HIP_TRY(hipMemsetAsync(s.row_offsets, 0, ((size_t)m + 1) * 8, st));
-        return 0;
-      });
-}
-
-// The WHERE clause over the last result (tfrg_select.h: verdicts, tile scan, write). Every grid size
-// comes from m and the tile: nothing is read back from the device. One implementation behind both entry
-// points: tfrg_result_select_rows is tfrg_result_select_match without patterns (`match` false: the
-// bytes subjects and the ops past GE are unknown to it).
-struct SelectCall {
-  const void* d_rows;
-  uint32_t rows_dtype, m;
-  int64_t row0;
-  void* d_out;
-  uint32_t out_dtype;
-  uint64_t cap;
-  uint64_t* d_count;
-  uint32_t* d_stats;
-  uint32_t flags;
-  void* consumer_stream;
-};
-
-static bool sel_bytes_subject(uint32_t subject) { return subject == TFRG_SEL_BYTES || subject == TFRG_SEL_BYTES_ANY; }
-
-static int result_select(const char* fn, bool match, tfrg_ctx* c, const tfrg_select_term* terms, uint32_t n_terms,
-                         const uint8_t* patterns, uint64_t patterns_len, const SelectCall& q) {
-  auto bad = [fn](const std::string& why) {
-    set_error(std::string(fn) + ": " + why);
-    return TFRG_E_ARG;
-  };
-  if (const int rc = check_result(c, bad)) return rc;
-  static_assert(TFRG_SEL_MAX_TERMS == kSelMaxTerms && TFRG_SEL_VALUE == kSelValue && TFRG_SEL_ANY == kSelAny &&
-                    TFRG_SEL_COUNT == kSelCount && TFRG_SEL_BYTES_LEN == kSelBytesLen &&
-                    TFRG_SEL_STATUS == kSelStatus && TFRG_SEL_BYTES == kSelBytes && TFRG_SEL_BYTES_ANY == kSelBytesAny &&
-                    TFRG_SEL_EQ == kSelEq && TFRG_SEL_GE == kSelGe && TFRG_SEL_PREFIX == kSelPrefix &&
-                    TFRG_SEL_SUFFIX == kSelSuffix && TFRG_SEL_CONTAINS == kSelContains &&
-                    TFRG_SEL_MAX_PATTERN == kSelMaxPattern && TFRG_SEL_MAX_PATTERN_BYTES == kSelMaxPatternBytes &&
-                    sizeof(tfrg_select_term) == 32,
-                "tfrg.h mirrors tfrg_select.h");
-  const uint32_t max_subject = match ? TFRG_SEL_BYTES_ANY : TFRG_SEL_STATUS, max_op = match ? TFRG_SEL_CONTAINS : TFRG_SEL_GE;
-  if (n_terms > TFRG_SEL_MAX_TERMS) return bad("n_terms must be at most " + std::to_string(TFRG_SEL_MAX_TERMS));
-  if (n_terms && !terms) return bad("terms is NULL");
-  if (patterns_len > TFRG_SEL_MAX_PATTERN_BYTES)
-    return bad("patterns_len must be at most " + std::to_string(TFRG_SEL_MAX_PATTERN_BYTES));
-  if (patterns_len && !patterns) return bad("patterns is NULL");
-  bool any_bytes = false;
-  for (uint32_t i = 0; i < n_terms; ++i) {
-    const tfrg_select_term& t = terms[i];
-    const std::string at = "term " + std::to_string(i) + ": ";
-    if (t.slot >= c->n_slots) return bad(at + "slot " + std::to_string(t.slot) + " >= n_slots");
-    if (t.subject > max_subject) return bad(at + "unknown subject " + std::to_string(t.subject));
-    if (t.op > max_op) return bad(at + "unknown op " + std::to_string(t.op));
-    if (t.group >= 32) return bad(at + "group must be below 32");
-    const uint32_t kind = c->slot_kind_h[t.slot] & 3u;
-    const bool list = t.subject == TFRG_SEL_VALUE || t.subject == TFRG_SEL_ANY;
-    const bool bytes = sel_bytes_subject(t.subject);
-    if ((list && kind != TFRG_KIND_INT64 && kind != TFRG_KIND_FLOAT) ||
-        ((t.subject == TFRG_SEL_BYTES_LEN || bytes) && kind != TFRG_KIND_BYTES) ||
-        (t.subject == TFRG_SEL_STATUS && t.slot != 0))
-      return bad(at + "subject " + std::to_string(t.subject) + " does not fit slot " + std::to_string(t.slot) +
-                 " of kind " + std::to_string(kind));
-    if (t.op > TFRG_SEL_GE && !bytes)
-      return bad(at + "op " + std::to_string(t.op) + " needs TFRG_SEL_BYTES or TFRG_SEL_BYTES_ANY");
-    if (t.index && t.subject != TFRG_SEL_VALUE && t.subject != TFRG_SEL_BYTES)
-      return bad(at + (match ? "index must be 0 outside TFRG_SEL_VALUE and TFRG_SEL_BYTES" : "index must be 0 outside TFRG_SEL_VALUE"));
-    if (t.reserved) return bad(at + "reserved must be 0");
-    if (list && kind == TFRG_KIND_FLOAT && (t.operand >> 32)) return bad(at + "a float operand has its high 32 bits set");
-    if (bytes) {
-      const uint64_t off = t.operand & 0xffffffffull, len = t.operand >> 32;
-      if (len > TFRG_SEL_MAX_PATTERN) return bad(at + "a pattern is at most " + std::to_string(TFRG_SEL_MAX_PATTERN) + " bytes long");
-      if (off + len > patterns_len) return bad(at + "the pattern lies outside patterns");
-      any_bytes = true;
-    }
-  }
-  if (const int rc = check_rows_dtype(q.d_rows, q.rows_dtype, false, bad)) return rc;
-  if (q.out_dtype != TFRG_ROWS_I32 && q.out_dtype != TFRG_ROWS_I64)
-    return bad("out_dtype must be TFRG_ROWS_I32 or TFRG_ROWS_I64, not " + std::to_string(q.out_dtype));
-  if (const int rc = check_rows_m(q.d_rows, q.m, false, bad)) return rc;
-  if (!q.d_count) return bad("d_count is NULL");
-  if (((uintptr_t)q.d_count & 7u) || ((uintptr_t)q.d_out & (q.out_dtype == TFRG_ROWS_I64 ? 7u : 3u)))
-    return bad("d_out and d_count must be aligned to their element size");
-  if (q.out_dtype == TFRG_ROWS_I32 && c->res.req.n &&
-      (q.row0 < (int64_t)INT32_MIN || q.row0 > (int64_t)INT32_MAX - ((int64_t)c->res.req.n - 1)))
-    return bad("rows [row0, row0 + n) do not fit an int32 output");
-  if (q.flags & ~TFRG_SEL_APPEND) return bad("unknown flag bits");
-  const bool append = (q.flags & TFRG_SEL_APPEND) != 0;
-  const uint32_t m = q.m;
-  uint32_t* const d_stats = q.d_stats;
-  HIP_TRY(hipSetDevice(c->device));
-  if (const int rc = confirm_pending(c)) return rc;
-  const uint32_t tile = c->select_tile;
-  const uint64_t tiles = ((uint64_t)m + tile - 1) / tile, nwords = ((uint64_t)m + 63) / 64;
-  const bool run = m && c->res.req.n;
-  if (run) HIP_TRY(c->sel_buf.ensure((size_t)(nwords + tiles) * 8));
-  hipStream_t st, cs;
-  if (const int rc = fence_open(c, q.consumer_stream, &st, &cs)) return rc;
-  if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, 8, st));
-  if (run) {
-    // (the bytes fields and the patterns are filled, and travel, only where a bytes term asks for them)
-    SelectBytesArgs ba{};
-    SelectArgs& a = ba.s;
-    fill_columns(c, a);
-    a.status = (c->res.implicit & TFRG_IMPLICIT_STATUS) ? nullptr : c->status.as<int32_t>();
-    a.stats = d_stats;
-    a.count = q.d_count;
-    a.words = c->sel_buf.as<uint64_t>();
-    a.tsum = a.words + nwords;
-    a.rows = q.d_rows;
-    a.out = q.d_out;
-    a.cap = q.d_out ? q.cap : 0;
-    a.row0 = q.row0;
-    a.m = m;
-    a.rows64 = q.rows_dtype == TFRG_ROWS_I64;
-    a.out64 = q.out_dtype == TFRG_ROWS_I64;
-    a.n_terms = n_terms;
-    a.tile = tile;
-    a.tiles = (uint32_t)tiles;
-    a.append = append;
-    for (uint32_t i = 0; i < n_terms; ++i) {
-      const tfrg_select_term& t = terms[i];
-      SelTerm& d = a.term[i];
-      d.slot = t.slot;
-      d.subject = t.subject;
-      d.op = t.op;
-      d.group = t.group;
-      d.index = t.index;
-      d.rhs = (int64_t)t.operand;
-      const bool list = t.subject == TFRG_SEL_VALUE || t.subject == TFRG_SEL_ANY;
-      if (list && (c->slot_kind_h[t.slot] & 3u) == TFRG_KIND_FLOAT) {
-        d.is_float = 1;
-        d.rhs_nan = sel_float_nan((uint32_t)t.operand);
-        d.rhs = d.rhs_nan ? 0 : sel_float_key((uint32_t)t.operand);
-      }
-      const bool bytes = sel_bytes_subject(t.subject);
-      d.const_len = const_len_of(c, t.slot, t.subject == TFRG_SEL_BYTES_LEN || bytes);
-      ba.const_off[i] = const_off_of(c, t.slot, bytes);
-      a.all_groups |= 1u << t.group;
-    }
-    if (any_bytes) {
-      static_assert(kDenseOffStored == kSelOffStored, "const_off_of serves select too");
-      fill_bytes_source(c, ba);
-      ba.scan_min = c->select_scan;
-      if (patterns_len) memcpy(ba.pat, patterns, (size_t)patterns_len);
-      HIP_TRY(launch_select_bytes(ba, st));
-    } else {
-      HIP_TRY(launch_select(a, st));
-    }
-  } else {
-    // no candidate, or no record (every candidate is skipped): nothing is selected
-    if (!append) HIP_TRY(hipMemsetAsync(q.d_count, 0, 8, st));
-    if (d_stats && m) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 1), (int)m, 1, st));
-  }
-  return fence_close(c, st, cs);
-}
-
-int tfrg_result_select_rows(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t n_terms, const void* d_rows,
-                            uint32_t rows_dtype, uint32_t m, int64_t row0, void* d_out, uint32_t out_dtype,
-                            uint64_t cap, uint64_t* d_count, uint32_t* d_stats, uint32_t flags, void* consumer_stream) {
-  return result_select("tfrg_result_select_rows", false, c, terms, n_terms, nullptr, 0,
-                       SelectCall{d_rows, rows_dtype, m, row0, d_out, out_dtype, cap, d_count, d_stats, flags, consumer_stream});
-}
-
-int tfrg_result_select_match(tfrg_ctx* c, const tfrg_select_term* terms, uint32_t n_terms, const uint8_t* patterns,
-                             uint64_t patterns_len, const void* d_rows, uint32_t rows_dtype, uint32_t m, int64_t row0,
-                             void* d_out, uint32_t out_dtype, uint64_t cap, uint64_t* d_count, uint32_t* d_stats,
-                             uint32_t flags, void* consumer_stream) {
-  return result_select("tfrg_result_select_match", true, c, terms, n_terms, patterns, patterns_len,
-                       SelectCall{d_rows, rows_dtype, m, row0, d_out, out_dtype, cap, d_count, d_stats, flags, consumer_stream});
 }
 
 int tfrg_result_fetch(tfrg_ctx* c, const tfrg_columns* h) {

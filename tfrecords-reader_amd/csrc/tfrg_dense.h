@@ -1,6 +1,6 @@
 // tfrg_dense.h — arguments of k_dense (tfrg_dense.hip), the collate kernel behind tfrg_result_dense
 // and tfrg_result_dense_rows: ragged result columns -> fixed-shape [n][width] outputs, or [m][width]
-// outputs whose row k is record rows[k] - row0. Shared with tfrg_capi.cpp only.
+// outputs whose row k is record rows[k] - row0. Shared with tfrg_fixed.cpp and, for the sentinels, tfrg_ctx.h only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

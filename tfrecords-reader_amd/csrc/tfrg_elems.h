@@ -1,6 +1,6 @@
 // tfrg_elems.h — arguments of the four kernels of tfrg_elems.hip behind tfrg_result_ragged_elems: every
 // element of a bytes_list slot for a list of rows, as packed bytes + element offsets ([E + 1]) + row
-// offsets ([m + 1], in elements). Shared with tfrg_capi.cpp only.
+// offsets ([m + 1], in elements). Shared with tfrg_rowlist.cpp and, for the sentinels and the defaults, tfrg_ctx.h only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // tfrg_ids.h — arguments of the three kernels of tfrg_ids.hip behind tfrg_result_elem_ids: one int64 id
 // per element of a bytes_list slot for a list of rows (a vocabulary lookup, hash buckets, or both), with
-// the row offsets ([m + 1], in elements) of tfrg_result_ragged_elems. Shared with tfrg_capi.cpp only.
+// the row offsets ([m + 1], in elements) of tfrg_result_ragged_elems. Shared with tfrg_rowlist.cpp only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

@@ -1,5 +1,6 @@
 // tfrg_internal.h — device-side views shared by the kernel files, their launch policy
-// (tfrg_decode.cpp) and the C-ABI orchestration (tfrg_capi.cpp). Not part of the public ABI (include/tfrg.h is).
+// (tfrg_decode.cpp) and the C-ABI orchestration (tfrg_capi.cpp, tfrg_fixed.cpp and tfrg_rowlist.cpp, through
+// tfrg_ctx.h). Not part of the public ABI (include/tfrg.h is).
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

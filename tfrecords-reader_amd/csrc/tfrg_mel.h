@@ -1,7 +1,7 @@
 // tfrg_mel.h — arguments of k_mel (tfrg_mel.hip), the kernel behind tfrg_result_mel: element 0 of a
 // bytes_list slot read as a PCM signal, framed, transformed by a windowed DFT (a matrix product on the
 // MFMA units), |X|^power, a mel filterbank (a second matrix product), an optional log, scale and bias,
-// written as [m][n_mels][frames] for a list of rows. Also the geometry that the host (tfrg_capi.cpp: the
+// written as [m][n_mels][frames] for a list of rows. Also the geometry that the host (tfrg_fixed.cpp: the
 // tables of a tfrg_mel, the tile and the LDS of a launch) and the kernel must agree on, each defined once.
 #pragma once
 #include <stdint.h>

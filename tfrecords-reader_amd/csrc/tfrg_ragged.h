@@ -1,6 +1,6 @@
 // tfrg_ragged.h — arguments of the three kernels of tfrg_ragged.hip behind tfrg_result_ragged_rows:
 // the ragged columns of a decoded batch as packed values + offsets ([m + 1], cu_seqlens) for a list of
-// rows. Shared with tfrg_capi.cpp only.
+// rows. Shared with tfrg_rowlist.cpp and, for the sentinels and the defaults, tfrg_ctx.h only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // tfrg_raw.h — arguments of k_raw (tfrg_raw.hip), the kernel behind tfrg_result_raw_rows: element 0 of
 // a bytes_list slot read as a tensor of a fixed element type (tf.io.decode_raw), cast, scaled per
 // channel and written as [m][count] rows, interleaved or planar (HWC -> CHW), for a list of rows.
-// Shared with tfrg_capi.cpp only.
+// Shared with tfrg_fixed.cpp only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

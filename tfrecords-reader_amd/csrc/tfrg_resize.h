@@ -3,7 +3,7 @@
 // element 0 of a bytes_list slot read as an H x W x channels image whose H and W are int64 features of the
 // same record, a per-row crop window resampled (bilinear or nearest, optionally mirrored) to a fixed
 // out_h x out_w, normalised per channel and written interleaved or planar, for a list of rows.
-// Shared with tfrg_capi.cpp only.
+// Shared with tfrg_fixed.cpp only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

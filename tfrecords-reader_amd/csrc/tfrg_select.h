@@ -1,6 +1,7 @@
 // tfrg_select.h — arguments of the three kernels of tfrg_select.hip behind tfrg_result_select_rows and
 // tfrg_result_select_match: predicates over the decoded columns of a list of candidate rows in, the
-// entries of the passing candidates compacted into a device row list out. Shared with tfrg_capi.cpp only.
+// entries of the passing candidates compacted into a device row list out. Shared with tfrg_rowlist.cpp
+// and, for the sentinels and the defaults, tfrg_ctx.h only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

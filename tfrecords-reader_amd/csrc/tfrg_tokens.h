@@ -1,7 +1,7 @@
 // tfrg_tokens.h — arguments of the three kernels of tfrg_tokens.hip behind tfrg_result_token_ids: the
 // elements of a bytes_list slot split into tokens at ASCII delimiter bytes, one int64 id per token (the
 // id rule of tfrg_ids.h) and the row offsets ([m + 1], in tokens) for a list of rows. Shared with
-// tfrg_capi.cpp only.
+// tfrg_rowlist.cpp and, for the default split, tfrg_ctx.h only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // tfrg_vocab.h — tfrg_hash64 and the vocabulary object (include/tfrg.h: tfrg_vocab), as host C, the
 // device (tfrg_ids.hip) and the C-ABI share them. No HIP header is needed: tfrg_host.cpp, which builds
 // the table and looks words up on the host, is plain C++. The device half (upload, free) lives in
-// tfrg_capi.cpp and reaches the host half through g_vocab_device.
+// tfrg_rowlist.cpp and reaches the host half through g_vocab_device.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -75,7 +75,7 @@ struct tfrg_vocab {
 };
 
 namespace tfrg {
-// The device half, registered by tfrg_capi.cpp where it is linked in (a program of the host files alone
+// The device half, registered by tfrg_rowlist.cpp where it is linked in (a program of the host files alone
 // has none: tfrg_vocab_create then refuses device >= 0). Both return a TFRG_* code and set the error.
 struct VocabDeviceOps {
   int (*upload)(tfrg_vocab* v);

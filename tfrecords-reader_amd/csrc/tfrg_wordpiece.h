@@ -1,7 +1,7 @@
 // tfrg_wordpiece.h — arguments of the three kernels of tfrg_wordpiece.hip behind tfrg_result_wordpiece_ids:
 // the elements of a bytes_list slot split into words (delimiters, isolated punctuation), every word cut
 // greedily into the longest pieces of two vocabularies, one int64 id per piece and the row offsets
-// ([m + 1], in pieces) for a list of rows. Shared with tfrg_capi.cpp only.
+// ([m + 1], in pieces) for a list of rows. Shared with tfrg_rowlist.cpp only.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
